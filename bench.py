@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """GNOT fwd+bwd training-step benchmark on MI355X (the driver's bench contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps, write
+the last step's outputs (--dump-outputs), print the result line.  --full adds everything else to the same
+line: the per-class device-time profile and the live roofline (`roofline`, --breakdown, --roofline-kernel),
+the companion bf16-mode measurement of the default fp32 run (`bf16_mode`) and the CPU baseline
+(`cpu_baseline`).
 
 Default workload = BASELINE.json configs[2], the largest configuration that fits one GPU: a synthetic
 3-D mesh of 262,144 query points, GNOT with d=256, 8 experts, 8 heads, 4 blocks, 4-layer MLPs and one
@@ -21,6 +27,13 @@ functions, 10k points), cfg4 = configs[3] (at N=1: the whole 1M mesh on one GPU,
 cfg5 = configs[4] (64 variable meshes, LPT sample-DP).  --points / --meshes resize.
 
 value = all query points processed by all ranks / max-over-ranks wall time of the K timed steps.
+--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy in float32 (rank 0): `out` (the
+prediction at every query point of the rank), `loss`, `grads` (every parameter gradient, W0, b0, W1, b1, ...
+in state_dict order, flattened) and `params` (the parameters after the step's AdamW update, same order).  An
+array of more than DUMP_MAX_ELEMS elements is written as a fixed seeded sample of its elements.  The data,
+the initial weights and the number of steps depend only on the arguments, so two builds run with the same
+arguments can be compared array by array.
+The next three are reported with --full only.
 roofline: the kernel class with the most device time in an untimed profiled step (normally the
 weight-gradient GEMMs or the MoE chain backward), timed live with hipEvents on the stream it runs on
 during the timed steps; achieved = its algorithmic FLOPs per launch / average launch duration; frac =
@@ -268,6 +281,24 @@ def cpu_baseline(w, steps=5, warmup=2):
                        f"points/s is flat in the mesh size (linear attention)")
 
 
+DUMP_MAX_ELEMS = 4 * 2 ** 20   # per dumped array (16 MiB of float32; four arrays stay below 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy (float32, flattened).  A tensor of more than DUMP_MAX_ELEMS
+    elements is written as a sample: the elements at DUMP_MAX_ELEMS sorted indices drawn without
+    replacement by a generator seeded with 0, the same indices in every run for the same size."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -339,24 +370,31 @@ def main():
                          "under torchrun it must equal WORLD_SIZE.  Default: WORLD_SIZE, else 1")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (prediction, loss, parameter "
+                         "gradients, updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-class profile and live "
+                         "roofline, the bf16-mode companion of the default fp32 run, the CPU baseline")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: cfg3 (configs[2], one 262,144-point mesh) at one GPU; cfg4 (configs[3], ONE "
                          "1,048,576-point mesh point-sharded over the GPUs: north_star's strong-scaling curve) at N > 1")
     ap.add_argument("--points", type=int, default=0, help="override points per sample")
     ap.add_argument("--meshes", type=int, default=0, help="cfg5: override the number of meshes")
     ap.add_argument("--roofline-kernel", default="auto", choices=["auto", "moe_fwd", "moe_bwd", "wgrad", "wgrad_b16"],
-                    help="kernel class timed live for the roofline (auto: the one with the most device time)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: kernel class timed live for the roofline (auto: the one with the most device time)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--torch-adamw", action="store_true", help="torch's fused AdamW instead of the native one")
-    ap.add_argument("--breakdown", action="store_true", help="print per-kernel-class device time to stderr")
+    ap.add_argument("--breakdown", action="store_true",
+                    help="with --full: print per-kernel-class device time to stderr")
     ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
                     help="fp32: the reference's arithmetic (bf16x6-exact MFMA); bf16: configs[2]'s bf16 training "
                          "(one RNE bf16 operand per MFMA in the chains / projections / weight gradients up to d=256, "
                          "fp32 accumulation; at d=256 the soft-MoE chains keep their saves, dZ and Linear inputs in "
                          "bf16; north_star's 1e-2 bar, tests/test_gpu_bf16.py)")
     ap.add_argument("--fp32-only", action="store_true",
-                    help="skip the companion bf16-mode measurement of the default fp32 run (configs[2], N=1)")
+                    help="--full without the companion bf16-mode measurement of the default fp32 run (configs[2], N=1)")
     ap.add_argument("--recompute", choices=["auto", "on", "off"], default="auto",
                     help="MoE activation recompute (GNOT.set_moe_recompute); auto: on when the plain workspace "
                          "would not fit the GPU (configs[3]'s 1M-point mesh on one GPU)")
@@ -364,6 +402,8 @@ def main():
                     help="variable-mesh workloads: a new mesh order (hence new packed offsets) every step, as "
                          "main.py:41's shuffled DataLoader does; eager launches")
     args = ap.parse_args()
+    if not args.full and (args.breakdown or args.roofline_kernel != "auto"):
+        ap.error("--breakdown and --roofline-kernel belong to the profiled run: add --full")
 
     world, rank, local = resolve_world(args)
     # rehearsal knobs for the multi-process path on a one-GPU box (the real run is RCCL, one GPU per
@@ -462,6 +502,8 @@ def main():
     # inside it)] -> [AdamW].  With hipGraphs the two bracketed parts are captured once and replayed
     # (RCCL kernels included); GNOT_BENCH_FLAT_ALLREDUCE=1 keeps one eager all-reduce of the flat gradient
     # buffer between them instead.
+    last = {}
+
     def fwd_bwd():
         nonlocal x, x_off, theta, fns, fn_offs, y
         if batches is not None:
@@ -478,6 +520,9 @@ def main():
         if args.torch_adamw:
             opt.zero_grad(set_to_none=True)
         loss.backward()
+        # what a caller of the step receives (--dump-outputs); under graph replay these are the capture's
+        # tensors, which every replay rewrites
+        last["out"], last["loss"] = out.detach(), loss.detach()
         return loss
 
     def opt_step():
@@ -574,18 +619,9 @@ def main():
         eng = model.engine()
         eng.param_grads = bool(args.torch_adamw)
 
-    def measure():
-        """warm-up, class profile, capture, K timed steps -> timing of the current precision"""
-        # warm-up (also the capture warm-up: allocations, plan binding, optimizer state)
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            for _ in range(max(args.warmup, 2)):
-                eager_step()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize()
-        print("[bench] warm-up done", file=sys.stderr, flush=True)
-        # which kernel class dominates device time: one profiled eager step per class (untimed)
+    def class_profile():
+        """one profiled eager step per kernel class (untimed) -> ({class: (ms, launches, flops)}, the class
+        the roofline follows)"""
         kinds = {}
         classes = ("moe_fwd", "moe_bwd", "wgrad") + (("wgrad_b16",) if eng.bf16 and m["n_attn_hidden_dim"] == 256 else ())
         for kind in classes:
@@ -605,16 +641,35 @@ def main():
             # bf16 mode: the soft-MoE weight gradients are their own class (wgrad_b16)
             pick = list(kinds)
             rkind = max(pick, key=lambda k: kinds[k][0])
+        return kinds, rkind
+
+    def measure():
+        """warm-up, class profile (--full), capture, K timed steps -> timing of the current precision"""
+        # warm-up (also the capture warm-up: allocations, plan binding, optimizer state)
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for _ in range(max(args.warmup, 2)):
+                eager_step()
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize()
+        print("[bench] warm-up done", file=sys.stderr, flush=True)
+        # --full: which kernel class dominates device time, one profiled eager step per class (untimed).
+        # A plain run profiles nothing: rkind "" keeps the engine's event recording off throughout
+        kinds, rkind = {}, ""
+        if args.full:
+            kinds, rkind = class_profile()
 
         step = eager_step
         if use_graph:
             # the roofline kernel's hipEvent pairs are recorded inside the captured graph, so the timed
             # replays carry them (the pool of events exists from one eager profiled step)
-            eng.profile_enable(rkind)
-            eager_step()
-            eng.profile_read()
-            torch.cuda.synchronize()
-            eng.profile_enable(rkind)
+            if rkind:
+                eng.profile_enable(rkind)
+                eager_step()
+                eng.profile_read()
+                torch.cuda.synchronize()
+                eng.profile_enable(rkind)
             g_fb, g_opt = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             print("[bench] capturing", file=sys.stderr, flush=True)
             if comm is not None and int(os.environ.get("GNOT_BENCH_FAIL_CAPTURE", "0")) > 0:
@@ -649,11 +704,12 @@ def main():
                 rebuild_engine()
                 g_fb = g_opt = None
                 torch.cuda.synchronize()
-                eng.profile_enable(rkind)
-                eager_step()                  # the new plan's event pool for the profiled class
-                eng.profile_read()
-                torch.cuda.synchronize()
-                eng.profile_enable(rkind)
+                if rkind:
+                    eng.profile_enable(rkind)
+                    eager_step()              # the new plan's event pool for the profiled class
+                    eng.profile_read()
+                    torch.cuda.synchronize()
+                    eng.profile_enable(rkind)
             print("[bench] captured" if captured else "[bench] eager", file=sys.stderr, flush=True)
 
             def graph_step():
@@ -683,17 +739,23 @@ def main():
         elapsed = time.perf_counter() - t0
         # eager: summed over every timed step; graph: the events hold the LAST replay's launches, and
         # launches/flops are those of one step -> both give the average launch duration
-        kms, klaunch, kflops = eng.profile_read()
+        kms, klaunch, kflops = eng.profile_read() if rkind else (0.0, 0, 0.0)
         eng.profile_enable("")
         if world > 1:
             t = torch.tensor([elapsed], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         return dict(elapsed=elapsed, kinds=kinds, rkind=rkind, kms=kms, klaunch=klaunch, kflops=kflops,
-                    klaunch_step=kinds[rkind][1])
+                    klaunch_step=kinds[rkind][1] if rkind else 0)
 
     M0 = measure()
     elapsed, kinds, rkind, kms, klaunch, kflops = (M0[k] for k in ("elapsed", "kinds", "rkind", "kms", "klaunch", "kflops"))
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything else runs on the model
+        dump_outputs(args.dump_outputs, {
+            "out": last["out"], "loss": last["loss"],
+            "grads": torch.cat([g.reshape(-1) for wb in eng.grad_views for g in wb]),
+            "params": torch.cat([p.detach().reshape(-1) for l in model.linears() for p in (l.weight, l.bias)])})
     pts = D["step_points"] * args.steps
     result = {
         "metric": "mesh points/sec (GNOT fwd+bwd, whole node)",
@@ -719,9 +781,10 @@ def main():
                    "parallelism": (f"point-shard{world}" if shard else f"sample-dp{world}") if (world > 1 or shard) else "single",
                    "step": "pack+fwd+RelL2+bwd+AdamW (native loss, " + ("torch fused AdamW" if args.torch_adamw else "native flat AdamW") + ")" + (" (hipGraph replay)" if M_graph["on"] else " (eager)")
                            + (f"; graph capture failed ({M_graph['fail']}): fresh engine, eager steps" if M_graph["fail"] else "")},
-        "roofline": roofline(M0, args.dtype),
     }
-    if (args.dtype == "fp32" and not args.fp32_only and world == 1 and m["n_attn_hidden_dim"] == 256
+    if args.full:
+        result["roofline"] = roofline(M0, args.dtype)
+    if (args.full and args.dtype == "fp32" and not args.fp32_only and world == 1 and m["n_attn_hidden_dim"] == 256
             and batches is None and not args.torch_adamw):
         # BASELINE configs[2] names bf16 training: the same workload in the bf16 arithmetic mode, timed the
         # same way on the same model and optimizer (the headline `value` above stays the fp32 path)
@@ -738,7 +801,7 @@ def main():
             "roofline": roofline(M1, "bf16"),
         }
         model.set_precision("fp32")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(w)
     if rank == 0:
         print(json.dumps(result), flush=True)

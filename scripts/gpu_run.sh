@@ -43,7 +43,7 @@ for step in "$@"; do
       rc=$?; tail -c 1500 $out.json; [ $rc -eq 0 ] || tail -20 $out.err ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$out" -o run \
-        -- python3 bench.py --no-cpu-baseline $arg > $out.log 2>&1
+        -- python3 bench.py --full --no-cpu-baseline $arg > $out.log 2>&1
       rc=$?; tail -3 $out.log ;;
     mb)
       timeout -k 10 300 gnot-replication_amd/lib/microbench $arg > $out.log 2>&1

@@ -63,6 +63,30 @@ def test_spawn_ranks_runs_n_children(clean_env, tmp_path):
     assert got == [f"{r} {r} 3 127.0.0.1 --gpus 3" for r in range(3)]
 
 
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    small = torch.arange(12, dtype=torch.float64).view(3, 4)
+    big = torch.arange(5000, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    a_small, a_big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_small.dtype == np.float32 and a_big.dtype == np.float32
+    assert a_small.tolist() == list(range(12))
+    # the sample: 1000 distinct elements in index order, the same ones in every run
+    assert a_big.shape == (1000,) and (np.diff(a_big) > 0).all() and a_big.max() < 5000
+    assert (a_big == np.load(tmp_path / "b" / "big.npy")).all()
+
+
+@pytest.mark.parametrize("flag", [["--breakdown"], ["--roofline-kernel", "wgrad"]])
+def test_profile_options_need_full(clean_env, monkeypatch, capsys, flag):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + flag)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2 and "--full" in capsys.readouterr().err
+
+
 def test_spawn_ranks_reports_failure(clean_env, tmp_path):
     script = tmp_path / "rank.py"
     script.write_text(textwrap.dedent("""
