@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2432,6 +2433,48 @@ extern "C" int gnot_adamw_step(float* param, const float* grad, float* exp_avg, 
                                const float* hyper, void* stream) {
   if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || !hyper) return fail(GNOT_E_INVALID, "bad adamw arguments");
   GNOT_CK(launch_adamw(param, grad, exp_avg, exp_avg_sq, n, hyper, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" size_t gnot_mse_work_floats(const int64_t* off_host, int B, int C) {
+  if (!off_host || B <= 0 || C <= 0) return 0;
+  std::vector<long> off(off_host, off_host + B + 1);
+  return (size_t)B * rel_l2_splits(off.data(), B) * C;
+}
+
+extern "C" int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
+                             int B, int C, float* work, float* loss, float* dpred, void* stream) {
+  if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
+    return fail(GNOT_E_INVALID, "bad mse arguments");
+  std::vector<long> off(off_host, off_host + B + 1);
+  if (off[0] != 0) return fail(GNOT_E_INVALID, "off[0] must be 0");
+  for (int b = 0; b < B; ++b) {
+    if (off[b + 1] < off[b]) return fail(GNOT_E_INVALID, "offsets must be non-decreasing");
+    if (off[b + 1] == off[b]) return fail(GNOT_E_INVALID, "empty sample: its mean over points is undefined");
+  }
+  GNOT_CK(launch_mse(pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
+                     work, loss, dpred, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" size_t gnot_grad_clip_work_floats(int64_t n) { return (size_t)grad_clip_partials(n); }
+
+extern "C" int gnot_grad_clip(const float* grad, int64_t n, const float* hyper, float max_norm, float* work,
+                              float* clip, void* stream) {
+  if (!grad || !hyper || !work || !clip) return fail(GNOT_E_INVALID, "bad grad_clip arguments");
+  // stage 1 launches one workgroup of 256 threads per partial: 2^32 threads per grid at the most
+  if (n < 1 || grad_clip_partials(n) >= (1L << 24)) return fail(GNOT_E_INVALID, "grad_clip: n out of range");
+  if (!(max_norm > 0.f) || !std::isfinite(max_norm))
+    return fail(GNOT_E_INVALID, "grad_clip: max_norm must be positive and finite");
+  GNOT_CK(launch_grad_clip(grad, n, hyper, max_norm, work, clip, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_adamw_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                       const float* hyper, const float* clip, void* stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || !hyper || !clip)
+    return fail(GNOT_E_INVALID, "bad adamw arguments");
+  GNOT_CK(launch_adamw_clipped(param, grad, exp_avg, exp_avg_sq, n, hyper, clip, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

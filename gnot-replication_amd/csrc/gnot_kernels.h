@@ -292,5 +292,15 @@ hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_de
                          long rows, float* work, float* loss, float* dpred, hipStream_t s);
 hipError_t launch_adamw(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
                         hipStream_t s);
+// work: B*nsplit*C floats (nsplit = rel_l2_splits); every sample must have at least one row
+hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
+                      float* work, float* loss, float* dpred, hipStream_t s);
+// stage-1 partial sums of sum g^2 over n elements (a function of n alone); 0 for n < 1
+long grad_clip_partials(long n);
+// work: grad_clip_partials(n) floats; clip: 2 floats {norm, coefficient}
+hipError_t launch_grad_clip(const float* grad, long n, const float* hyper, float max_norm, float* work, float* clip,
+                            hipStream_t s);
+hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
+                                const float* clip, hipStream_t s);
 
 }  // namespace gnot

@@ -8,6 +8,10 @@
 //             over ONE flat fp32 arena of parameters / gradients / moments, in torch's op order.
 //             Hyper-parameters come from a small device array so a captured hipGraph replays
 //             whatever the host's schedule (OneCycleLR, main.py:52/106) wrote there.
+//   mse_*     MSELoss (reference loss.py:4-12): per-sample means of (p - t)^2 (dgl AvgPooling), in the
+//             shape of the rel_l2 passes.
+//   grad_clip global L2 norm of the flat gradient and torch.nn.utils.clip_grad_norm_'s coefficient, on
+//             the device (two fixed-order stages), consumed by adamw_clipped_kernel.
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
@@ -113,6 +117,159 @@ hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_de
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- MSELoss (reference loss.py:4-12)
+// dgl AvgPooling of (p - t)^2 = per-sample mean over points, then the mean over (sample, channel); the
+// passes have the shape of the RelL2 ones above (which stay as they are, bit for bit).
+// partial[b][split][0..C) = sum (p-t)^2 over the split's rows of sample b
+__global__ void __launch_bounds__(256) mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                          const long* __restrict__ off, int C, int nsplit,
+                                                          float* __restrict__ partial) {
+  __shared__ float red[256];
+  const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
+  const long r0 = off[b] + (long)split * kLossRows;
+  const long r1 = min(off[b + 1], r0 + kLossRows);
+  for (int c = 0; c < C; ++c) {
+    float num = 0.f;
+    for (long r = r0 + threadIdx.x; r < r1; r += 256) {
+      const float d = pred[r * C + c] - tgt[r * C + c];
+      num = fmaf(d, d, num);
+    }
+    red[threadIdx.x] = num;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[((long)b * nsplit + split) * C + c] = red[0];
+    __syncthreads();
+  }
+}
+
+// one workgroup: sum per (b, c) in split order, loss = 1/(B C) sum_b sum_c num / N_b
+__global__ void __launch_bounds__(256) mse_finish_kernel(const float* __restrict__ partial,
+                                                         const long* __restrict__ off, int B, int C, int nsplit,
+                                                         float* __restrict__ loss) {
+  __shared__ float red[256];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < B * C; i += 256) {
+    const int b = i / C, c = i % C;
+    float num = 0.f;
+    for (int s = 0; s < nsplit; ++s) num += partial[((long)b * nsplit + s) * C + c];
+    acc += num / (float)(off[b + 1] - off[b]);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss = red[0] / (float)(B * C);
+}
+
+// d loss / d pred = 2 (p - t) / (B C N_b)
+__global__ void __launch_bounds__(256) mse_grad_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                       const long* __restrict__ off, int B, int C,
+                                                       float* __restrict__ dpred, long rows) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * C) return;
+  const long r = i / C;
+  int lo = 0, hi = B - 1;                           // sample of row r
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= r) lo = mid; else hi = mid - 1;
+  }
+  dpred[i] = (pred[i] - tgt[i]) * (2.0f / ((float)(B * C) * (float)(off[lo + 1] - off[lo])));
+}
+
+// work: B*nsplit*C floats
+hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
+                      float* work, float* loss, float* dpred, hipStream_t s) {
+  hipLaunchKernelGGL(mse_partial_kernel, dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev, C, nsplit, work);
+  hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)work, off_dev, B, C, nsplit, loss);
+  if (dpred && rows > 0)
+    hipLaunchKernelGGL(mse_grad_kernel, dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s, pred, tgt, off_dev,
+                       B, C, dpred, rows);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- global gradient norm and clip coefficient
+// torch.nn.utils.clip_grad_norm_ (L2, error_if_nonfinite=False) over the flat gradient arena, on the device.
+// Stage 1: workgroup k sums g^2 over elements [k kClipSlice, (k + 1) kClipSlice) -- the number of partials
+// depends on n alone, never on the device -- in a fixed order; stage 2: one workgroup sums the partials in
+// index order.  No atomics: the same pointer and n give the same bits every run.
+constexpr long kClipSlice = 8192;   // elements per stage-1 workgroup: 8 float4 loads per thread
+
+long grad_clip_partials(long n) { return n < 1 ? 0 : (n + kClipSlice - 1) / kClipSlice; }
+
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ grad, long n,
+                                                         float* __restrict__ partial) {
+  __shared__ float red[256];
+  const long s0 = (long)blockIdx.x * kClipSlice;
+  const int len = (int)min(kClipSlice, n - s0);
+  const float* p = grad + s0;
+  // 16-byte loads over the aligned body of the slice; the (up to 3) elements before and after it one by one
+  const int head = min(len, (int)((4 - (((uintptr_t)p >> 2) & 3)) & 3));
+  const int body4 = (len - head) >> 2;
+  const int tail = len - head - 4 * body4;
+  const float4* q = reinterpret_cast<const float4*>(p + head);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 8
+  for (int j = threadIdx.x; j < body4; j += 256) {
+    const float4 g = q[j];
+    a0 = fmaf(g.x, g.x, a0);
+    a1 = fmaf(g.y, g.y, a1);
+    a2 = fmaf(g.z, g.z, a2);
+    a3 = fmaf(g.w, g.w, a3);
+  }
+  if ((int)threadIdx.x < head) {
+    const float g = p[threadIdx.x];
+    a0 = fmaf(g, g, a0);
+  }
+  if ((int)threadIdx.x < tail) {
+    const float g = p[head + 4 * body4 + threadIdx.x];
+    a1 = fmaf(g, g, a1);
+  }
+  red[threadIdx.x] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// clip[0] = |grad_scale| sqrt(sum g^2), the norm of the gradient AdamW consumes (hyper[7] scales it);
+// clip[1] = min(1, max_norm / (norm + 1e-6)) as torch clamps it: a NaN norm stays a NaN coefficient
+__global__ void __launch_bounds__(256) grad_clip_finish_kernel(const float* __restrict__ partial, long nparts,
+                                                               const float* __restrict__ hyper, float max_norm,
+                                                               float* __restrict__ clip) {
+  __shared__ float red[256];
+  float acc = 0.f;
+  for (long i = threadIdx.x; i < nparts; i += 256) acc += partial[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = fabsf(hyper[7]) * sqrtf(red[0]);
+    const float c = max_norm / (norm + 1e-6f);
+    clip[0] = norm;
+    clip[1] = c > 1.0f ? 1.0f : c;
+  }
+}
+
+// work: grad_clip_partials(n) floats
+hipError_t launch_grad_clip(const float* grad, long n, const float* hyper, float max_norm, float* work, float* clip,
+                            hipStream_t s) {
+  const long nparts = grad_clip_partials(n);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nparts), dim3(256), 0, s, grad, n, work);
+  hipLaunchKernelGGL(grad_clip_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)work, nparts, hyper, max_norm,
+                     clip);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- AdamW over a flat arena
 // hyper = {lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, grad_scale}
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ param, const float* __restrict__ grad,
@@ -141,6 +298,46 @@ hipError_t launch_adamw(float* param, const float* grad, float* m, float* v, lon
   if (n <= 0) return hipSuccess;
   const long blocks = std::min<long>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper);
+  return hipGetLastError();
+}
+
+// adamw_kernel on the clipped gradient (grad[i] * grad_scale) * clip[1]; clip is what launch_grad_clip wrote,
+// read from device memory so a captured graph applies the coefficient of the step it replays.  Everything
+// after g is adamw_kernel's operation order: a coefficient of 1.0f gives its bits whenever grad[i] * grad_scale
+// is exact (a grad_scale of 1, which FlatAdamW writes, or any power of two).
+__global__ void __launch_bounds__(256) adamw_clipped_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                            float* __restrict__ m, float* __restrict__ v, long n,
+                                                            const float* __restrict__ hyper,
+                                                            const float* __restrict__ clip) {
+  // Which multiply-adds of adamw_kernel's expressions the compiler fuses depends on the code around them
+  // (the extra multiply here moved one), so the fusions it applies there are written out and no others
+  // are allowed: exp_avg_sq = fma(g, (1 - beta2) g, beta2 v), the rest as the expressions read.
+#pragma clang fp contract(off)
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
+  const float bc1 = hyper[5], bc2 = hyper[6], gs = hyper[7];
+  const float coef = clip[1];
+  const float step_size = lr / bc1;
+  const float bc2_sqrt = sqrtf(bc2);
+  const float decay = fmaf(-lr, wd, 1.0f);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float gi = grad[i] * gs;
+    const float g = gi * coef;
+    float mi = m[i];
+    mi = fmaf(1.0f - b1, fmaf(gi, coef, -mi), mi);       // exp_avg.lerp_(grad, 1 - beta1)
+    const float vi = fmaf(g, (1.0f - b2) * g, v[i] * b2);   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    const float p = fmaf(decay, param[i], -(step_size * (mi / denom)));
+    param[i] = p;
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
+hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
+                                const float* clip, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const long blocks = std::min<long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(adamw_clipped_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper, clip);
   return hipGetLastError();
 }
 

@@ -4,6 +4,9 @@
     model = GNOT(input_dim, theta_dim, input_func_dim, out_dim, n_attn_layers, n_attn_hidden_dim,
                  n_mlp_num_layers, n_mlp_hidden_dim, n_input_hidden_dim, n_expert, n_head,
                  n_input_functions).cuda()
+
+The training step around it lives in `gnot_amd.train` (`RelL2Loss`, `MSELoss`, `FlatAdamW` with optional
+global-norm gradient clipping, `OneCycle`, `fit`) and the multi-GPU glue in `gnot_amd.parallel`.
 """
 from .model import GNOT, MLP, LinearAttention, HeterogeneousNormalizedAttentionBlock  # noqa: F401
 from . import _lib  # noqa: F401

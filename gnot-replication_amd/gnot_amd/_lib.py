@@ -31,6 +31,7 @@ EXPORTS = [
     "gnot_backward", "gnot_profile_enable", "gnot_profile_read", "gnot_debug_buffer", "gnot_last_error",
     "gnot_version", "gnot_plan_set_shard", "gnot_plan_set_grad_comm", "gnot_shard_range", "gnot_shard_exchange",
     "gnot_rel_l2_work_floats", "gnot_rel_l2_loss", "gnot_adamw_step",
+    "gnot_mse_work_floats", "gnot_mse_loss", "gnot_grad_clip_work_floats", "gnot_grad_clip", "gnot_adamw_step_clipped",
 ]
 
 # gnot_comm callbacks (include/gnot_hip.h)
@@ -108,6 +109,13 @@ def _declare(lib):
     lib.gnot_rel_l2_work_floats.restype = sz
     lib.gnot_rel_l2_loss.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, P, P, P, P]
     lib.gnot_adamw_step.argtypes = [P, P, P, P, i64, P, P]
+    lib.gnot_mse_work_floats.argtypes = [ctypes.POINTER(i64), i32, i32]
+    lib.gnot_mse_work_floats.restype = sz
+    lib.gnot_mse_loss.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, P, P, P, P]
+    lib.gnot_grad_clip_work_floats.argtypes = [i64]
+    lib.gnot_grad_clip_work_floats.restype = sz
+    lib.gnot_grad_clip.argtypes = [P, i64, P, ctypes.c_float, P, P, P]
+    lib.gnot_adamw_step_clipped.argtypes = [P, P, P, P, i64, P, P, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p

@@ -10,7 +10,7 @@ backward, overlapped with it (gnot_plan_set_grad_comm):
   (`shard_range`); the engine calls back into `PointShardComm` for the two exchanges the reference's
   attention needs (include/gnot_hip.h: state all-reduce, scramble all-to-all) and the caller sums
   gradients over ranks.  `rel_l2_loss_sharded` is the reference loss (loss.py:14-23) on a sharded
-  mesh: its per-sample sums are all-reduced.
+  mesh: its per-sample sums are all-reduced; `mse_loss_sharded` the same for MSELoss (loss.py:4-12).
 
 The reference itself is single-device (main.py:27); nothing here has a reference counterpart beyond
 the arithmetic it must reproduce.
@@ -202,3 +202,14 @@ def rel_l2_loss_sharded(out, tgt, seg, B, group=None, stage_via_host=False):
     num = _SumOverRanks.apply(num, group, stage_via_host)
     den = _SumOverRanks.apply(den, group, stage_via_host)
     return (num / den).sqrt().mean()
+
+
+def mse_loss_sharded(out, tgt, seg, n_global, group=None, stage_via_host=False):
+    """MSELoss (loss.py:4-12) of meshes whose points are sharded over ranks: per-sample sums of (p - t)^2
+    over ALL ranks' points divided by the global point counts n_global [B] (the dgl AvgPooling), then the
+    mean over samples x channels."""
+    B, C = len(n_global), out.shape[1]
+    num = torch.zeros(B, C, device=out.device, dtype=out.dtype).index_add(0, seg, (out - tgt) ** 2)
+    num = _SumOverRanks.apply(num, group, stage_via_host)
+    cnt = torch.tensor([float(n) for n in n_global], device=out.device, dtype=out.dtype)
+    return (num / cnt[:, None]).mean()

@@ -11,7 +11,11 @@
   arena: the model's parameters are re-homed into a single buffer laid out exactly like the engine's
   gradient arena, so the whole update is one kernel (gnot_adamw_step) reading the step's flat
   gradient buffer directly.  The hyper-parameters live in a small device array that `prepare()`
-  refreshes from the host schedule, so `launch()` can be captured in a hipGraph.
+  refreshes from the host schedule, so `launch()` can be captured in a hipGraph.  `max_grad_norm`
+  adds torch.nn.utils.clip_grad_norm_ in front of the update, computed on the device
+  (gnot_grad_clip + gnot_adamw_step_clipped), still without a host synchronisation.
+* `MSELoss` -- reference loss.py:4-12 (dgl AvgPooling: per-sample mean over points, then the mean over
+  samples x channels), the reference's second loss, through gnot_mse_loss.
 """
 import ctypes
 import math
@@ -44,9 +48,33 @@ class _RelL2(torch.autograd.Function):
         return dpred * g, None, None, None, None
 
 
+class _MSE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, tgt, off_dev, off_host, work):
+        lib = _lib.load()
+        B = len(off_host) - 1
+        C = pred.shape[1]
+        loss = torch.empty((), device=pred.device, dtype=torch.float32)
+        dpred = torch.empty_like(pred) if pred.requires_grad else None
+        oh = (ctypes.c_int64 * (B + 1))(*off_host)
+        s = ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+        _lib.check(lib.gnot_mse_loss(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, C,
+                                     work.data_ptr(), loss.data_ptr(),
+                                     dpred.data_ptr() if dpred is not None else None, s))
+        ctx.save_for_backward(dpred) if dpred is not None else None
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g, None, None, None, None
+
+
 class RelL2Loss(torch.nn.Module):
     """mean over (sample, channel) of sqrt(sum_n (p - t)^2 / sum_n t^2) (reference loss.py:14-23).
     The dgl graph argument of the reference becomes the packed offsets x_off [B+1] (host list)."""
+
+    _fn, _work_floats = _RelL2, "gnot_rel_l2_work_floats"
 
     def __init__(self):
         super().__init__()
@@ -54,19 +82,28 @@ class RelL2Loss(torch.nn.Module):
 
     def forward(self, x_off, predictions, targets):
         if not predictions.is_cuda:
-            raise RuntimeError("gnot_amd.RelL2Loss runs on a ROCm GPU only (libgnot_hip.so)")
+            raise RuntimeError(f"gnot_amd.{type(self).__name__} runs on a ROCm GPU only (libgnot_hip.so)")
         key = (tuple(int(v) for v in x_off), predictions.shape[1], predictions.device)
         if key not in self._cache:
             B = len(key[0]) - 1
             oh = (ctypes.c_int64 * (B + 1))(*key[0])
-            n = _lib.load().gnot_rel_l2_work_floats(oh, B, key[1])
+            n = getattr(_lib.load(), self._work_floats)(oh, B, key[1])
             # pinned source + non_blocking: a new geometry must not stall the host on the stream
             # (a pageable copy would); the pinned tensor lives in the cache entry past the copy
             pinned = torch.tensor(key[0], dtype=torch.int64).pin_memory()
             self._cache = {key: (pinned.to(predictions.device, non_blocking=True),
                                  torch.empty(n, dtype=torch.float32, device=predictions.device), pinned)}
         off_dev, work, _ = self._cache[key]
-        return _RelL2.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0], work)
+        return self._fn.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0], work)
+
+
+class MSELoss(RelL2Loss):
+    """mean over (sample, channel) of the per-sample mean over points of (p - t)^2 (reference loss.py:4-12,
+    dgl AvgPooling): `MSELoss()(x_off, pred, tgt)`, one native pass (gnot_mse_loss) for the segment means,
+    the loss and d loss/d pred.  Not torch.nn.MSELoss: every sample weighs the same whatever its size.
+    A sample without points is refused (its mean is undefined)."""
+
+    _fn, _work_floats = _MSE, "gnot_mse_work_floats"
 
 
 # ------------------------------------------------------------------ OneCycleLR (main.py:52)
@@ -127,9 +164,28 @@ def flatten_parameters(model):
 
 class FlatAdamW:
     """torch.optim.AdamW(params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2) on a flat arena.
-    grad: the flat gradient buffer of the step (Engine.grad_flat, same layout as `flat`)."""
+    grad: the flat gradient buffer of the step (Engine.grad_flat, same layout as `flat`).
 
-    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, schedule=None):
+    max_grad_norm: torch.nn.utils.clip_grad_norm_(params, max_grad_norm) (L2, error_if_nonfinite=False)
+    in front of every step, on the device: `launch()` issues gnot_grad_clip (the global norm of the whole
+    arena and the coefficient min(1, max / (norm + 1e-6))) and gnot_adamw_step_clipped, which scales each
+    gradient element as it reads it.  Unlike torch, which scales `.grad` in place, the gradient buffer is
+    NOT modified: `grad_flat` stays unclipped after the step.  `grad_norm` is a 0-d device tensor (a view
+    of the norm the last launch computed, before clipping); reading it is the caller's synchronisation.
+    With several ranks every rank holds the same summed gradient after the backward, so every rank
+    computes the same norm: no collective.  None (default): the plain gnot_adamw_step, nothing else."""
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, schedule=None,
+                 max_grad_norm=None):
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None
+        if self.max_grad_norm is not None:
+            if not (self.max_grad_norm > 0 and math.isfinite(self.max_grad_norm)):
+                raise ValueError("max_grad_norm must be positive and finite")
+            self._clip = torch.zeros(2, dtype=torch.float32, device=flat.device)       # {norm, coefficient}
+            self._clip_work = torch.empty(_lib.load().gnot_grad_clip_work_floats(flat.numel()),
+                                          dtype=torch.float32, device=flat.device)
+            self.grad_norm = self._clip[0]
         self.flat = flat
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
@@ -159,10 +215,19 @@ class FlatAdamW:
         self._ev[k] = ev
 
     def launch(self, grad):
-        """The update kernel only (graph-capturable)."""
+        """The update kernel only -- with max_grad_norm, the two norm kernels and the clipped update
+        (graph-capturable either way)."""
         if grad.numel() != self.flat.numel():
             raise ValueError("gradient buffer does not match the parameter arena")
         s = ctypes.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
+        if self.max_grad_norm is not None:
+            lib = _lib.load()
+            _lib.check(lib.gnot_grad_clip(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(), self.max_grad_norm,
+                                          self._clip_work.data_ptr(), self._clip.data_ptr(), s))
+            _lib.check(lib.gnot_adamw_step_clipped(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
+                                                   self.v.data_ptr(), self.flat.numel(), self.hyper.data_ptr(),
+                                                   self._clip.data_ptr(), s))
+            return
         _lib.check(_lib.load().gnot_adamw_step(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
                                                self.v.data_ptr(), self.flat.numel(), self.hyper.data_ptr(), s))
 
@@ -221,21 +286,25 @@ def evaluate(model, loader, loss_fn=None):
 
 
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
-        log=print):
+        log=print, loss_fn=None, max_grad_norm=None):
     """The reference training loop (main.py:50-153): AdamW(lr) + OneCycleLR(max_lr=lr, steps_per_epoch,
     epochs), RelL2 loss, per-epoch test metric and best checkpoint.  With per_epoch_schedule=True the
     schedule is stepped once per epoch, as main.py:106 does.  The loaders decide the batch form:
     collate_padded batches run main.py's zero-padded semantics (pad rows in the attention sums),
     collate_packed batches the packed (per-sample exact) one.
+    loss_fn: the training loss, `RelL2Loss()` (default) or `MSELoss()` (main.py:97-98); the test metric is
+    RelL2 either way (main.py:143).  max_grad_norm: global-norm gradient clipping in front of every AdamW
+    step (FlatAdamW's max_grad_norm; None = off, the reference's loop).
     Returns (train losses per epoch, test metrics per epoch)."""
     flat = flatten_parameters(model)
     sched = OneCycle(lr, epochs, len(train_loader))
-    opt = FlatAdamW(flat, lr=lr, schedule=sched)
+    opt = FlatAdamW(flat, lr=lr, schedule=sched, max_grad_norm=max_grad_norm)
     dev = flat.device
     eng = model.engine()
     prev = eng.param_grads
     eng.param_grads = False          # FlatAdamW reads the gradient arena; no .grad copies
-    loss_fn = RelL2Loss()
+    loss_fn = loss_fn or RelL2Loss()
+    metric = loss_fn if type(loss_fn) is RelL2Loss else RelL2Loss()
     best, hist_train, hist_test = float("inf"), [], []
     try:
         for epoch in range(epochs):
@@ -253,7 +322,7 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             hist_train.append(sum(losses) / max(len(losses), 1))
             log(f"Epoch {epoch}, Loss: {hist_train[-1]}")
             if test_loader is not None:
-                res = evaluate(model, test_loader, loss_fn)
+                res = evaluate(model, test_loader, metric)
                 hist_test.append(res)
                 log(f"Epoch {epoch}, Test Metric: {res}")
                 if res < best and checkpoint:

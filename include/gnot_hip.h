@@ -211,6 +211,34 @@ int gnot_rel_l2_loss(const float* pred, const float* tgt, const int64_t* off_dev
 int gnot_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
                     void* stream);
 
+/* MSELoss (reference loss.py:4-12, the dgl AvgPooling as packed segment means), same arguments as
+ * gnot_rel_l2_loss: loss = 1/(B C) sum_b sum_c (1/N_b) sum_n (p-t)^2 to *loss (device) and, if
+ * dpred != NULL, d loss / d pred = 2 (p-t) / (B C N_b).  work: device scratch of
+ * gnot_mse_work_floats(off_host, B, C) floats.  Every sample needs at least one row (GNOT_E_INVALID,
+ * "empty sample": its mean is undefined).  Deterministic (fixed-order reductions). */
+size_t gnot_mse_work_floats(const int64_t* off_host, int B, int C);
+int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B, int C,
+                  float* work, float* loss, float* dpred, void* stream);
+
+/* torch.nn.utils.clip_grad_norm_(params, max_norm) with its defaults (L2 norm, error_if_nonfinite=False)
+ * over a flat fp32 gradient of n >= 1 elements (any 4-byte-aligned pointer), computed on the device:
+ * clip[0] = norm = |hyper[7]| sqrt(sum g^2), the norm of the scaled gradient gnot_adamw_step consumes
+ * (hyper as below), clip[1] = min(1, max_norm / (norm + 1e-6)); a non-finite norm gives a non-finite
+ * coefficient that propagates, as in torch.  clip: DEVICE array of 2 floats; work: device scratch of
+ * gnot_grad_clip_work_floats(n) floats (a function of n alone).  Two fixed-order reduction stages, no
+ * atomics: the same arguments give the same bits on every run and device.  max_norm must be positive
+ * and finite.  `grad` is only read. */
+size_t gnot_grad_clip_work_floats(int64_t n);
+int gnot_grad_clip(const float* grad, int64_t n, const float* hyper, float max_norm, float* work, float* clip,
+                   void* stream);
+
+/* gnot_adamw_step on the clipped gradient (grad[i] * hyper[7]) * clip[1], clip as written by gnot_grad_clip
+ * and read from device memory when the kernel runs (a captured graph applies each replay's own
+ * coefficient); with clip[1] == 1 and a hyper[7] of 1 (or any power of two) the result is
+ * gnot_adamw_step's bit for bit. */
+int gnot_adamw_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                            const float* hyper, const float* clip, void* stream);
+
 /* Live kernel timing for the bench's roofline: while enabled, every launch of kernel class `kind`
  * ("moe_fwd" fused expert chains forward, "moe_bwd" their backward, "wgrad" weight-gradient GEMMs;
  * "" disables) is bracketed by hipEvents on its stream.  gnot_profile_read synchronizes on those

@@ -39,6 +39,10 @@ def main():
     ap.add_argument("--checkpoint", default="best_model.pth")
     ap.add_argument("--packed", action="store_true",
                     help="packed batches (per-sample exact); default: main.py's zero-padded batches")
+    ap.add_argument("--loss", choices=["rel_l2", "mse"], default="rel_l2",
+                    help="training loss: RelL2Loss (main.py:98) or MSELoss (main.py:97); the test metric stays RelL2")
+    ap.add_argument("--grad-clip", type=float, default=None, metavar="FLOAT",
+                    help="clip the global gradient norm to this value before every AdamW step (default: off)")
     args = ap.parse_args()
     if args.synthetic:
         rng = np.random.default_rng(0)
@@ -55,7 +59,9 @@ def main():
                                                     collate_fn=data.collate_packed if args.packed
                                                     else data.collate_padded)
     _, test = train.fit(model, dl(tr, True), dl(te, False), epochs=args.epochs,
-                        per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint)
+                        per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint,
+                        loss_fn=train.MSELoss() if args.loss == "mse" else train.RelL2Loss(),
+                        max_grad_norm=args.grad_clip)
     print(f"\nBest Test Metric: {min(test)}")
 
 
