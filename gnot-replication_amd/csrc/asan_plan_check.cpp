@@ -1,8 +1,8 @@
 // Host-side planning check, built with AddressSanitizer on the HOST code only (csrc/Makefile `asan`):
 // exercises every C-ABI entry point that needs no GPU -- plan creation for the supported widths, packed
 // batch geometries (ragged, empty samples, many meshes, padded-equal strides), MoE recompute and
-// precision switches, workspace sizing, gradient offsets, the point-shard exchange tables and the
-// error paths -- so heap overflows / use-after-free in engine.cpp's table building show up on the CPU.
+// precision switches, workspace sizing, gradient offsets, the caller-owned gradient arena, the flag
+// validation of gnot_backward_ex, the point-shard exchange tables and the error paths -- so heap overflows / use-after-free in engine.cpp's table building show up on the CPU.
 // Run by tests/test_asan.py; exit status 0 = every check passed and ASan reported nothing.
 #include <cstdio>
 #include <cstdlib>
@@ -99,6 +99,48 @@ static void exercise(const gnot_config& cfg, std::mt19937& rng) {
       }
     }
     CHECK(gnot_plan_set_shard(p, 0, 1, B, n.data(), nullptr) == GNOT_OK);
+  }
+  // caller-owned gradient arena: the size is known from create on; a short or misaligned arena is refused;
+  // a good one invalidates the batch and leaves workspace size and offsets as they were (the pointer is
+  // only stored in the job tables here, nothing dereferences it without a GPU)
+  {
+    int64_t gf = 0;
+    for (int k = 0; k < nlin; ++k) gf += (int64_t)dims[2 * k] * dims[2 * k + 1] + dims[2 * k];
+    CHECK(gnot_plan_grad_floats(p) == gf);
+    CHECK(gnot_plan_grad_floats(nullptr) == 0);
+    const std::vector<int64_t> n2 = {300, 77}, m2 = {40, 40};
+    const auto xo = offsets(n2);
+    std::vector<int64_t> fo;
+    for (int i = 0; i < I; ++i) {
+      const auto o = offsets(m2);
+      fo.insert(fo.end(), o.begin(), o.end());
+    }
+    CHECK(gnot_plan_set_batch(p, 2, xo.data(), I ? fo.data() : nullptr, 1) == GNOT_OK);
+    const size_t ws = gnot_plan_workspace_bytes(p);
+    std::vector<float> host(gf + 8);
+    float* arena = host.data();
+    while (reinterpret_cast<uintptr_t>(arena) & 15) ++arena;
+    CHECK(gnot_plan_set_grad_arena(p, arena, gf - 1) == GNOT_E_INVALID);
+    CHECK(gnot_plan_set_grad_arena(p, arena + 1, gf) == GNOT_E_INVALID);
+    CHECK(gnot_plan_set_grad_arena(nullptr, arena, gf) == GNOT_E_INVALID);
+    CHECK(gnot_plan_workspace_bytes(p) == ws);               // the refusals changed nothing
+    // the flag validation of gnot_backward_ex fails before any launch
+    float dout = 0.f;
+    CHECK(gnot_backward_ex(p, &dout, 4, nullptr) == GNOT_E_INVALID);
+    CHECK(gnot_backward_ex(p, &dout, GNOT_BWD_ACCUMULATE | 8, nullptr) == GNOT_E_INVALID);
+    CHECK(gnot_backward_ex(p, &dout, GNOT_BWD_ACCUMULATE, nullptr) == GNOT_E_STATE);   // no caller arena
+    CHECK(gnot_plan_set_grad_arena(p, arena, gf) == GNOT_OK);
+    CHECK(gnot_plan_workspace_bytes(p) == 0);                // batch invalidated
+    CHECK(gnot_plan_set_batch(p, 2, xo.data(), I ? fo.data() : nullptr, 1) == GNOT_OK);
+    CHECK(gnot_plan_workspace_bytes(p) == ws);               // same layout with a caller arena
+    std::vector<int64_t> go(2 * nlin);
+    CHECK(gnot_plan_grad_offsets(p, go.data()) == GNOT_OK);
+    CHECK(go[0] == 0 && go[2 * nlin - 1] + dims[2 * nlin - 2] == gf);
+    CHECK(gnot_plan_set_grad_arena(p, arena, gf) == GNOT_OK);   // the same arena again: nothing invalidated
+    CHECK(gnot_plan_workspace_bytes(p) == ws);
+    CHECK(gnot_plan_set_grad_arena(p, nullptr, 0) == GNOT_OK);  // back to the workspace arena
+    CHECK(gnot_plan_workspace_bytes(p) == 0);
+    CHECK(gnot_backward_ex(p, &dout, GNOT_BWD_ACCUMULATE | GNOT_BWD_SKIP_GRAD_COMM, nullptr) == GNOT_E_STATE);
   }
   gnot_plan_destroy(p);
 }

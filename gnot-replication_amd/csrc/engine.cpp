@@ -223,6 +223,19 @@ struct gnot_plan {
   // group's (dW, db) ranges are summed over the ranks on `comm_stream` as soon as the group is written
   gnot_comm grad_comm{};
   bool grad_comm_on = false;
+  // the running gnot_backward_ex: its gradient collectives are live (grad_comm_on without
+  // GNOT_BWD_SKIP_GRAD_COMM) and its split-K finishes add onto the arena (GNOT_BWD_ACCUMULATE)
+  bool grad_comm_live = false;
+  bool bwd_accumulate = false;
+  // caller-owned gradient arena (gnot_plan_set_grad_arena): the job tables' dW / db, the gradient
+  // collectives and gnot_debug_buffer("grads") use it; null: the workspace's "grads" buffer
+  float* user_grads = nullptr;
+  float* grads() const { return user_grads ? user_grads : P_("grads"); }
+  long arena_floats() const {
+    long g = 0;
+    for (size_t li = 0; li < lin_o.size(); ++li) g += (long)lin_o[li] * lin_i[li] + lin_o[li];
+    return g;
+  }
   hipStream_t comm_stream = nullptr;
   std::vector<long> nglob;                 // [B] global points per sample (sharded batches)
   bool sharded = false;                    // world > 1 for the current batch
@@ -816,7 +829,7 @@ static void build_groups(gnot_plan* p) {
 
   auto lin_job = [&](WgradGroup& G, int li, const float* dz, long lddz, const float* x, long ldx, int gelu,
                      long rows) {
-    float* grads = p->P_("grads");
+    float* grads = p->grads();
     WgradJob J{};
     J.dz = dz; J.lddz = lddz; J.x = x; J.ldx = ldx; J.x_gelu = gelu;
     J.out = p->lin_o[li]; J.in = p->lin_i[li];
@@ -833,7 +846,7 @@ static void build_groups(gnot_plan* p) {
       lin_job(G, li, dz, lddz, x, ldx, 0, rows);
       return;
     }
-    float* grads = p->P_("grads");
+    float* grads = p->grads();
     const int in = p->lin_i[li];
     for (int h = 0; h < p->H; ++h) {
       WgradJob J{};
@@ -1193,6 +1206,23 @@ extern "C" int gnot_plan_set_grad_comm(gnot_plan* p, const gnot_comm* comm) {
   if (comm && !comm->allreduce_sum) return fail(GNOT_E_INVALID, "gnot_comm.allreduce_sum is required");
   p->grad_comm_on = comm != nullptr;
   p->grad_comm = comm ? *comm : gnot_comm{};
+  return GNOT_OK;
+}
+
+extern "C" int64_t gnot_plan_grad_floats(const gnot_plan* p) { return p ? (int64_t)p->arena_floats() : 0; }
+
+extern "C" int gnot_plan_set_grad_arena(gnot_plan* p, float* arena, int64_t floats) {
+  if (!p) return fail(GNOT_E_INVALID, "null plan");
+  if (arena) {
+    if (floats < (int64_t)p->arena_floats())
+      return fail(GNOT_E_INVALID, "gradient arena smaller than gnot_plan_grad_floats");
+    if (reinterpret_cast<uintptr_t>(arena) & 15) return fail(GNOT_E_INVALID, "gradient arena must be 16-byte aligned");
+  }
+  if (p->user_grads != arena) {
+    p->user_grads = arena;
+    p->batch_set = false;          // the job tables hold the arena's pointers: set_batch + bind again
+    p->ws_bound = false;
+  }
   return GNOT_OK;
 }
 
@@ -1756,10 +1786,10 @@ int guard_write(Ctx& c, const float* buf) {
 int launch_group(gnot_plan* p, const WgradGroup& G, float* slab, hipStream_t s) {
   if (G.b16)
     GNOT_CK(launch_wgrad_b16(G.d_jobs, G.d_wg_prefix, (int)G.jobs.size(), G.total_wgs, G.d_red_prefix, G.total_red,
-                             slab, s, G.d_segs, G.d_seg_start));
+                             slab, s, G.d_segs, G.d_seg_start, p->bwd_accumulate));
   else
     GNOT_CK(launch_wgrad(G.d_jobs, G.d_wg_prefix, (int)G.jobs.size(), G.total_wgs, G.d_red_prefix, G.total_red, slab,
-                         s, G.x6, G.wide, p->npk(), G.tw, G.d_segs, G.d_seg_start));
+                         s, G.x6, G.wide, p->npk(), G.tw, G.d_segs, G.d_seg_start, p->bwd_accumulate));
   return GNOT_OK;
 }
 
@@ -1770,7 +1800,7 @@ int grad_allreduce(gnot_plan* p, const WgradGroup& G, hipEvent_t done) {
   GNOT_CK(hipStreamWaitEvent(p->comm_stream, done, 0));
   std::vector<int> ls(G.lins);
   std::sort(ls.begin(), ls.end());
-  float* grads = p->P_("grads");
+  float* grads = p->grads();
   for (size_t k = 0; k < ls.size();) {
     size_t m = k + 1;
     while (m < ls.size() && ls[m] == ls[m - 1] + 1) ++m;
@@ -1806,7 +1836,7 @@ int run_wgrad_side(Ctx& c, const WgradGroup& G, std::initializer_list<const floa
       ProfScope ps(c, G.b16 ? "wgrad_b16" : "wgrad", group_flops(G));
       GNOT_RUN(launch_group(c.p, G, slab, c.s));
     }
-    if (p->grad_comm_on) {
+    if (p->grad_comm_live) {
       hipEvent_t done = next_event(p);
       GNOT_CK(hipEventRecord(done, c.s));
       GNOT_RUN(grad_allreduce(p, G, done));
@@ -1839,7 +1869,7 @@ int flush_deferred(Ctx& c) {
     hipEvent_t done = next_event(p);
     GNOT_CK(hipEventRecord(done, p->side));
     for (const float* r : d.reads) p->readers[r] = done;
-    if (p->grad_comm_on) GNOT_RUN(grad_allreduce(p, *d.G, done));
+    if (p->grad_comm_live) GNOT_RUN(grad_allreduce(p, *d.G, done));
   }
   return GNOT_OK;
 }
@@ -2042,17 +2072,26 @@ static void rejoin_side_streams(gnot_plan* p, hipStream_t origin) {
 
 static int forward_impl(gnot_plan* p, const float* x, const float* theta, const float* const* fns, float* out,
                         void* stream);
-static int backward_impl(gnot_plan* p, const float* dout, void* stream);
+static int backward_impl(gnot_plan* p, const float* dout, int flags, void* stream);
 extern "C" int gnot_forward(gnot_plan* p, const float* x, const float* theta, const float* const* fns,
                             float* out, void* stream) {
   const int rc = forward_impl(p, x, theta, fns, out, stream);
   if (rc != GNOT_OK && p) rejoin_side_streams(p, static_cast<hipStream_t>(stream));
   return rc;
 }
-extern "C" int gnot_backward(gnot_plan* p, const float* dout, void* stream) {
-  const int rc = backward_impl(p, dout, stream);
+extern "C" int gnot_backward_ex(gnot_plan* p, const float* dout, int flags, void* stream) {
+  // flag validation comes first: it fails before any launch (and before the side streams are touched)
+  if (flags & ~(GNOT_BWD_ACCUMULATE | GNOT_BWD_SKIP_GRAD_COMM))
+    return fail(GNOT_E_INVALID, "unknown gnot_backward_ex flag bits");
+  if (p && (flags & GNOT_BWD_ACCUMULATE) && !p->user_grads)
+    return fail(GNOT_E_STATE, "GNOT_BWD_ACCUMULATE needs a caller-owned arena (gnot_plan_set_grad_arena): the "
+                              "workspace arena does not survive a geometry change (a re-plan moves or clears it)");
+  const int rc = backward_impl(p, dout, flags, stream);
   if (rc != GNOT_OK && p) rejoin_side_streams(p, static_cast<hipStream_t>(stream));
   return rc;
+}
+extern "C" int gnot_backward(gnot_plan* p, const float* dout, void* stream) {
+  return gnot_backward_ex(p, dout, 0, stream);
 }
 
 static int forward_impl(gnot_plan* p, const float* x, const float* theta, const float* const* fns, float* out,
@@ -2149,10 +2188,12 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   return GNOT_OK;
 }
 
-static int backward_impl(gnot_plan* p, const float* dout, void* stream) {
+static int backward_impl(gnot_plan* p, const float* dout, int flags, void* stream) {
   if (!p || !p->ws_bound || !p->fwd_done) return fail(GNOT_E_STATE, "gnot_forward must run before gnot_backward");
   if (!p->training) return fail(GNOT_E_STATE, "plan was set up with training = 0");
   if (!dout) return fail(GNOT_E_INVALID, "null dout");
+  p->bwd_accumulate = (flags & GNOT_BWD_ACCUMULATE) != 0;
+  p->grad_comm_live = p->grad_comm_on && !(flags & GNOT_BWD_SKIP_GRAD_COMM);
   Ctx c{p, static_cast<hipStream_t>(stream)};
   const long P = p->P;
   const int D = p->D, E = p->E, NL = p->NL;
@@ -2160,7 +2201,7 @@ static int backward_impl(gnot_plan* p, const float* dout, void* stream) {
   float* stage = p->P_("stage");
   p->readers.clear();
   p->deferred.clear();
-  if (p->grad_comm_on) {                   // the comm stream joins here (a first-level fork of the caller's)
+  if (p->grad_comm_live) {                   // the comm stream joins here (a first-level fork of the caller's)
     if (!p->comm_stream) GNOT_CK(hipStreamCreateWithFlags(&p->comm_stream, hipStreamNonBlocking));
     hipEvent_t fork = next_event(p);
     GNOT_CK(hipEventRecord(fork, c.s));
@@ -2242,7 +2283,7 @@ static int backward_impl(gnot_plan* p, const float* dout, void* stream) {
   // ranks issue their gradient collectives in one host order whatever serial_wgrad() says (it is chosen
   // per rank from the local point count): a forked rank still holds the last attention call's groups
   // (wg_cross[0]) deferred here, and side2 issues its groups' all-reduces at once -- flush first
-  if (p->grad_comm_on) GNOT_RUN(flush_deferred(c));
+  if (p->grad_comm_live) GNOT_RUN(flush_deferred(c));
   if (br) {
     hipEvent_t fork = next_event(p);
     GNOT_CK(hipEventRecord(fork, c.s));
@@ -2316,7 +2357,7 @@ static int backward_impl(gnot_plan* p, const float* dout, void* stream) {
       ProfScope ps(c, "wgrad", group_flops(p->wg_gate));
       GNOT_RUN(launch_group(p, p->wg_gate, p->P_("slab_wgrad2"), c.s));
     }
-    if (p->grad_comm_on) {
+    if (p->grad_comm_live) {
       hipEvent_t done = next_event(p);
       GNOT_CK(hipEventRecord(done, c.s));
       GNOT_RUN(grad_allreduce(p, p->wg_gate, done));
@@ -2327,7 +2368,7 @@ static int backward_impl(gnot_plan* p, const float* dout, void* stream) {
   hipEvent_t join = next_event(p);
   GNOT_CK(hipEventRecord(join, p->side));
   GNOT_CK(hipStreamWaitEvent(c.s, join, 0));
-  if (p->grad_comm_on) {                   // ... and summed over the ranks
+  if (p->grad_comm_live) {                   // ... and summed over the ranks
     hipEvent_t joinc = next_event(p);
     GNOT_CK(hipEventRecord(joinc, p->comm_stream));
     GNOT_CK(hipStreamWaitEvent(c.s, joinc, 0));
@@ -2404,7 +2445,7 @@ extern "C" int gnot_debug_buffer(const gnot_plan* p, const char* name, float** p
   if (!p || !name || !ptr || !p->ws_bound) return fail(GNOT_E_STATE, "bind_workspace first");
   auto it = p->bufs.find(name);
   if (it == p->bufs.end()) return fail(GNOT_E_INVALID, std::string("unknown buffer ") + name);
-  *ptr = it->second.p;
+  *ptr = (p->user_grads && it->first == "grads") ? p->user_grads : it->second.p;
   if (ld) *ld = it->second.ld;
   return GNOT_OK;
 }

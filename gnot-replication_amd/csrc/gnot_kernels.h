@@ -157,7 +157,9 @@ hipError_t launch_chain2(const ChainArgs& a, bool bwd, hipStream_t s);
 
 // ------------------------------------------------------------------ point-reduction GEMM (wgrad.hip)
 // C[out, in] = sum_p dz[p, :out]^T x[p, :in] over a point range, plus column sums of dz.
-struct WgradJob {
+// (alignas(16): 128 bytes per job, so that in the device tables -- 256-byte aligned, engine.cpp bind -- no job
+// straddles a 128-byte line and the kernels' scalar loads of its fields stay aligned)
+struct alignas(16) WgradJob {
   const float* dz; long lddz;        // A rows [P, out]
   const float* x;  long ldx;         // B rows [P, in]
   int x_gelu;                        // 1: B = gelu(x) (x is a saved pre-activation)
@@ -171,7 +173,6 @@ struct WgradJob {
   int tiles_o, tiles_i;              // 128x128 output tiles
   int splits;                        // split-K count over points
   long slab_off;                     // offset (floats) of this job's partial slabs
-  int accumulate;                    // 1: dW += result
 };
 // one workgroup per (job, tile, split); wg_prefix / red_prefix: per-job prefix sums of workgroups and
 // of reduce elements (ntile * 128 * 129)
@@ -182,15 +183,18 @@ struct WgradJob {
 // segs / seg_start (wide kernel only, optional): the balanced form -- workgroup w runs the point ranges
 // segs[seg_start[w] .. seg_start[w+1]) = {job, slab slot, first point, end point}; each job's J.splits
 // then counts the ranges that touch it (slots 0 .. splits-1)
+// accumulate: the split-K finish adds its sum onto dW / db instead of overwriting them (per launch, not in
+// the job tables: one bound plan overwrites in one backward and accumulates in the next); jobs with
+// state_dh > 0 always overwrite
 hipError_t launch_wgrad(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
                         const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, bool x6 = false,
                         bool wide = false, int np = 3, int tw = 256,    // np: operand pieces (1 = bf16 mode)
-                        const int4* segs = nullptr, const int* seg_start = nullptr);
+                        const int4* segs = nullptr, const int* seg_start = nullptr, bool accumulate = false);
 // bf16-storage jobs (ChainArgs::b16s): dz and x point at bf16 pair-interleaved rows [P, 256] (x already
 // the Linear's input, no GELU), out = in = 256, one workgroup per (job, split) as the wide kernel
 hipError_t launch_wgrad_b16(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
                             const int* red_prefix_dev, int total_red, float* slab, hipStream_t s,
-                            const int4* segs = nullptr, const int* seg_start = nullptr);
+                            const int4* segs = nullptr, const int* seg_start = nullptr, bool accumulate = false);
 
 // ------------------------------------------------------------------ attention states (state.hip)
 // Jobs are WgradJobs with state_dh > 0: A = dz/lddz, B = x/ldx, optional w/ldw, out = dW as

@@ -836,10 +836,13 @@ __global__ void __launch_bounds__(kWThreads) pgemm_b16_kernel(const WgradJob* __
 }
 
 // sum the split partials; normal jobs write dW[out, in] (+ db[out]); state jobs (state_dh > 0) write
-// the per-head diagonal blocks into [H][dh*dh + dh] (S row-major, then z)
+// the per-head diagonal blocks into [H][dh*dh + dh] (S row-major, then z).
+// accumulate (a launch argument, gnot_backward_ex GNOT_BWD_ACCUMULATE): parameter-gradient jobs add the
+// same fixed-order sum s onto the destination (one read, one add, no atomics: each element has one writer);
+// state jobs overwrite in every mode
 __global__ void __launch_bounds__(256) pgemm_reduce_kernel(const WgradJob* __restrict__ jobs,
                                                            const int* __restrict__ prefix, int njobs, int total,
-                                                           const float* __restrict__ slab) {
+                                                           const float* __restrict__ slab, int accumulate) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int j = find_job(prefix, njobs, idx);
@@ -880,12 +883,12 @@ __global__ void __launch_bounds__(256) pgemm_reduce_kernel(const WgradJob* __res
   } else {
     dst = isdb ? (J.db + row) : (J.dW + (long)row * J.in + col);
   }
-  *dst = J.accumulate ? (*dst + s) : s;
+  *dst = (accumulate && J.state_dh == 0) ? (*dst + s) : s;
 }
 
 hipError_t launch_wgrad_b16(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
                             const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, const int4* segs,
-                            const int* seg_start) {
+                            const int* seg_start, bool accumulate) {
   if (njobs <= 0) return hipSuccess;
   static bool attr = false;
   if (!attr) {
@@ -896,13 +899,13 @@ hipError_t launch_wgrad_b16(const WgradJob* jobs_dev, const int* wg_prefix_dev, 
   hipLaunchKernelGGL(pgemm_b16_kernel, dim3(total_wgs), dim3(kWThreads), kBLds, s, jobs_dev, wg_prefix_dev, njobs, slab,
                      segs, seg_start);
   hipLaunchKernelGGL(pgemm_reduce_kernel, dim3((total_red + 255) / 256), dim3(256), 0, s, jobs_dev, red_prefix_dev,
-                     njobs, total_red, (const float*)slab);
+                     njobs, total_red, (const float*)slab, accumulate ? 1 : 0);
   return hipGetLastError();
 }
 
 hipError_t launch_wgrad(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
                         const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, bool x6, bool wide,
-                        int np, int tw, const int4* segs, const int* seg_start) {
+                        int np, int tw, const int4* segs, const int* seg_start, bool accumulate) {
   if (njobs <= 0) return hipSuccess;
   if (wide) {
     const size_t lds = w_lds_bytes(np, tw);
@@ -926,7 +929,7 @@ hipError_t launch_wgrad(const WgradJob* jobs_dev, const int* wg_prefix_dev, int 
   else
     hipLaunchKernelGGL(pgemm_kernel, dim3(total_wgs), dim3(256), 0, s, jobs_dev, wg_prefix_dev, njobs, slab);
   hipLaunchKernelGGL(pgemm_reduce_kernel, dim3((total_red + 255) / 256), dim3(256), 0, s, jobs_dev,
-                     red_prefix_dev, njobs, total_red, (const float*)slab);
+                     red_prefix_dev, njobs, total_red, (const float*)slab, accumulate ? 1 : 0);
   return hipGetLastError();
 }
 

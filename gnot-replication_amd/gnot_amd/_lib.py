@@ -32,7 +32,14 @@ EXPORTS = [
     "gnot_version", "gnot_plan_set_shard", "gnot_plan_set_grad_comm", "gnot_shard_range", "gnot_shard_exchange",
     "gnot_rel_l2_work_floats", "gnot_rel_l2_loss", "gnot_adamw_step",
     "gnot_mse_work_floats", "gnot_mse_loss", "gnot_grad_clip_work_floats", "gnot_grad_clip", "gnot_adamw_step_clipped",
+    "gnot_plan_set_grad_arena", "gnot_backward_ex",
 ]
+# (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
+# declared in _declare like the rest)
+
+# gnot_backward_ex flags (include/gnot_hip.h)
+BWD_ACCUMULATE = 1
+BWD_SKIP_GRAD_COMM = 2
 
 # gnot_comm callbacks (include/gnot_hip.h)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
@@ -96,6 +103,10 @@ def _declare(lib):
     lib.gnot_pack_weights.argtypes = [P, P]
     lib.gnot_forward.argtypes = [P, P, P, ctypes.POINTER(P), P, P]
     lib.gnot_backward.argtypes = [P, P, P]
+    lib.gnot_backward_ex.argtypes = [P, P, i32, P]
+    lib.gnot_plan_grad_floats.argtypes = [P]
+    lib.gnot_plan_grad_floats.restype = i64
+    lib.gnot_plan_set_grad_arena.argtypes = [P, P, i64]
     lib.gnot_profile_enable.argtypes = [P, ctypes.c_char_p]
     lib.gnot_profile_read.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64),
                                       ctypes.POINTER(ctypes.c_double)]

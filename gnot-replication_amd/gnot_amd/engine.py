@@ -47,6 +47,9 @@ class Engine:
         self.moe_recompute = False # re-run each MoE call's expert forward in the backward (memory option)
         self.bf16 = False          # bf16 arithmetic mode of the MFMA kernels up to d = 256 (gnot_plan_set_precision)
         self.input_grads = False   # also differentiate x, theta, input functions (gnot_plan_set_input_grads)
+        self.user_arena = None     # caller-owned flat fp32 gradient arena (GNOT.set_grad_arena); None: the workspace's
+        # options of the next backward(s), shared by the engines of one module (GNOT.backward_options)
+        self.bwd_opts = {"accumulate": False, "reduce": True}
         self.fwd_token = 0
         self.pending = None        # weakref to the autograd node of a training forward awaiting its backward
         self.pending_seq = 0
@@ -96,7 +99,8 @@ class Engine:
         self._bind_params()
         geom = (tuple(x_off), tuple(tuple(o) for o in fn_offs), bool(training),
                 tuple(n_global) if n_global is not None else None, bool(self.moe_recompute), bool(self.bf16),
-                bool(self.input_grads) and bool(training), id(self.grad_comm))
+                bool(self.input_grads) and bool(training), id(self.grad_comm),
+                None if self.user_arena is None else (self.user_arena.data_ptr(), self.user_arena.numel()))
         if geom == self.geom:
             return
         B = len(x_off) - 1
@@ -114,6 +118,10 @@ class Engine:
         _lib.check(self.lib.gnot_plan_set_moe_recompute(self.plan, int(bool(self.moe_recompute))))
         _lib.check(self.lib.gnot_plan_set_precision(self.plan, int(bool(self.bf16))))
         _lib.check(self.lib.gnot_plan_set_input_grads(self.plan, int(bool(self.input_grads) and bool(training))))
+        if self.user_arena is not None:
+            _lib.check(self.lib.gnot_plan_set_grad_arena(self.plan, self.user_arena.data_ptr(), self.user_arena.numel()))
+        else:
+            _lib.check(self.lib.gnot_plan_set_grad_arena(self.plan, None, 0))
         xo = (ctypes.c_int64 * (B + 1))(*x_off)
         flat = [v for o in fn_offs for v in o]
         fo = (ctypes.c_int64 * max(1, len(flat)))(*flat) if flat else None
@@ -140,8 +148,12 @@ class Engine:
             n = len(self.dims)
             offs = (ctypes.c_int64 * (2 * n))()
             _lib.check(self.lib.gnot_plan_grad_offsets(self.plan, offs))
-            base = self.debug_ptr("grads")[0] - self.ws.data_ptr()
-            wsf = self.ws[: (self.ws.numel() // 4) * 4].view(torch.float32)
+            if self.user_arena is not None:
+                # the caller's tensor IS the arena: offsets count from its start, nothing is derived from the workspace
+                base, wsf = 0, self.user_arena
+            else:
+                base = self.debug_ptr("grads")[0] - self.ws.data_ptr()
+                wsf = self.ws[: (self.ws.numel() // 4) * 4].view(torch.float32)
             views, layout = [], []
             for k, (o, i) in enumerate(self.dims):
                 wo = base // 4 + offs[2 * k]
@@ -187,6 +199,7 @@ class Engine:
         for c in (self.comm, self.grad_comm):
             if c is not None:
                 c.ws = self.ws
+                c.arena = self.user_arena
 
     def forward(self, x, theta, fns, out):
         self._own_comms()
@@ -206,10 +219,28 @@ class Engine:
         with torch.cuda.device(self.ws.device):
             _lib.check(self.lib.gnot_input_grads(self.plan, ptr(dx), ptr(dtheta), fptr, self.stream()))
 
+    def grad_numel(self):
+        """Floats of the gradient arena (gnot_plan_grad_floats): every Linear's out * in + out."""
+        return int(self.lib.gnot_plan_grad_floats(self.plan))
+
     def backward(self, dout):
+        """The backward kernels, under self.bwd_opts: `accumulate` adds the parameter gradients onto the
+        (caller-owned) arena instead of overwriting it; without `reduce` no gradient collective runs, neither
+        the in-backward all-reduce (grad_comm) nor grad_hook."""
+        acc, red = bool(self.bwd_opts["accumulate"]), bool(self.bwd_opts["reduce"])
+        if acc and self.param_grads:
+            raise RuntimeError("backward_options(accumulate=True) needs param_grads = False: autograd would add the "
+                               "already-accumulated arena into .grad again")
+        if acc and self.user_arena is None:
+            raise RuntimeError("backward_options(accumulate=True) needs GNOT.set_grad_arena: the workspace arena "
+                               "does not survive a geometry change")
+        flags = (_lib.BWD_ACCUMULATE if acc else 0) | (0 if red else _lib.BWD_SKIP_GRAD_COMM)
         self._own_comms()
         with torch.cuda.device(self.ws.device):
-            _lib.check(self.lib.gnot_backward(self.plan, dout.data_ptr(), self.stream()))
-        if self.grad_hook is not None:
+            if flags:
+                _lib.check(self.lib.gnot_backward_ex(self.plan, dout.data_ptr(), flags, self.stream()))
+            else:
+                _lib.check(self.lib.gnot_backward(self.plan, dout.data_ptr(), self.stream()))
+        if self.grad_hook is not None and red:
             self.grad_hook(self.grad_arena)     # e.g. ONE all-reduce of all gradients (sample-DP)
         return self.grad_views

@@ -15,6 +15,7 @@ Only the whole-model forward/backward runs on the GPU through libgnot_hip.so (on
 Function); the submodules exist to own the parameters.  There is no CPU path: on a tensor that is
 not on a ROCm device the forward raises.
 """
+import contextlib
 import weakref
 
 import torch
@@ -162,6 +163,8 @@ class GNOT(nn.Module):
         self._grad_comm = None     # parallel.PointShardComm (set_grad_allreduce)
         self._moe_recompute = False
         self._bf16 = False
+        self._grad_arena = None    # caller-owned gradient arena (set_grad_arena); survives engine rebuilds
+        self._bwd_opts = {"accumulate": False, "reduce": True}   # backward_options; one dict for every engine
 
     # canonical Linear order == named_parameters() order of the reference module
     def linears(self):
@@ -178,6 +181,8 @@ class GNOT(nn.Module):
         e.grad_comm = self._grad_comm
         e.moe_recompute = self._moe_recompute
         e.bf16 = self._bf16
+        e.user_arena = self._grad_arena
+        e.bwd_opts = self._bwd_opts
         return e
 
     def engine(self):
@@ -285,6 +290,55 @@ class GNOT(nn.Module):
         self.engine().grad_comm = comm
         self.engine().geom = None
         self._extra = []
+
+    def grad_numel(self):
+        """Elements of the flat gradient arena: the sum of out * in + out over the Linears in canonical order
+        (gnot_plan_grad_floats) -- the size a set_grad_arena tensor needs, and FlatAdamW's arena size."""
+        return self.engine().grad_numel()
+
+    def set_grad_arena(self, t):
+        """Write the parameter gradients into the caller's tensor `t` instead of the workspace (None: back
+        to the workspace arena).  `t`: contiguous float32 on the model's device with at least grad_numel()
+        elements, laid out as Engine.grad_layout (W0, b0, W1, b1, ... in canonical order).  Every engine of
+        the module shares it, and no batch geometry change moves or clears it, so gradients can be summed
+        over micro-batches there (backward_options).  Engine.grad_arena / grad_views / grad_flat then view
+        `t`.  The setting survives engine rebuilds."""
+        if t is not None:
+            dev = self.linears()[0].weight.device
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1):
+                raise ValueError("the gradient arena must be a contiguous 1-d float32 tensor")
+            if t.device != dev:
+                raise ValueError(f"the gradient arena must be on the model's device ({dev}), got {t.device}")
+            if t.numel() < self.grad_numel():
+                raise ValueError(f"the gradient arena needs at least {self.grad_numel()} elements, got {t.numel()}")
+            if t.data_ptr() % 16:
+                raise ValueError("the gradient arena must be 16-byte aligned")
+        self._grad_arena = t
+        for e in [self.engine()] + self._extra:
+            e.user_arena = t
+            e.geom = None
+
+    @contextlib.contextmanager
+    def backward_options(self, accumulate=False, reduce=True):
+        """Options of the backward(s) run inside the context (gnot_backward_ex).  accumulate: the parameter
+        gradients are added onto the arena instead of overwriting it -- needs set_grad_arena and
+        Engine.param_grads = False (autograd would add the already-accumulated arena into .grad).  reduce:
+        False skips the gradient collectives of this backward, the in-backward all-reduce of
+        set_grad_allreduce and Engine.grad_hook alike; of a group of micro-batches only the last reduces.
+        The first micro-batch of a group runs with accumulate=False, so the arena needs no clear."""
+        if accumulate:
+            if self._grad_arena is None:
+                raise RuntimeError("backward_options(accumulate=True) needs set_grad_arena: the workspace arena does "
+                                   "not survive a geometry change")
+            if self.engine().param_grads:
+                raise RuntimeError("backward_options(accumulate=True) needs engine().param_grads = False: autograd "
+                                   "would add the already-accumulated arena into .grad again")
+        prev = dict(self._bwd_opts)
+        self._bwd_opts.update(accumulate=bool(accumulate), reduce=bool(reduce))
+        try:
+            yield self
+        finally:
+            self._bwd_opts.update(prev)
 
     def forward_packed(self, x, x_off, theta, fns=(), fn_offs=(), n_global=None):
         """Packed-offsets forward (no padding): x [sum N_b, input_dim] with host offsets x_off [B+1];

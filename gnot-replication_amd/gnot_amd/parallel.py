@@ -88,12 +88,17 @@ class PointShardComm:
         self.world = dist.get_world_size(group)
         self.stage = stage_via_host
         self.ws = None                        # the engine's uint8 workspace tensor (set by Engine)
+        self.arena = None                     # the caller-owned fp32 gradient arena, when one is set (Engine)
         self.fail_next_captured = 0           # test knob: the n-th collective issued under capture fails (0: off)
         self._ar = _lib.ALLREDUCE_FN(self._allreduce)
         self._a2a = _lib.ALLTOALLV_FN(self._alltoallv)
         self.struct = _lib.GnotComm(None, self._ar, self._a2a)
 
     def _view(self, ptr, n):
+        if self.arena is not None:            # a gradient range of the caller-owned arena (GNOT.set_grad_arena)
+            off = int(ptr) - self.arena.data_ptr()
+            if off >= 0 and off % 4 == 0 and off // 4 + n <= self.arena.numel():
+                return self.arena[off // 4: off // 4 + n]
         off = int(ptr) - self.ws.data_ptr()
         if off < 0 or off % 4 or off + 4 * n > self.ws.numel():
             raise RuntimeError("gnot_comm buffer outside the engine workspace")

@@ -285,8 +285,53 @@ def evaluate(model, loader, loss_fn=None):
     return sum(vals) / max(len(vals), 1)
 
 
+def accum_groups(sizes, accum_steps):
+    """Gradient accumulation over micro-batches: `sizes` (samples of every loader batch of an epoch, in
+    order) in groups of `accum_steps` consecutive batches -- the tail group may be shorter -- and every
+    micro-batch's weight B_i / sum B of its group.  Both native losses are means over samples, so
+    sum_i (B_i / sum B) loss_i is the loss of the concatenated batch.  One optimizer step per group:
+    len(groups) = ceil(len(sizes) / accum_steps) steps per epoch.  Returns (groups, weights)."""
+    k = int(accum_steps)
+    if k < 1:
+        raise ValueError("accum_steps must be >= 1")
+    groups = [list(sizes[i:i + k]) for i in range(0, len(sizes), k)]
+    weights = [[b / sum(g) for b in g] for g in groups]
+    return groups, weights
+
+
+def _batch_samples(batch):
+    return len(batch["counts"]) if "counts" in batch else len(batch["x_off"]) - 1
+
+
+def _grouped(loader, k):
+    """the loader's batches in lists of k consecutive ones (the last may be shorter)"""
+    group = []
+    for batch in loader:
+        group.append(batch)
+        if len(group) == k:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
+def _accum_step(model, eng, opt, loss_fn, group, dev):
+    """One optimizer step on a group of micro-batches (fit's accum_steps): returns sum_i (B_i / sum B) loss_i."""
+    _, (weights,) = accum_groups([_batch_samples(b) for b in group], len(group))
+    vals = []
+    for i, (batch, w) in enumerate(zip(group, weights)):
+        pred, off, y = _forward_batch(model, batch, dev)
+        loss = loss_fn(off, pred, y)
+        # the first micro-batch overwrites the arena (no clear), the others add; only the last one reduces
+        with model.backward_options(accumulate=i > 0, reduce=i == len(group) - 1):
+            (loss * w).backward()
+        vals.append(loss.detach())
+    opt.step(eng.grad_flat)          # the clip (max_grad_norm) and AdamW read the accumulated arena once
+    return sum(float(l) * w for l, w in zip(vals, weights))
+
+
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
-        log=print, loss_fn=None, max_grad_norm=None):
+        log=print, loss_fn=None, max_grad_norm=None, accum_steps=1):
     """The reference training loop (main.py:50-153): AdamW(lr) + OneCycleLR(max_lr=lr, steps_per_epoch,
     epochs), RelL2 loss, per-epoch test metric and best checkpoint.  With per_epoch_schedule=True the
     schedule is stepped once per epoch, as main.py:106 does.  The loaders decide the batch form:
@@ -295,11 +340,24 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     loss_fn: the training loss, `RelL2Loss()` (default) or `MSELoss()` (main.py:97-98); the test metric is
     RelL2 either way (main.py:143).  max_grad_norm: global-norm gradient clipping in front of every AdamW
     step (FlatAdamW's max_grad_norm; None = off, the reference's loop).
+    accum_steps: every accum_steps consecutive loader batches (micro-batches; the epoch's tail group may be
+    shorter) form ONE optimizer step on the gradient of their concatenation (accum_groups): micro-batch i
+    runs (loss_i * B_i / sum B).backward(), the first overwriting and the others adding onto a gradient
+    arena owned by fit (GNOT.set_grad_arena), only the last one reducing over ranks; AdamW and the clip read
+    the arena once per group, and the schedule counts optimizer steps.  The logged loss of a step is
+    sum_i (B_i / sum B) loss_i.  A batch of main.py:41's four large meshes that does not fit one plan
+    runs as accum_steps = 4 loader batches of one.  1 (default): one step per loader batch, no arena.
     Returns (train losses per epoch, test metrics per epoch)."""
+    accum_steps = int(accum_steps)
+    if accum_steps < 1:
+        raise ValueError("accum_steps must be >= 1")
     flat = flatten_parameters(model)
-    sched = OneCycle(lr, epochs, len(train_loader))
+    sched = OneCycle(lr, epochs, -(-len(train_loader) // accum_steps))
     opt = FlatAdamW(flat, lr=lr, schedule=sched, max_grad_norm=max_grad_norm)
     dev = flat.device
+    prev_arena = model._grad_arena
+    if accum_steps > 1:
+        model.set_grad_arena(torch.empty(flat.numel(), dtype=torch.float32, device=dev))
     eng = model.engine()
     prev = eng.param_grads
     eng.param_grads = False          # FlatAdamW reads the gradient arena; no .grad copies
@@ -309,14 +367,20 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     try:
         for epoch in range(epochs):
             losses = []
-            for batch in train_loader:
-                pred, off, y = _forward_batch(model, batch, dev)
-                loss = loss_fn(off, pred, y)
-                loss.backward()
-                opt.step(eng.grad_flat)
-                if not per_epoch_schedule:
-                    sched.step()
-                losses.append(float(loss))
+            if accum_steps == 1:
+                for batch in train_loader:
+                    pred, off, y = _forward_batch(model, batch, dev)
+                    loss = loss_fn(off, pred, y)
+                    loss.backward()
+                    opt.step(eng.grad_flat)
+                    if not per_epoch_schedule:
+                        sched.step()
+                    losses.append(float(loss))
+            else:
+                for group in _grouped(train_loader, accum_steps):
+                    losses.append(_accum_step(model, eng, opt, loss_fn, group, dev))
+                    if not per_epoch_schedule:
+                        sched.step()
             if per_epoch_schedule:
                 sched.step()
             hist_train.append(sum(losses) / max(len(losses), 1))
@@ -330,4 +394,6 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                     save_checkpoint(model, checkpoint)
     finally:
         eng.param_grads = prev       # ordinary autograd use after fit() gets .grad again
+        if accum_steps > 1:
+            model.set_grad_arena(prev_arena)
     return hist_train, hist_test

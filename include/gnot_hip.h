@@ -125,9 +125,24 @@ size_t gnot_plan_workspace_bytes(const gnot_plan* plan);
 int gnot_plan_bind_workspace(gnot_plan* plan, void* workspace, size_t bytes);
 int gnot_plan_bind_workspace_async(gnot_plan* plan, void* workspace, size_t bytes, void* stream);
 
-/* Parameter-gradient arena inside the workspace: offsets (in floats) of every Linear's weight
- * gradient and bias gradient, grad_off[2*i] / grad_off[2*i+1]. */
+/* Parameter-gradient arena: offsets (in floats) of every Linear's weight gradient and bias gradient,
+ * grad_off[2*i] / grad_off[2*i+1], relative to whichever arena is in use (the workspace's, or the
+ * caller's of gnot_plan_set_grad_arena). */
 int gnot_plan_grad_offsets(const gnot_plan* plan, int64_t* grad_off);
+
+/* Size of the gradient arena in floats: the sum over gnot_plan_linear_dims of out * in + out.  A function
+ * of the config alone, valid from gnot_plan_create on (0 for a null plan). */
+int64_t gnot_plan_grad_floats(const gnot_plan* plan);
+
+/* Caller-owned gradient arena.  By default the arena is a buffer of the workspace, which a new batch
+ * geometry re-plans (and may move or, with padded widths, clear at bind): gradients summed over several
+ * backwards cannot live there.  With arena != NULL (device memory, 16-byte aligned, `floats` >=
+ * gnot_plan_grad_floats -- GNOT_E_INVALID otherwise) the weight-gradient jobs, the gradient collectives of
+ * gnot_plan_set_grad_comm and gnot_debug_buffer("grads") use the caller's buffer instead, which no
+ * set_batch / bind touches; several plans may share one arena.  NULL returns to the workspace arena.  The
+ * workspace layout and size are the same either way.  Changing the arena invalidates the batch, like the
+ * other setters: set_batch + bind again.  No reference counterpart (torch's .grad tensors play this role). */
+int gnot_plan_set_grad_arena(gnot_plan* plan, float* arena, int64_t floats);
 
 /* Re-pack the bound parameters into the kernels' MFMA operand images (call after every optimizer
  * step, before gnot_forward). */
@@ -140,8 +155,27 @@ int gnot_forward(gnot_plan* plan, const float* x, const float* theta, const floa
                  float* out, void* stream);
 
 /* Backward of the last gnot_forward: dout [P, out_dim] -> every parameter gradient, written
- * (overwritten) into the gradient arena. */
+ * (overwritten) into the gradient arena.  The same as gnot_backward_ex(plan, dout, 0, stream). */
 int gnot_backward(gnot_plan* plan, const float* dout, void* stream);
+
+/* Backward with options (gradient accumulation over micro-batches: the reference takes one optimizer
+ * step per batch of four meshes, main.py:41, which need not fit one plan).
+ *   GNOT_BWD_ACCUMULATE      every parameter gradient is ADDED onto the arena: the split-K finish of each
+ *                            weight-gradient job stores old + s, s being the fixed-order sum the plain
+ *                            backward stores (one add per element, no atomics: deterministic).  Needs a
+ *                            caller-owned arena (GNOT_E_STATE otherwise: the workspace arena does not
+ *                            survive a geometry change).  The first micro-batch of a group runs without
+ *                            the flag, so no clear is needed.  The attention states and the input
+ *                            gradients (gnot_input_grads) are per backward and never accumulated.
+ *   GNOT_BWD_SKIP_GRAD_COMM  this backward issues none of the gradient collectives of
+ *                            gnot_plan_set_grad_comm (no work on their stream, no join): every micro-batch
+ *                            but the last of a group.  The point-shard state all-reduces and the scramble
+ *                            all-to-all are not gradient collectives and always run.
+ * Unknown flag bits give GNOT_E_INVALID.  The flags are launch arguments, not part of the bound tables:
+ * one bound plan may overwrite in one backward and accumulate in the next, and a captured graph replays
+ * with the flags it was captured with. */
+enum { GNOT_BWD_ACCUMULATE = 1, GNOT_BWD_SKIP_GRAD_COMM = 2 };
+int gnot_backward_ex(gnot_plan* plan, const float* dout, int flags, void* stream);
 
 /* ---------------------------------------------------------------- point sharding (multi-GPU)
  * One process per GPU.  Every sample b of a batch is split over `world` ranks in contiguous point

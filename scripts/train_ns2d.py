@@ -43,6 +43,9 @@ def main():
                     help="training loss: RelL2Loss (main.py:98) or MSELoss (main.py:97); the test metric stays RelL2")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="FLOAT",
                     help="clip the global gradient norm to this value before every AdamW step (default: off)")
+    ap.add_argument("--accum-steps", type=int, default=1, metavar="N",
+                    help="accumulate gradients over N consecutive batches per optimizer step (an effective batch of "
+                         "N x --batch meshes when that many do not fit one plan; default 1: a step per batch)")
     args = ap.parse_args()
     if args.synthetic:
         rng = np.random.default_rng(0)
@@ -61,7 +64,7 @@ def main():
     _, test = train.fit(model, dl(tr, True), dl(te, False), epochs=args.epochs,
                         per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint,
                         loss_fn=train.MSELoss() if args.loss == "mse" else train.RelL2Loss(),
-                        max_grad_norm=args.grad_clip)
+                        max_grad_norm=args.grad_clip, accum_steps=args.accum_steps)
     print(f"\nBest Test Metric: {min(test)}")
 
 
