@@ -2519,5 +2519,21 @@ extern "C" int gnot_adamw_step_clipped(float* param, const float* grad, float* e
   return GNOT_OK;
 }
 
+extern "C" int gnot_grad_norm(const float* grad, int64_t n, const float* hyper, float* work, float* clip, void* stream) {
+  if (!grad || !hyper || !work || !clip) return fail(GNOT_E_INVALID, "bad grad_norm arguments");
+  if (n < 1 || grad_clip_partials(n) >= (1L << 24)) return fail(GNOT_E_INVALID, "grad_norm: n out of range");
+  GNOT_CK(launch_grad_norm(grad, n, hyper, work, clip, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                       const float* hyper, const float* clip, int32_t* guard, void* stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 1 || !hyper || !clip || !guard)
+    return fail(GNOT_E_INVALID, "bad guarded adamw arguments");
+  GNOT_CK(launch_adamw_guarded(param, grad, exp_avg, exp_avg_sq, n, hyper, clip, guard,
+                               static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
 extern "C" const char* gnot_last_error(void) { return g_err.c_str(); }
 extern "C" const char* gnot_version(void) { return "gnot-mi355x 0.1 (gfx950, fp32 MFMA)"; }

@@ -304,7 +304,13 @@ long grad_clip_partials(long n);
 // work: grad_clip_partials(n) floats; clip: 2 floats {norm, coefficient}
 hipError_t launch_grad_clip(const float* grad, long n, const float* hyper, float max_norm, float* work, float* clip,
                             hipStream_t s);
+// the same two stages without a max_norm: clip = {norm (launch_grad_clip's bits), 1.0f}
+hipError_t launch_grad_norm(const float* grad, long n, const float* hyper, float* work, float* clip, hipStream_t s);
 hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
                                 const float* clip, hipStream_t s);
+// launch_adamw_clipped unless clip[0] is NaN or +-inf: then nothing but guard (2 ints {skipped count, skipped
+// now}) is written.  n >= 1.
+hipError_t launch_adamw_guarded(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
+                                const float* clip, int* guard, hipStream_t s);
 
 }  // namespace gnot

@@ -12,6 +12,8 @@
 //             shape of the rel_l2 passes.
 //   grad_clip global L2 norm of the flat gradient and torch.nn.utils.clip_grad_norm_'s coefficient, on
 //             the device (two fixed-order stages), consumed by adamw_clipped_kernel.
+//   guarded   the clipped update behind a device-side test of that norm: a NaN or infinite norm leaves
+//             the parameters and both moments untouched and counts the skipped step (adamw_guarded_kernel).
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
@@ -239,10 +241,11 @@ __global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict
 }
 
 // clip[0] = |grad_scale| sqrt(sum g^2), the norm of the gradient AdamW consumes (hyper[7] scales it);
-// clip[1] = min(1, max_norm / (norm + 1e-6)) as torch clamps it: a NaN norm stays a NaN coefficient
+// clip[1] = min(1, max_norm / (norm + 1e-6)) as torch clamps it: a NaN norm stays a NaN coefficient.
+// norm_only (gnot_grad_norm): the same norm, no max_norm, clip[1] = 1.0f.
 __global__ void __launch_bounds__(256) grad_clip_finish_kernel(const float* __restrict__ partial, long nparts,
                                                                const float* __restrict__ hyper, float max_norm,
-                                                               float* __restrict__ clip) {
+                                                               int norm_only, float* __restrict__ clip) {
   __shared__ float red[256];
   float acc = 0.f;
   for (long i = threadIdx.x; i < nparts; i += 256) acc += partial[i];
@@ -256,18 +259,27 @@ __global__ void __launch_bounds__(256) grad_clip_finish_kernel(const float* __re
     const float norm = fabsf(hyper[7]) * sqrtf(red[0]);
     const float c = max_norm / (norm + 1e-6f);
     clip[0] = norm;
-    clip[1] = c > 1.0f ? 1.0f : c;
+    clip[1] = (norm_only || c > 1.0f) ? 1.0f : c;
   }
 }
 
 // work: grad_clip_partials(n) floats
-hipError_t launch_grad_clip(const float* grad, long n, const float* hyper, float max_norm, float* work, float* clip,
-                            hipStream_t s) {
+static hipError_t launch_grad_norm_stages(const float* grad, long n, const float* hyper, float max_norm, int norm_only,
+                                          float* work, float* clip, hipStream_t s) {
   const long nparts = grad_clip_partials(n);
   hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nparts), dim3(256), 0, s, grad, n, work);
   hipLaunchKernelGGL(grad_clip_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)work, nparts, hyper, max_norm,
-                     clip);
+                     norm_only, clip);
   return hipGetLastError();
+}
+
+hipError_t launch_grad_clip(const float* grad, long n, const float* hyper, float max_norm, float* work, float* clip,
+                            hipStream_t s) {
+  return launch_grad_norm_stages(grad, n, hyper, max_norm, 0, work, clip, s);
+}
+
+hipError_t launch_grad_norm(const float* grad, long n, const float* hyper, float* work, float* clip, hipStream_t s) {
+  return launch_grad_norm_stages(grad, n, hyper, 1.0f, 1, work, clip, s);
 }
 
 // ---------------------------------------------------------------- AdamW over a flat arena
@@ -301,21 +313,19 @@ hipError_t launch_adamw(float* param, const float* grad, float* m, float* v, lon
   return hipGetLastError();
 }
 
-// adamw_kernel on the clipped gradient (grad[i] * grad_scale) * clip[1]; clip is what launch_grad_clip wrote,
-// read from device memory so a captured graph applies the coefficient of the step it replays.  Everything
-// after g is adamw_kernel's operation order: a coefficient of 1.0f gives its bits whenever grad[i] * grad_scale
-// is exact (a grad_scale of 1, which FlatAdamW writes, or any power of two).
-__global__ void __launch_bounds__(256) adamw_clipped_kernel(float* __restrict__ param, const float* __restrict__ grad,
-                                                            float* __restrict__ m, float* __restrict__ v, long n,
-                                                            const float* __restrict__ hyper,
-                                                            const float* __restrict__ clip) {
+// adamw_kernel on the clipped gradient (grad[i] * grad_scale) * coef over this thread's grid-stride elements: the
+// body of adamw_clipped_kernel and adamw_guarded_kernel.  Everything after g is adamw_kernel's operation
+// order: a coefficient of 1.0f gives its bits whenever grad[i] * grad_scale is exact (a grad_scale of 1, which
+// FlatAdamW writes, or any power of two).
+__device__ __forceinline__ void adamw_clipped_elements(float* __restrict__ param, const float* __restrict__ grad,
+                                                       float* __restrict__ m, float* __restrict__ v, long n,
+                                                       const float* __restrict__ hyper, float coef) {
   // Which multiply-adds of adamw_kernel's expressions the compiler fuses depends on the code around them
   // (the extra multiply here moved one), so the fusions it applies there are written out and no others
   // are allowed: exp_avg_sq = fma(g, (1 - beta2) g, beta2 v), the rest as the expressions read.
 #pragma clang fp contract(off)
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
   const float bc1 = hyper[5], bc2 = hyper[6], gs = hyper[7];
-  const float coef = clip[1];
   const float step_size = lr / bc1;
   const float bc2_sqrt = sqrtf(bc2);
   const float decay = fmaf(-lr, wd, 1.0f);
@@ -333,11 +343,46 @@ __global__ void __launch_bounds__(256) adamw_clipped_kernel(float* __restrict__ 
   }
 }
 
+// clip is what launch_grad_clip wrote, read from device memory so a captured graph applies the coefficient of
+// the step it replays.
+__global__ void __launch_bounds__(256) adamw_clipped_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                            float* __restrict__ m, float* __restrict__ v, long n,
+                                                            const float* __restrict__ hyper,
+                                                            const float* __restrict__ clip) {
+  adamw_clipped_elements(param, grad, m, v, n, hyper, clip[1]);
+}
+
 hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
                                 const float* clip, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const long blocks = std::min<long>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(adamw_clipped_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper, clip);
+  return hipGetLastError();
+}
+
+// adamw_clipped_kernel behind the non-finite guard: every thread reads the norm clip[0] (one value for the
+// whole grid, so the decision is uniform); NaN or +-inf (exponent bits all ones) -> no element of param / m / v
+// is written.  guard = {skipped launches since the caller zeroed it, 1 if this launch skipped else 0}, written
+// by thread 0 of workgroup 0 alone; launches on one stream are ordered, so the count needs no atomic.
+__global__ void __launch_bounds__(256) adamw_guarded_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                            float* __restrict__ m, float* __restrict__ v, long n,
+                                                            const float* __restrict__ hyper,
+                                                            const float* __restrict__ clip, int* __restrict__ guard) {
+  const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (!finite) guard[0] = guard[0] + 1;
+    guard[1] = finite ? 0 : 1;
+  }
+  if (!finite) return;
+  adamw_clipped_elements(param, grad, m, v, n, hyper, clip[1]);
+}
+
+// n >= 1 (the guard is written by the grid's first thread); the grid of launch_adamw
+hipError_t launch_adamw_guarded(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
+                                const float* clip, int* guard, hipStream_t s) {
+  const long blocks = std::min<long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(adamw_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper, clip,
+                     guard);
   return hipGetLastError();
 }
 

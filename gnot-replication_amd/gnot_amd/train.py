@@ -13,12 +13,18 @@
   gradient buffer directly.  The hyper-parameters live in a small device array that `prepare()`
   refreshes from the host schedule, so `launch()` can be captured in a hipGraph.  `max_grad_norm`
   adds torch.nn.utils.clip_grad_norm_ in front of the update, computed on the device
-  (gnot_grad_clip + gnot_adamw_step_clipped), still without a host synchronisation.
+  (gnot_grad_clip + gnot_adamw_step_clipped), still without a host synchronisation.  `skip_nonfinite`
+  puts a device-side test of that norm in front of the update (gnot_adamw_step_guarded): a NaN or
+  infinite gradient leaves parameters and moments untouched.
+* `save_training_state` / `load_training_state` and `fit(state_path=..., resume=True)` -- the whole
+  training state (weights, moments, step count, schedule position, histories, host random state) once
+  per epoch, so a killed run continues bit for bit.
 * `MSELoss` -- reference loss.py:4-12 (dgl AvgPooling: per-sample mean over points, then the mean over
   samples x channels), the reference's second loss, through gnot_mse_loss.
 """
 import ctypes
 import math
+import os
 
 import torch
 
@@ -114,6 +120,9 @@ class OneCycle:
 
     def __init__(self, max_lr, epochs, steps_per_epoch, pct_start=0.3, div_factor=25.0, final_div_factor=1e4,
                  base_momentum=0.85, max_momentum=0.95):
+        self._ctor = dict(max_lr=max_lr, epochs=epochs, steps_per_epoch=steps_per_epoch, pct_start=pct_start,
+                          div_factor=div_factor, final_div_factor=final_div_factor, base_momentum=base_momentum,
+                          max_momentum=max_momentum)
         self.total = epochs * steps_per_epoch
         self.max_lr = max_lr
         self.initial_lr = max_lr / div_factor
@@ -139,6 +148,20 @@ class OneCycle:
 
     def step(self):
         self.last += 1
+
+    def state_dict(self):
+        """`last` and the constructor values (plain Python numbers)."""
+        return dict(self._ctor, last=self.last, total=self.total)
+
+    def load_state_dict(self, state):
+        """Continue at the stored position.  A schedule of a different length or peak is another trajectory
+        and is refused; the shape arguments (pct_start, the factors, the momenta) are taken from the file."""
+        for k in ("total", "max_lr"):
+            if state[k] != getattr(self, k):
+                raise ValueError(f"OneCycle.load_state_dict: {k} is {state[k]!r} in the stored state, "
+                                 f"{getattr(self, k)!r} here")
+        self.__init__(**{k: state[k] for k in self._ctor})
+        self.last = int(state["last"])
 
 
 # ------------------------------------------------------------------ AdamW (main.py:51)
@@ -173,19 +196,34 @@ class FlatAdamW:
     NOT modified: `grad_flat` stays unclipped after the step.  `grad_norm` is a 0-d device tensor (a view
     of the norm the last launch computed, before clipping); reading it is the caller's synchronisation.
     With several ranks every rank holds the same summed gradient after the backward, so every rank
-    computes the same norm: no collective.  None (default): the plain gnot_adamw_step, nothing else."""
+    computes the same norm: no collective.  None (default): the plain gnot_adamw_step, nothing else.
+
+    skip_nonfinite: a step whose gradient norm is NaN or infinite changes no parameter and no moment.  The
+    test runs on the device inside the update kernel (gnot_adamw_step_guarded, behind gnot_grad_clip with
+    max_grad_norm and gnot_grad_norm without), so `launch()` still never synchronises and stays capturable:
+    every replay decides on its own gradient.  `skipped_steps` (skips since construction) and `last_skipped`
+    (1 if the last launch skipped) are 0-d int32 device views; reading them is the caller's
+    synchronisation, like `grad_norm`.  A skipped step still consumes its step number `t` and its schedule
+    slot -- `prepare()` runs before the device knows the outcome -- unlike torch's GradScaler, which does
+    not call optimizer.step() on a skip.  A finite gradient whose sum of squares overflows fp32 is skipped
+    too.  With ranks or accumulated micro-batches every rank tests the same summed arena: one decision.
+    False (default): the paths above, unchanged."""
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, schedule=None,
-                 max_grad_norm=None):
+                 max_grad_norm=None, skip_nonfinite=False):
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self.grad_norm = None
-        if self.max_grad_norm is not None:
-            if not (self.max_grad_norm > 0 and math.isfinite(self.max_grad_norm)):
-                raise ValueError("max_grad_norm must be positive and finite")
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.grad_norm = self.skipped_steps = self.last_skipped = None
+        if self.max_grad_norm is not None and not (self.max_grad_norm > 0 and math.isfinite(self.max_grad_norm)):
+            raise ValueError("max_grad_norm must be positive and finite")
+        if self.max_grad_norm is not None or self.skip_nonfinite:
             self._clip = torch.zeros(2, dtype=torch.float32, device=flat.device)       # {norm, coefficient}
             self._clip_work = torch.empty(_lib.load().gnot_grad_clip_work_floats(flat.numel()),
                                           dtype=torch.float32, device=flat.device)
             self.grad_norm = self._clip[0]
+        if self.skip_nonfinite:
+            self._guard = torch.zeros(2, dtype=torch.int32, device=flat.device)        # {skipped, skipped now}
+            self.skipped_steps, self.last_skipped = self._guard[0], self._guard[1]
         self.flat = flat
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
@@ -215,11 +253,23 @@ class FlatAdamW:
         self._ev[k] = ev
 
     def launch(self, grad):
-        """The update kernel only -- with max_grad_norm, the two norm kernels and the clipped update
-        (graph-capturable either way)."""
+        """The update kernel only -- with max_grad_norm, the two norm kernels and the clipped update; with
+        skip_nonfinite, the two norm kernels and the guarded update (graph-capturable every way)."""
         if grad.numel() != self.flat.numel():
             raise ValueError("gradient buffer does not match the parameter arena")
         s = ctypes.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
+        if self.skip_nonfinite:
+            lib = _lib.load()
+            if self.max_grad_norm is not None:
+                _lib.check(lib.gnot_grad_clip(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
+                                              self.max_grad_norm, self._clip_work.data_ptr(), self._clip.data_ptr(), s))
+            else:
+                _lib.check(lib.gnot_grad_norm(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
+                                              self._clip_work.data_ptr(), self._clip.data_ptr(), s))
+            _lib.check(lib.gnot_adamw_step_guarded(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
+                                                   self.v.data_ptr(), self.flat.numel(), self.hyper.data_ptr(),
+                                                   self._clip.data_ptr(), self._guard.data_ptr(), s))
+            return
         if self.max_grad_norm is not None:
             lib = _lib.load()
             _lib.check(lib.gnot_grad_clip(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(), self.max_grad_norm,
@@ -235,6 +285,30 @@ class FlatAdamW:
         self.prepare()
         self.launch(grad)
 
+    def state_dict(self):
+        """Copies of exp_avg / exp_avg_sq, the step count, the skipped count (a device read when
+        skip_nonfinite is on) and the scalar hyper-parameters.  The parameters themselves are the model's."""
+        return {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "t": self.t,
+                "skipped": int(self.skipped_steps) if self.skip_nonfinite else 0, "numel": self.flat.numel(),
+                "lr": self.lr, "beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps,
+                "weight_decay": self.wd, "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
+
+    def load_state_dict(self, state):
+        """Continue from state_dict()'s values: moments, step count, skipped count, lr / betas / eps /
+        weight_decay.  An arena of another size is refused.  max_grad_norm and skip_nonfinite stay the
+        constructor's (they decide which kernels launch() issues)."""
+        if int(state["numel"]) != self.flat.numel() or state["exp_avg"].numel() != self.flat.numel() \
+                or state["exp_avg_sq"].numel() != self.flat.numel():
+            raise ValueError(f"FlatAdamW.load_state_dict: the stored state has numel {int(state['numel'])}, "
+                             f"this arena {self.flat.numel()}")
+        self.m.copy_(state["exp_avg"].reshape(-1))
+        self.v.copy_(state["exp_avg_sq"].reshape(-1))
+        self.t = int(state["t"])
+        self.lr, self.betas, self.eps, self.wd = state["lr"], (state["beta1"], state["beta2"]), state["eps"], \
+            state["weight_decay"]
+        if self.skip_nonfinite:
+            self._guard.copy_(torch.tensor([int(state["skipped"]), 0], dtype=torch.int32))
+
 
 # ------------------------------------------------------------------ driver (main.py:55-153)
 def save_checkpoint(model, path):
@@ -246,6 +320,62 @@ def load_checkpoint(model, path):
     """Load a reference (or gnot_amd) state_dict checkpoint; tensors only (weights_only=True)."""
     model.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
     return model
+
+
+# the arguments of fit that decide the trajectory: a stored state continues only the run that wrote it
+# (compared in this order; steps_per_epoch = ceil(len(train_loader) / accum_steps) last, so a changed
+# accum_steps is named as such)
+TRAJECTORY_ARGS = ("epochs", "lr", "accum_steps", "per_epoch_schedule", "max_grad_norm", "loss", "skip_nonfinite",
+                   "steps_per_epoch")
+
+
+def _cpu(obj):
+    """tensors of a (nested) state moved to the host as copies, everything else as it is"""
+    if torch.is_tensor(obj):
+        return obj.detach().cpu().clone()
+    if isinstance(obj, dict):
+        return {k: _cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_cpu(v) for v in obj]
+    return obj
+
+
+def rng_state(train_loader=None):
+    """The host random state a shuffling loader draws from: torch's CPU generator (a DataLoader without a
+    generator seeds every epoch's permutation from it) and the loader's own `generator`, if it has one."""
+    gen = getattr(train_loader, "generator", None)
+    return {"torch": torch.get_rng_state(), "loader": gen.get_state() if gen is not None else None}
+
+
+def restore_rng_state(state, train_loader=None):
+    """Put back what rng_state() returned (the loader state only if this loader has a generator too)."""
+    torch.set_rng_state(state["torch"])
+    gen = getattr(train_loader, "generator", None)
+    if gen is not None and state.get("loader") is not None:
+        gen.set_state(state["loader"])
+
+
+def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, hist_test, args, train_loader=None):
+    """Everything fit needs to continue a run bit for bit, in one torch.save of tensors (on the host) and plain
+    Python values, readable with weights_only=True: the model state_dict (reference keys), the optimizer's
+    and the schedule's state_dict(), the next epoch, the best metric, both histories, the host random state
+    (rng_state) and the trajectory arguments `args` (TRAJECTORY_ARGS).  Written under a temporary name in
+    the same directory and moved into place with os.replace: a kill in mid-write leaves the previous file."""
+    state = {"model": _cpu(model.state_dict()), "optimizer": _cpu(opt.state_dict()), "schedule": sched.state_dict(),
+             "next_epoch": int(next_epoch), "best": float(best), "hist_train": [float(v) for v in hist_train],
+             "hist_test": [float(v) for v in hist_test], "rng": rng_state(train_loader), "args": dict(args)}
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        torch.save(state, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def load_training_state(path):
+    """The dict save_training_state wrote; tensors on the host (weights_only=True, like load_checkpoint)."""
+    return torch.load(path, map_location="cpu", weights_only=True)
 
 
 def _to(batch, dev):
@@ -331,7 +461,8 @@ def _accum_step(model, eng, opt, loss_fn, group, dev):
 
 
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
-        log=print, loss_fn=None, max_grad_norm=None, accum_steps=1):
+        log=print, loss_fn=None, max_grad_norm=None, accum_steps=1, skip_nonfinite=False, state_path=None,
+        resume=False):
     """The reference training loop (main.py:50-153): AdamW(lr) + OneCycleLR(max_lr=lr, steps_per_epoch,
     epochs), RelL2 loss, per-epoch test metric and best checkpoint.  With per_epoch_schedule=True the
     schedule is stepped once per epoch, as main.py:106 does.  The loaders decide the batch form:
@@ -347,13 +478,39 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     the arena once per group, and the schedule counts optimizer steps.  The logged loss of a step is
     sum_i (B_i / sum B) loss_i.  A batch of main.py:41's four large meshes that does not fit one plan
     runs as accum_steps = 4 loader batches of one.  1 (default): one step per loader batch, no arena.
-    Returns (train losses per epoch, test metrics per epoch)."""
+    skip_nonfinite: FlatAdamW's device-side guard -- a step (with accum_steps, a whole group) whose gradient
+    norm is NaN or infinite leaves the parameters and moments alone.  An epoch's train loss is then the mean
+    over its finite step losses, and an epoch that skipped steps logs their number (one device read per
+    epoch).  False (default): one NaN gradient makes every parameter NaN, as in the reference's loop.
+    state_path: after every epoch (after its evaluation and checkpoint) the whole training state is written
+    there (save_training_state).  resume: if state_path exists, continue the run it holds -- weights,
+    moments, step count, schedule position, histories, best metric, host random state -- at its next epoch,
+    bit for bit the uninterrupted run; if it does not exist, start from scratch, so one command line serves
+    the first launch and every restart.  A file written under other trajectory arguments (TRAJECTORY_ARGS)
+    is refused.
+    Returns (train losses per epoch, test metrics per epoch), the resumed epochs included."""
     accum_steps = int(accum_steps)
     if accum_steps < 1:
         raise ValueError("accum_steps must be >= 1")
+    if resume and not state_path:
+        raise ValueError("resume needs a state_path")
+    loss_fn = loss_fn or RelL2Loss()
+    steps_per_epoch = -(-len(train_loader) // accum_steps)
+    args = dict(epochs=int(epochs), lr=float(lr), steps_per_epoch=steps_per_epoch, accum_steps=accum_steps,
+                per_epoch_schedule=bool(per_epoch_schedule),
+                max_grad_norm=None if max_grad_norm is None else float(max_grad_norm),
+                loss=type(loss_fn).__name__, skip_nonfinite=bool(skip_nonfinite))
+    state = None
+    if resume and os.path.exists(state_path):
+        state = load_training_state(state_path)
+        for k in TRAJECTORY_ARGS:
+            if state["args"].get(k) != args[k]:
+                raise ValueError(f"fit(resume=True): {state_path} was written with {k}={state['args'].get(k)!r}, "
+                                 f"this call has {k}={args[k]!r}")
+        model.load_state_dict(state["model"])       # before the parameters move into the flat arena
     flat = flatten_parameters(model)
-    sched = OneCycle(lr, epochs, -(-len(train_loader) // accum_steps))
-    opt = FlatAdamW(flat, lr=lr, schedule=sched, max_grad_norm=max_grad_norm)
+    sched = OneCycle(lr, epochs, steps_per_epoch)
+    opt = FlatAdamW(flat, lr=lr, schedule=sched, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     dev = flat.device
     prev_arena = model._grad_arena
     if accum_steps > 1:
@@ -361,11 +518,16 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     eng = model.engine()
     prev = eng.param_grads
     eng.param_grads = False          # FlatAdamW reads the gradient arena; no .grad copies
-    loss_fn = loss_fn or RelL2Loss()
     metric = loss_fn if type(loss_fn) is RelL2Loss else RelL2Loss()
-    best, hist_train, hist_test = float("inf"), [], []
+    best, hist_train, hist_test, first, skipped = float("inf"), [], [], 0, 0
+    if state is not None:
+        opt.load_state_dict(state["optimizer"])
+        sched.load_state_dict(state["schedule"])
+        best, hist_train, hist_test = state["best"], list(state["hist_train"]), list(state["hist_test"])
+        first, skipped = state["next_epoch"], int(state["optimizer"]["skipped"])
+        restore_rng_state(state["rng"], train_loader)
     try:
-        for epoch in range(epochs):
+        for epoch in range(first, epochs):
             losses = []
             if accum_steps == 1:
                 for batch in train_loader:
@@ -383,8 +545,15 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                         sched.step()
             if per_epoch_schedule:
                 sched.step()
+            if skip_nonfinite:
+                losses = [l for l in losses if math.isfinite(l)]
             hist_train.append(sum(losses) / max(len(losses), 1))
             log(f"Epoch {epoch}, Loss: {hist_train[-1]}")
+            if skip_nonfinite:
+                total = int(opt.skipped_steps)
+                if total > skipped:
+                    log(f"Epoch {epoch}, Skipped steps: {total - skipped} (non-finite gradient norm)")
+                skipped = total
             if test_loader is not None:
                 res = evaluate(model, test_loader, metric)
                 hist_test.append(res)
@@ -392,6 +561,9 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                 if res < best and checkpoint:
                     best = res
                     save_checkpoint(model, checkpoint)
+            if state_path:
+                save_training_state(state_path, model, opt, sched, epoch + 1, best, hist_train, hist_test, args,
+                                    train_loader)
     finally:
         eng.param_grads = prev       # ordinary autograd use after fit() gets .grad again
         if accum_steps > 1:

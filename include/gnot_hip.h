@@ -273,6 +273,27 @@ int gnot_grad_clip(const float* grad, int64_t n, const float* hyper, float max_n
 int gnot_adamw_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                             const float* hyper, const float* clip, void* stream);
 
+/* The two reduction stages of gnot_grad_clip without a max_norm: clip[0] = |hyper[7]| sqrt(sum g^2), with
+ * the bits gnot_grad_clip writes there for the same grad, n and hyper, and clip[1] = 1.0f.  work as for
+ * gnot_grad_clip (gnot_grad_clip_work_floats(n) floats); n >= 1.  The norm in front of
+ * gnot_adamw_step_guarded when nothing is clipped. */
+int gnot_grad_norm(const float* grad, int64_t n, const float* hyper, float* work, float* clip, void* stream);
+
+/* gnot_adamw_step_clipped behind a device-side test of the norm: clip as written by gnot_grad_clip or
+ * gnot_grad_norm, read from device memory when the kernel runs.  guard: DEVICE array of two int32,
+ * {steps skipped since the caller zeroed it, 1 if this launch skipped else 0}.
+ *   clip[0] finite:      the update of gnot_adamw_step_clipped, bit for bit; guard[1] = 0.
+ *   clip[0] NaN or +-inf: no element of param, exp_avg or exp_avg_sq is written; guard[0] += 1, guard[1] = 1.
+ * Kernel launches only, stream-ordered, nothing read back: capturable, and every replay of a captured
+ * graph decides on its own clip.  n >= 1.
+ * A skipped step still consumes its step number and its schedule slot: the host writes t and the bias
+ * corrections of hyper before the device knows the outcome, so only the parameters and the moments are
+ * left alone.  (torch's GradScaler, in contrast, does not call optimizer.step() on a skip, so there the
+ * optimizer's step count does not advance.)  A finite gradient whose sum of squares overflows fp32 has
+ * an infinite norm and is skipped as well. */
+int gnot_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                            const float* hyper, const float* clip, int32_t* guard, void* stream);
+
 /* Live kernel timing for the bench's roofline: while enabled, every launch of kernel class `kind`
  * ("moe_fwd" fused expert chains forward, "moe_bwd" their backward, "wgrad" weight-gradient GEMMs;
  * "" disables) is bracketed by hipEvents on its stream.  gnot_profile_read synchronizes on those

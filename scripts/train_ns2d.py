@@ -46,6 +46,13 @@ def main():
     ap.add_argument("--accum-steps", type=int, default=1, metavar="N",
                     help="accumulate gradients over N consecutive batches per optimizer step (an effective batch of "
                          "N x --batch meshes when that many do not fit one plan; default 1: a step per batch)")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="leave the parameters and moments alone on a step whose gradient norm is NaN or infinite "
+                         "(tested on the device; default: off, one bad gradient ends the run)")
+    ap.add_argument("--state", default=None, metavar="PATH",
+                    help="write the whole training state here after every epoch (default: off)")
+    ap.add_argument("--resume", action="store_true",
+                    help="continue the run stored in --state if that file exists, else start from scratch")
     args = ap.parse_args()
     if args.synthetic:
         rng = np.random.default_rng(0)
@@ -64,7 +71,8 @@ def main():
     _, test = train.fit(model, dl(tr, True), dl(te, False), epochs=args.epochs,
                         per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint,
                         loss_fn=train.MSELoss() if args.loss == "mse" else train.RelL2Loss(),
-                        max_grad_norm=args.grad_clip, accum_steps=args.accum_steps)
+                        max_grad_norm=args.grad_clip, accum_steps=args.accum_steps,
+                        skip_nonfinite=args.skip_nonfinite, state_path=args.state, resume=args.resume)
     print(f"\nBest Test Metric: {min(test)}")
 
 
