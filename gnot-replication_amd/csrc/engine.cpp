@@ -2535,5 +2535,23 @@ extern "C" int gnot_adamw_step_guarded(float* param, const float* grad, float* e
   return GNOT_OK;
 }
 
+extern "C" int gnot_ema_update(float* ema, const float* param, int64_t n, const float* weight, void* stream) {
+  if (!ema || !param || n < 1 || !weight) return fail(GNOT_E_INVALID, "bad ema_update arguments");
+  if (ema == param) return fail(GNOT_E_INVALID, "ema_update: ema must not alias param");
+  GNOT_CK(launch_ema_update(ema, param, n, weight, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                                   int64_t n, const float* hyper, const float* clip, int32_t* guard, void* stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !ema || n < 1 || !hyper)
+    return fail(GNOT_E_INVALID, "bad ema adamw arguments");
+  if (guard && !clip) return fail(GNOT_E_INVALID, "adamw_step_ema: a guard needs a clip");
+  if (ema == param) return fail(GNOT_E_INVALID, "adamw_step_ema: ema must not alias param");
+  GNOT_CK(launch_adamw_ema(param, grad, exp_avg, exp_avg_sq, ema, n, hyper, clip, guard,
+                           static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
 extern "C" const char* gnot_last_error(void) { return g_err.c_str(); }
 extern "C" const char* gnot_version(void) { return "gnot-mi355x 0.1 (gfx950, fp32 MFMA)"; }

@@ -312,5 +312,11 @@ hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float
 // now}) is written.  n >= 1.
 hipError_t launch_adamw_guarded(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
                                 const float* clip, int* guard, hipStream_t s);
+// ema = fma(weight[0], param - ema, ema); n >= 1, ema and param distinct arrays
+hipError_t launch_ema_update(float* ema, const float* param, long n, const float* weight, hipStream_t s);
+// the plain (clip == nullptr), clipped or guarded (guard != nullptr, needs clip) update with launch_ema_update's
+// pass on the stored parameter fused in; hyper: 9 floats, hyper[8] the EMA weight.  n >= 1.
+hipError_t launch_adamw_ema(float* param, const float* grad, float* m, float* v, float* ema, long n,
+                            const float* hyper, const float* clip, int* guard, hipStream_t s);
 
 }  // namespace gnot

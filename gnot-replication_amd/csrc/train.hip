@@ -14,6 +14,9 @@
 //             the device (two fixed-order stages), consumed by adamw_clipped_kernel.
 //   guarded   the clipped update behind a device-side test of that norm: a NaN or infinite norm leaves
 //             the parameters and both moments untouched and counts the skipped step (adamw_guarded_kernel).
+//   ema       an exponential moving average of the parameters, ema += w (param - ema), as one more stream of
+//             the update kernels (adamw_ema_kernel: plain, clipped or guarded) or as a pass of its own
+//             (ema_update_kernel); w comes from device memory like the other hyper-parameters.
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
@@ -317,8 +320,13 @@ hipError_t launch_adamw(float* param, const float* grad, float* m, float* v, lon
 // body of adamw_clipped_kernel and adamw_guarded_kernel.  Everything after g is adamw_kernel's operation
 // order: a coefficient of 1.0f gives its bits whenever grad[i] * grad_scale is exact (a grad_scale of 1, which
 // FlatAdamW writes, or any power of two).
+// kEma: the element's average follows the parameter value just stored, ema = fma(w, p - ema, ema) with
+// w = hyper[8] -- ema_update_kernel's expression on the same operands, so fused and stand-alone agree bit for
+// bit; param / m / v are computed exactly as without it.
+template <bool kEma>
 __device__ __forceinline__ void adamw_clipped_elements(float* __restrict__ param, const float* __restrict__ grad,
-                                                       float* __restrict__ m, float* __restrict__ v, long n,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ ema, long n,
                                                        const float* __restrict__ hyper, float coef) {
   // Which multiply-adds of adamw_kernel's expressions the compiler fuses depends on the code around them
   // (the extra multiply here moved one), so the fusions it applies there are written out and no others
@@ -329,6 +337,7 @@ __device__ __forceinline__ void adamw_clipped_elements(float* __restrict__ param
   const float step_size = lr / bc1;
   const float bc2_sqrt = sqrtf(bc2);
   const float decay = fmaf(-lr, wd, 1.0f);
+  const float w = kEma ? hyper[8] : 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float gi = grad[i] * gs;
     const float g = gi * coef;
@@ -340,6 +349,10 @@ __device__ __forceinline__ void adamw_clipped_elements(float* __restrict__ param
     param[i] = p;
     m[i] = mi;
     v[i] = vi;
+    if (kEma) {
+      const float e = ema[i];
+      ema[i] = fmaf(w, p - e, e);
+    }
   }
 }
 
@@ -349,7 +362,7 @@ __global__ void __launch_bounds__(256) adamw_clipped_kernel(float* __restrict__ 
                                                             float* __restrict__ m, float* __restrict__ v, long n,
                                                             const float* __restrict__ hyper,
                                                             const float* __restrict__ clip) {
-  adamw_clipped_elements(param, grad, m, v, n, hyper, clip[1]);
+  adamw_clipped_elements<false>(param, grad, m, v, nullptr, n, hyper, clip[1]);
 }
 
 hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
@@ -374,7 +387,7 @@ __global__ void __launch_bounds__(256) adamw_guarded_kernel(float* __restrict__ 
     guard[1] = finite ? 0 : 1;
   }
   if (!finite) return;
-  adamw_clipped_elements(param, grad, m, v, n, hyper, clip[1]);
+  adamw_clipped_elements<false>(param, grad, m, v, nullptr, n, hyper, clip[1]);
 }
 
 // n >= 1 (the guard is written by the grid's first thread); the grid of launch_adamw
@@ -382,6 +395,54 @@ hipError_t launch_adamw_guarded(float* param, const float* grad, float* m, float
                                 const float* clip, int* guard, hipStream_t s) {
   const long blocks = std::min<long>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(adamw_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper, clip,
+                     guard);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- weight EMA
+// ema = fma(w, param - ema, ema) over n elements, w = weight[0] from device memory (a captured graph picks up
+// each step's value).  The subtraction is rounded on its own: the expression of adamw_clipped_elements<true>.
+__global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ ema, const float* __restrict__ param,
+                                                         long n, const float* __restrict__ weight) {
+#pragma clang fp contract(off)
+  const float w = weight[0];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float e = ema[i];
+    ema[i] = fmaf(w, param[i] - e, e);
+  }
+}
+
+// n >= 1; the grid of launch_adamw
+hipError_t launch_ema_update(float* ema, const float* param, long n, const float* weight, hipStream_t s) {
+  const long blocks = std::min<long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ema, param, n, weight);
+  return hipGetLastError();
+}
+
+// The three updates with the average as a fifth stream, one kernel: clip == nullptr is the plain update (the
+// clipped body with a coefficient of 1.0f, adamw_kernel's bits), guard != nullptr (needs clip) puts
+// adamw_guarded_kernel's test in front -- a skipped step writes no element of ema either.  hyper has 9 floats.
+__global__ void __launch_bounds__(256) adamw_ema_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                        float* __restrict__ m, float* __restrict__ v,
+                                                        float* __restrict__ ema, long n,
+                                                        const float* __restrict__ hyper,
+                                                        const float* __restrict__ clip, int* __restrict__ guard) {
+  if (guard) {
+    const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (!finite) guard[0] = guard[0] + 1;
+      guard[1] = finite ? 0 : 1;
+    }
+    if (!finite) return;
+  }
+  adamw_clipped_elements<true>(param, grad, m, v, ema, n, hyper, clip ? clip[1] : 1.0f);
+}
+
+// n >= 1; the grid of launch_adamw
+hipError_t launch_adamw_ema(float* param, const float* grad, float* m, float* v, float* ema, long n,
+                            const float* hyper, const float* clip, int* guard, hipStream_t s) {
+  const long blocks = std::min<long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, ema, n, hyper, clip,
                      guard);
   return hipGetLastError();
 }

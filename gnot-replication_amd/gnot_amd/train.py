@@ -21,7 +21,11 @@
   per epoch, so a killed run continues bit for bit.
 * `MSELoss` -- reference loss.py:4-12 (dgl AvgPooling: per-sample mean over points, then the mean over
   samples x channels), the reference's second loss, through gnot_mse_loss.
+* `WeightEMA` and `FlatAdamW(ema_decay=...)` / `fit(ema_decay=...)` -- an exponential moving average of the
+  parameters, updated inside the AdamW kernel (gnot_adamw_step_ema) and evaluated and checkpointed in place
+  of the raw weights (`WeightEMA.swapped()`).
 """
+import contextlib
 import ctypes
 import math
 import os
@@ -185,6 +189,69 @@ def flatten_parameters(model):
     return flat
 
 
+class WeightEMA:
+    """An exponential moving average of a flat parameter arena: ema += w_t (flat - ema) after optimizer step t,
+    w_t = 1 - decay_t.  `ema` starts as a copy of `flat`.
+    warmup: decay_t = min(decay, (1 + t) / (10 + t)), so the first steps -- far from anything worth
+    averaging -- fade quickly; False: decay_t = decay throughout.
+    `FlatAdamW(ema_decay=...)` owns one and updates it inside its update kernel; `update(t)` is the same
+    arithmetic as a pass of its own (gnot_ema_update) behind any other optimizer.  `swapped()` makes the
+    average the module's parameters for an evaluation or a checkpoint."""
+
+    def __init__(self, flat, decay, warmup=True):
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError("WeightEMA: decay must lie strictly between 0 and 1")
+        self.flat, self.decay, self.warmup = flat, decay, bool(warmup)
+        self.ema = flat.detach().clone()
+        self._w = torch.zeros(1, dtype=torch.float32, device=flat.device)
+
+    def weight(self, t):
+        """w_t = 1 - decay_t of optimizer step t (1, 2, ...): host double arithmetic, rounded to fp32."""
+        d = min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
+        return torch.tensor(1.0 - d, dtype=torch.float32).item()
+
+    def update(self, t):
+        """ema += w_t (flat - ema) on the current stream (one fill, one kernel, no synchronisation)."""
+        self._w.fill_(self.weight(t))
+        s = ctypes.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
+        _lib.check(_lib.load().gnot_ema_update(self.ema.data_ptr(), self.flat.data_ptr(), self.flat.numel(),
+                                               self._w.data_ptr(), s))
+
+    def _exchange(self):
+        with torch.no_grad():
+            tmp = self.flat.clone()
+            self.flat.copy_(self.ema)
+            self.ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def swapped(self):
+        """Inside the block `flat` -- the module's parameters -- holds the average and `ema` the raw weights;
+        the contents are exchanged in place (the engine re-packs its weight images from the same pointers at
+        every forward: no rebind) and exchanged back on exit, also after an exception."""
+        self._exchange()
+        try:
+            yield self
+        finally:
+            self._exchange()
+
+    def state_dict(self):
+        return {"ema": self.ema.detach().clone(), "decay": self.decay, "warmup": self.warmup,
+                "numel": self.flat.numel()}
+
+    def load_state_dict(self, state):
+        """Continue the stored average.  Another size or decay is another average and is refused; the warm-up
+        flag is taken from the file."""
+        if int(state["numel"]) != self.flat.numel() or state["ema"].numel() != self.flat.numel():
+            raise ValueError(f"WeightEMA.load_state_dict: the stored average has numel {int(state['numel'])}, "
+                             f"this arena {self.flat.numel()}")
+        if float(state["decay"]) != self.decay:
+            raise ValueError(f"WeightEMA.load_state_dict: decay is {state['decay']!r} in the stored state, "
+                             f"{self.decay!r} here")
+        self.warmup = bool(state["warmup"])
+        self.ema.copy_(state["ema"].reshape(-1))
+
+
 class FlatAdamW:
     """torch.optim.AdamW(params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2) on a flat arena.
     grad: the flat gradient buffer of the step (Engine.grad_flat, same layout as `flat`).
@@ -207,10 +274,18 @@ class FlatAdamW:
     slot -- `prepare()` runs before the device knows the outcome -- unlike torch's GradScaler, which does
     not call optimizer.step() on a skip.  A finite gradient whose sum of squares overflows fp32 is skipped
     too.  With ranks or accumulated micro-batches every rank tests the same summed arena: one decision.
-    False (default): the paths above, unchanged."""
+    False (default): the paths above, unchanged.
+
+    ema_decay: keep an exponential moving average of the parameters, `opt.ema` (a WeightEMA; ema_warmup is
+    its warm-up flag).  The update kernel of whichever path above is replaced by gnot_adamw_step_ema, which
+    computes the same parameters and moments bit for bit and moves the average in the same pass; the weight
+    w_t of step t is a ninth hyper-parameter `prepare()` writes, so `launch()` stays capturable.  A step the
+    guard skips leaves the average alone.  None (default): no average, the kernels and the 8-float hyper
+    above."""
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, schedule=None,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True):
+        self.ema = None if ema_decay is None else WeightEMA(flat, ema_decay, ema_warmup)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
         self.grad_norm = self.skipped_steps = self.last_skipped = None
@@ -230,10 +305,11 @@ class FlatAdamW:
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.schedule = schedule
         self.t = 0
-        self.hyper = torch.zeros(8, dtype=torch.float32, device=flat.device)
+        nh = 8 if self.ema is None else 9          # hyper[8]: the EMA weight of the step
+        self.hyper = torch.zeros(nh, dtype=torch.float32, device=flat.device)
         # pinned staging ring: the host may run steps ahead of the GPU; a slot is rewritten only
         # after the copy that last read it has executed (its event)
-        self._ring = [torch.zeros(8, dtype=torch.float32).pin_memory() for _ in range(4)]
+        self._ring = [torch.zeros(nh, dtype=torch.float32).pin_memory() for _ in range(4)]
         self._ev = [None] * 4
 
     def prepare(self):
@@ -247,6 +323,8 @@ class FlatAdamW:
         h = self._ring[k]
         for i, val in enumerate((lr, b1, b2, self.eps, self.wd, 1 - b1 ** self.t, 1 - b2 ** self.t, 1.0)):
             h[i] = val
+        if self.ema is not None:
+            h[8] = self.ema.weight(self.t)
         self.hyper.copy_(h, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -254,10 +332,25 @@ class FlatAdamW:
 
     def launch(self, grad):
         """The update kernel only -- with max_grad_norm, the two norm kernels and the clipped update; with
-        skip_nonfinite, the two norm kernels and the guarded update (graph-capturable every way)."""
+        skip_nonfinite, the two norm kernels and the guarded update (graph-capturable every way).  With
+        ema_decay the update is gnot_adamw_step_ema in each case, behind the same norm kernels."""
         if grad.numel() != self.flat.numel():
             raise ValueError("gradient buffer does not match the parameter arena")
         s = ctypes.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
+        if self.ema is not None:
+            lib = _lib.load()
+            if self.max_grad_norm is not None:
+                _lib.check(lib.gnot_grad_clip(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
+                                              self.max_grad_norm, self._clip_work.data_ptr(), self._clip.data_ptr(), s))
+            elif self.skip_nonfinite:
+                _lib.check(lib.gnot_grad_norm(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
+                                              self._clip_work.data_ptr(), self._clip.data_ptr(), s))
+            clip = self._clip.data_ptr() if self.grad_norm is not None else None
+            guard = self._guard.data_ptr() if self.skip_nonfinite else None
+            _lib.check(lib.gnot_adamw_step_ema(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
+                                               self.v.data_ptr(), self.ema.ema.data_ptr(), self.flat.numel(),
+                                               self.hyper.data_ptr(), clip, guard, s))
+            return
         if self.skip_nonfinite:
             lib = _lib.load()
             if self.max_grad_norm is not None:
@@ -287,11 +380,15 @@ class FlatAdamW:
 
     def state_dict(self):
         """Copies of exp_avg / exp_avg_sq, the step count, the skipped count (a device read when
-        skip_nonfinite is on) and the scalar hyper-parameters.  The parameters themselves are the model's."""
-        return {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "t": self.t,
-                "skipped": int(self.skipped_steps) if self.skip_nonfinite else 0, "numel": self.flat.numel(),
-                "lr": self.lr, "beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps,
-                "weight_decay": self.wd, "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
+        skip_nonfinite is on), the scalar hyper-parameters and, with ema_decay, the average ("ema": WeightEMA's
+        state).  The parameters themselves are the model's."""
+        state = {"exp_avg": self.m.detach().clone(), "exp_avg_sq": self.v.detach().clone(), "t": self.t,
+                 "skipped": int(self.skipped_steps) if self.skip_nonfinite else 0, "numel": self.flat.numel(),
+                 "lr": self.lr, "beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps,
+                 "weight_decay": self.wd, "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
+        if self.ema is not None:
+            state["ema"] = self.ema.state_dict()       # only with ema_decay: the keys above are the rest
+        return state
 
     def load_state_dict(self, state):
         """Continue from state_dict()'s values: moments, step count, skipped count, lr / betas / eps /
@@ -301,6 +398,12 @@ class FlatAdamW:
                 or state["exp_avg_sq"].numel() != self.flat.numel():
             raise ValueError(f"FlatAdamW.load_state_dict: the stored state has numel {int(state['numel'])}, "
                              f"this arena {self.flat.numel()}")
+        if (self.ema is not None) != (state.get("ema") is not None):
+            raise ValueError("FlatAdamW.load_state_dict: the stored state "
+                             + ("holds no weight average (ema_decay is set here)" if self.ema is not None
+                                else "holds a weight average (ema_decay is not set here)"))
+        if self.ema is not None:
+            self.ema.load_state_dict(state["ema"])
         self.m.copy_(state["exp_avg"].reshape(-1))
         self.v.copy_(state["exp_avg_sq"].reshape(-1))
         self.t = int(state["t"])
@@ -355,15 +458,20 @@ def restore_rng_state(state, train_loader=None):
         gen.set_state(state["loader"])
 
 
-def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, hist_test, args, train_loader=None):
+def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, hist_test, args, train_loader=None,
+                        ema_args=None):
     """Everything fit needs to continue a run bit for bit, in one torch.save of tensors (on the host) and plain
     Python values, readable with weights_only=True: the model state_dict (reference keys), the optimizer's
     and the schedule's state_dict(), the next epoch, the best metric, both histories, the host random state
-    (rng_state) and the trajectory arguments `args` (TRAJECTORY_ARGS).  Written under a temporary name in
+    (rng_state) and the trajectory arguments `args` (TRAJECTORY_ARGS); with a weight average also `ema_args`
+    (fit's ema_decay / ema_warmup; the average itself travels in the optimizer's state, the model entry holds
+    the raw weights).  Written under a temporary name in
     the same directory and moved into place with os.replace: a kill in mid-write leaves the previous file."""
     state = {"model": _cpu(model.state_dict()), "optimizer": _cpu(opt.state_dict()), "schedule": sched.state_dict(),
              "next_epoch": int(next_epoch), "best": float(best), "hist_train": [float(v) for v in hist_train],
              "hist_test": [float(v) for v in hist_test], "rng": rng_state(train_loader), "args": dict(args)}
+    if ema_args is not None:
+        state["ema_args"] = dict(ema_args)
     tmp = f"{path}.tmp{os.getpid()}"
     try:
         torch.save(state, tmp)
@@ -462,7 +570,7 @@ def _accum_step(model, eng, opt, loss_fn, group, dev):
 
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
         log=print, loss_fn=None, max_grad_norm=None, accum_steps=1, skip_nonfinite=False, state_path=None,
-        resume=False):
+        resume=False, ema_decay=None, ema_warmup=True):
     """The reference training loop (main.py:50-153): AdamW(lr) + OneCycleLR(max_lr=lr, steps_per_epoch,
     epochs), RelL2 loss, per-epoch test metric and best checkpoint.  With per_epoch_schedule=True the
     schedule is stepped once per epoch, as main.py:106 does.  The loaders decide the batch form:
@@ -488,6 +596,13 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     bit for bit the uninterrupted run; if it does not exist, start from scratch, so one command line serves
     the first launch and every restart.  A file written under other trajectory arguments (TRAJECTORY_ARGS)
     is refused.
+    ema_decay: FlatAdamW's weight average (ema_warmup: WeightEMA's warm-up).  The per-epoch test metric and
+    the best checkpoint are computed on the averaged weights (`opt.ema.swapped()`); training itself -- the
+    train losses, the raw weights, the moments -- is bit for bit the run without it, and the average moves
+    once per optimizer step (with accum_steps, per group; with ranks every rank averages the same
+    parameters: no collective).  The state file keeps the raw weights, carries the average inside the
+    optimizer state and names the two arguments in its own entry, "ema_args"; resume refuses a file whose
+    entry differs from this call's, an absent one included.  None (default): raw weights throughout.
     Returns (train losses per epoch, test metrics per epoch), the resumed epochs included."""
     accum_steps = int(accum_steps)
     if accum_steps < 1:
@@ -500,6 +615,8 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                 per_epoch_schedule=bool(per_epoch_schedule),
                 max_grad_norm=None if max_grad_norm is None else float(max_grad_norm),
                 loss=type(loss_fn).__name__, skip_nonfinite=bool(skip_nonfinite))
+    # beside args, not in it: TRAJECTORY_ARGS is the raw trajectory, which the average does not touch
+    ema_args = None if ema_decay is None else dict(ema_decay=float(ema_decay), ema_warmup=bool(ema_warmup))
     state = None
     if resume and os.path.exists(state_path):
         state = load_training_state(state_path)
@@ -507,10 +624,16 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             if state["args"].get(k) != args[k]:
                 raise ValueError(f"fit(resume=True): {state_path} was written with {k}={state['args'].get(k)!r}, "
                                  f"this call has {k}={args[k]!r}")
+        stored = state.get("ema_args") or {}
+        for k in ("ema_decay", "ema_warmup"):
+            if stored.get(k) != (ema_args or {}).get(k):
+                raise ValueError(f"fit(resume=True): {state_path} was written with {k}={stored.get(k)!r}, "
+                                 f"this call has {k}={(ema_args or {}).get(k)!r}")
         model.load_state_dict(state["model"])       # before the parameters move into the flat arena
     flat = flatten_parameters(model)
     sched = OneCycle(lr, epochs, steps_per_epoch)
-    opt = FlatAdamW(flat, lr=lr, schedule=sched, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    opt = FlatAdamW(flat, lr=lr, schedule=sched, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                    ema_decay=ema_decay, ema_warmup=ema_warmup)
     dev = flat.device
     prev_arena = model._grad_arena
     if accum_steps > 1:
@@ -555,15 +678,17 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                     log(f"Epoch {epoch}, Skipped steps: {total - skipped} (non-finite gradient norm)")
                 skipped = total
             if test_loader is not None:
-                res = evaluate(model, test_loader, metric)
-                hist_test.append(res)
-                log(f"Epoch {epoch}, Test Metric: {res}")
-                if res < best and checkpoint:
-                    best = res
-                    save_checkpoint(model, checkpoint)
-            if state_path:
+                # with ema_decay the metric and the checkpoint see the averaged weights
+                with opt.ema.swapped() if opt.ema is not None else contextlib.nullcontext():
+                    res = evaluate(model, test_loader, metric)
+                    hist_test.append(res)
+                    log(f"Epoch {epoch}, Test Metric: {res}")
+                    if res < best and checkpoint:
+                        best = res
+                        save_checkpoint(model, checkpoint)
+            if state_path:       # outside the swap: the raw weights, the average inside the optimizer state
                 save_training_state(state_path, model, opt, sched, epoch + 1, best, hist_train, hist_test, args,
-                                    train_loader)
+                                    train_loader, ema_args)
     finally:
         eng.param_grads = prev       # ordinary autograd use after fit() gets .grad again
         if accum_steps > 1:

@@ -294,6 +294,26 @@ int gnot_grad_norm(const float* grad, int64_t n, const float* hyper, float* work
 int gnot_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                             const float* hyper, const float* clip, int32_t* guard, void* stream);
 
+/* An exponential moving average of the parameters over flat fp32 arrays of n >= 1 elements, a pass of its
+ * own: ema[i] = fmaf(w, param[i] - ema[i], ema[i]) with the difference rounded first, w = weight[0] =
+ * 1 - decay of this step, read from DEVICE memory when the kernel runs (a captured graph picks up each
+ * replay's value).  `param` is only read; ema must not be the same array as param (GNOT_E_INVALID). */
+int gnot_ema_update(float* ema, const float* param, int64_t n, const float* weight, void* stream);
+
+/* One AdamW step with gnot_ema_update fused in: every element's average follows the parameter value the step
+ * just stored, in the same kernel.  hyper: DEVICE array of 9 floats, the 8 of gnot_adamw_step, then w.
+ *   clip == NULL, guard == NULL: param / exp_avg / exp_avg_sq as gnot_adamw_step leaves them, bit for bit
+ *                                (for a hyper[7] of 1 or any power of two, as for gnot_adamw_step_clipped);
+ *   clip != NULL, guard == NULL: as gnot_adamw_step_clipped;
+ *   clip != NULL, guard != NULL: as gnot_adamw_step_guarded -- on a NaN or infinite clip[0] no element of
+ *                                param, exp_avg, exp_avg_sq or ema is written, only guard;
+ *   a guard without a clip is refused (GNOT_E_INVALID).
+ * In every form ema ends as gnot_ema_update(ema, param, n, &hyper[8]) after that entry would leave it, bit
+ * for bit.  n >= 1; ema must not be the same array as param.  One kernel launch, stream-ordered, nothing read
+ * back: capturable.  The 8-float hyper of the other entries is unchanged. */
+int gnot_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                        const float* hyper, const float* clip, int32_t* guard, void* stream);
+
 /* Live kernel timing for the bench's roofline: while enabled, every launch of kernel class `kind`
  * ("moe_fwd" fused expert chains forward, "moe_bwd" their backward, "wgrad" weight-gradient GEMMs;
  * "" disables) is bracketed by hipEvents on its stream.  gnot_profile_read synchronizes on those

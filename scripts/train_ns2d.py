@@ -53,6 +53,11 @@ def main():
                     help="write the whole training state here after every epoch (default: off)")
     ap.add_argument("--resume", action="store_true",
                     help="continue the run stored in --state if that file exists, else start from scratch")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
+                    help="keep an exponential moving average of the weights with this decay (e.g. 0.999) and "
+                         "evaluate and checkpoint it instead of the raw weights (default: off)")
+    ap.add_argument("--no-ema-warmup", action="store_true",
+                    help="use --ema-decay from the first step on (default: min(decay, (1 + t) / (10 + t)) at step t)")
     args = ap.parse_args()
     if args.synthetic:
         rng = np.random.default_rng(0)
@@ -72,7 +77,8 @@ def main():
                         per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint,
                         loss_fn=train.MSELoss() if args.loss == "mse" else train.RelL2Loss(),
                         max_grad_norm=args.grad_clip, accum_steps=args.accum_steps,
-                        skip_nonfinite=args.skip_nonfinite, state_path=args.state, resume=args.resume)
+                        skip_nonfinite=args.skip_nonfinite, state_path=args.state, resume=args.resume,
+                        ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
     print(f"\nBest Test Metric: {min(test)}")
 
 
