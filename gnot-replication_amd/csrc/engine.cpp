@@ -2451,6 +2451,23 @@ extern "C" int gnot_debug_buffer(const gnot_plan* p, const char* name, float** p
 }
 
 // ====================================================================== training step
+// packed offsets of a loss entry: off[0] = 0, non-decreasing; allow_empty: a sample may have no rows
+static int check_loss_offsets(const std::vector<long>& off, bool allow_empty) {
+  if (off[0] != 0) return fail(GNOT_E_INVALID, "off[0] must be 0");
+  for (size_t b = 0; b + 1 < off.size(); ++b) {
+    if (off[b + 1] < off[b]) return fail(GNOT_E_INVALID, "offsets must be non-decreasing");
+    if (!allow_empty && off[b + 1] == off[b])
+      return fail(GNOT_E_INVALID, "empty sample: its mean over points is undefined");
+  }
+  return GNOT_OK;
+}
+
+// the arrays every AdamW entry takes
+static bool adamw_pointers(const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq,
+                           const float* hyper) {
+  return param && grad && exp_avg && exp_avg_sq && hyper;
+}
+
 extern "C" size_t gnot_rel_l2_work_floats(const int64_t* off_host, int B, int C) {
   if (!off_host || B <= 0 || C <= 0) return 0;
   std::vector<long> off(off_host, off_host + B + 1);
@@ -2462,9 +2479,7 @@ extern "C" int gnot_rel_l2_loss(const float* pred, const float* tgt, const int64
   if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
     return fail(GNOT_E_INVALID, "bad rel_l2 arguments");
   std::vector<long> off(off_host, off_host + B + 1);
-  if (off[0] != 0) return fail(GNOT_E_INVALID, "off[0] must be 0");
-  for (int b = 0; b < B; ++b)
-    if (off[b + 1] < off[b]) return fail(GNOT_E_INVALID, "offsets must be non-decreasing");
+  if (int rc = check_loss_offsets(off, true)) return rc;
   GNOT_CK(launch_rel_l2(pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B),
                         off[B], work, loss, dpred, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
@@ -2472,8 +2487,10 @@ extern "C" int gnot_rel_l2_loss(const float* pred, const float* tgt, const int64
 
 extern "C" int gnot_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                const float* hyper, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || !hyper) return fail(GNOT_E_INVALID, "bad adamw arguments");
-  GNOT_CK(launch_adamw(param, grad, exp_avg, exp_avg_sq, n, hyper, static_cast<hipStream_t>(stream)));
+  if (!adamw_pointers(param, grad, exp_avg, exp_avg_sq, hyper) || n < 0)
+    return fail(GNOT_E_INVALID, "bad adamw arguments");
+  GNOT_CK(launch_adamw_update(param, grad, exp_avg, exp_avg_sq, nullptr, n, hyper, nullptr, nullptr,
+                              static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 
@@ -2488,11 +2505,7 @@ extern "C" int gnot_mse_loss(const float* pred, const float* tgt, const int64_t*
   if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
     return fail(GNOT_E_INVALID, "bad mse arguments");
   std::vector<long> off(off_host, off_host + B + 1);
-  if (off[0] != 0) return fail(GNOT_E_INVALID, "off[0] must be 0");
-  for (int b = 0; b < B; ++b) {
-    if (off[b + 1] < off[b]) return fail(GNOT_E_INVALID, "offsets must be non-decreasing");
-    if (off[b + 1] == off[b]) return fail(GNOT_E_INVALID, "empty sample: its mean over points is undefined");
-  }
+  if (int rc = check_loss_offsets(off, false)) return rc;
   GNOT_CK(launch_mse(pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
                      work, loss, dpred, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
@@ -2513,9 +2526,10 @@ extern "C" int gnot_grad_clip(const float* grad, int64_t n, const float* hyper, 
 
 extern "C" int gnot_adamw_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                        const float* hyper, const float* clip, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || !hyper || !clip)
+  if (!adamw_pointers(param, grad, exp_avg, exp_avg_sq, hyper) || n < 0 || !clip)
     return fail(GNOT_E_INVALID, "bad adamw arguments");
-  GNOT_CK(launch_adamw_clipped(param, grad, exp_avg, exp_avg_sq, n, hyper, clip, static_cast<hipStream_t>(stream)));
+  GNOT_CK(launch_adamw_update(param, grad, exp_avg, exp_avg_sq, nullptr, n, hyper, clip, nullptr,
+                              static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 
@@ -2528,10 +2542,10 @@ extern "C" int gnot_grad_norm(const float* grad, int64_t n, const float* hyper, 
 
 extern "C" int gnot_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                        const float* hyper, const float* clip, int32_t* guard, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 1 || !hyper || !clip || !guard)
+  if (!adamw_pointers(param, grad, exp_avg, exp_avg_sq, hyper) || n < 1 || !clip || !guard)
     return fail(GNOT_E_INVALID, "bad guarded adamw arguments");
-  GNOT_CK(launch_adamw_guarded(param, grad, exp_avg, exp_avg_sq, n, hyper, clip, guard,
-                               static_cast<hipStream_t>(stream)));
+  GNOT_CK(launch_adamw_update(param, grad, exp_avg, exp_avg_sq, nullptr, n, hyper, clip, guard,
+                              static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 
@@ -2544,12 +2558,12 @@ extern "C" int gnot_ema_update(float* ema, const float* param, int64_t n, const 
 
 extern "C" int gnot_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
                                    int64_t n, const float* hyper, const float* clip, int32_t* guard, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || !ema || n < 1 || !hyper)
+  if (!adamw_pointers(param, grad, exp_avg, exp_avg_sq, hyper) || !ema || n < 1)
     return fail(GNOT_E_INVALID, "bad ema adamw arguments");
   if (guard && !clip) return fail(GNOT_E_INVALID, "adamw_step_ema: a guard needs a clip");
   if (ema == param) return fail(GNOT_E_INVALID, "adamw_step_ema: ema must not alias param");
-  GNOT_CK(launch_adamw_ema(param, grad, exp_avg, exp_avg_sq, ema, n, hyper, clip, guard,
-                           static_cast<hipStream_t>(stream)));
+  GNOT_CK(launch_adamw_update(param, grad, exp_avg, exp_avg_sq, ema, n, hyper, clip, guard,
+                              static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

@@ -294,8 +294,6 @@ int rel_l2_splits(const long* off_host, int B);
 // work: B*nsplit*2C + B*C floats
 hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
                          long rows, float* work, float* loss, float* dpred, hipStream_t s);
-hipError_t launch_adamw(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
-                        hipStream_t s);
 // work: B*nsplit*C floats (nsplit = rel_l2_splits); every sample must have at least one row
 hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
                       float* work, float* loss, float* dpred, hipStream_t s);
@@ -306,17 +304,13 @@ hipError_t launch_grad_clip(const float* grad, long n, const float* hyper, float
                             hipStream_t s);
 // the same two stages without a max_norm: clip = {norm (launch_grad_clip's bits), 1.0f}
 hipError_t launch_grad_norm(const float* grad, long n, const float* hyper, float* work, float* clip, hipStream_t s);
-hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
-                                const float* clip, hipStream_t s);
-// launch_adamw_clipped unless clip[0] is NaN or +-inf: then nothing but guard (2 ints {skipped count, skipped
-// now}) is written.  n >= 1.
-hipError_t launch_adamw_guarded(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
-                                const float* clip, int* guard, hipStream_t s);
 // ema = fma(weight[0], param - ema, ema); n >= 1, ema and param distinct arrays
 hipError_t launch_ema_update(float* ema, const float* param, long n, const float* weight, hipStream_t s);
-// the plain (clip == nullptr), clipped or guarded (guard != nullptr, needs clip) update with launch_ema_update's
-// pass on the stored parameter fused in; hyper: 9 floats, hyper[8] the EMA weight.  n >= 1.
-hipError_t launch_adamw_ema(float* param, const float* grad, float* m, float* v, float* ema, long n,
-                            const float* hyper, const float* clip, int* guard, hipStream_t s);
+// AdamW on the gradient (grad[i] * hyper[7]) * clip[1], every variant in one kernel.  clip == nullptr: no
+// coefficient (the plain update).  guard != nullptr (needs clip, n >= 1): nothing but guard (2 ints {skipped
+// count, skipped now}) is written when clip[0] is NaN or +-inf.  ema != nullptr: launch_ema_update's pass on the
+// stored parameter fused in; hyper then has 9 floats, hyper[8] the EMA weight.  n <= 0 launches nothing.
+hipError_t launch_adamw_update(float* param, const float* grad, float* m, float* v, float* ema, long n,
+                               const float* hyper, const float* clip, int* guard, hipStream_t s);
 
 }  // namespace gnot

@@ -11,12 +11,13 @@
 //   mse_*     MSELoss (reference loss.py:4-12): per-sample means of (p - t)^2 (dgl AvgPooling), in the
 //             shape of the rel_l2 passes.
 //   grad_clip global L2 norm of the flat gradient and torch.nn.utils.clip_grad_norm_'s coefficient, on
-//             the device (two fixed-order stages), consumed by adamw_clipped_kernel.
+//             the device (two fixed-order stages), consumed by the update through its clip argument.
 //   guarded   the clipped update behind a device-side test of that norm: a NaN or infinite norm leaves
-//             the parameters and both moments untouched and counts the skipped step (adamw_guarded_kernel).
+//             the parameters and both moments untouched and counts the skipped step (the guard argument).
 //   ema       an exponential moving average of the parameters, ema += w (param - ema), as one more stream of
-//             the update kernels (adamw_ema_kernel: plain, clipped or guarded) or as a pass of its own
+//             the update (adamw_update_kernel<true>: plain, clipped or guarded) or as a pass of its own
 //             (ema_update_kernel); w comes from device memory like the other hyper-parameters.
+// adamw, its clipped and guarded forms and the fused average are one kernel, adamw_update_kernel<kEma>.
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
@@ -24,12 +25,39 @@ namespace gnot {
 
 constexpr int kLossRows = 2048;   // rows per partial-sum workgroup
 
+// The sum of x over the workgroup's 256 threads, to every thread: a binary tree through red (256 floats of
+// shared memory), always in the same order.  red is free again on return.
+__device__ __forceinline__ float block_sum(float x, float* red) {
+  red[threadIdx.x] = x;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float sum = red[0];
+  __syncthreads();
+  return sum;
+}
+
+// the sample b of packed row r: off[b] <= r < off[b + 1], for 0 <= r < off[B]
+__device__ __forceinline__ int sample_of_row(const long* __restrict__ off, int B, long r) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= r) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the grid of an elementwise grid-stride kernel over n >= 1 elements, 256 threads a workgroup
+static unsigned flat_grid(long n) { return (unsigned)std::min<long>((n + 255) / 256, 2048); }
+
 // partial[b][split][0..2C) = (sum (p-t)^2 [C], sum t^2 [C]) over the split's rows of sample b
 __global__ void __launch_bounds__(256) rel_l2_partial_kernel(const float* __restrict__ pred,
                                                              const float* __restrict__ tgt,
                                                              const long* __restrict__ off, int C, int nsplit,
                                                              float* __restrict__ partial) {
-  __shared__ float red[256 * 2];
+  __shared__ float red[256];
   const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
   const long r0 = off[b] + (long)split * kLossRows;
   const long r1 = min(off[b + 1], r0 + kLossRows);
@@ -41,22 +69,13 @@ __global__ void __launch_bounds__(256) rel_l2_partial_kernel(const float* __rest
       num = fmaf(d, d, num);
       den = fmaf(t, t, den);
     }
-    red[threadIdx.x] = num;
-    red[256 + threadIdx.x] = den;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < s) {
-        red[threadIdx.x] += red[threadIdx.x + s];
-        red[256 + threadIdx.x] += red[256 + threadIdx.x + s];
-      }
-      __syncthreads();
-    }
+    num = block_sum(num, red);
+    den = block_sum(den, red);
     if (threadIdx.x == 0) {
       float* P = partial + ((long)b * nsplit + split) * 2 * C;
-      P[c] = red[0];
-      P[C + c] = red[256];
+      P[c] = num;
+      P[C + c] = den;
     }
-    __syncthreads();
   }
 }
 
@@ -79,13 +98,8 @@ __global__ void __launch_bounds__(256) rel_l2_finish_kernel(const float* __restr
     acc += r;
     scale[i] = 1.0f / ((float)(B * C) * den * r);
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *loss = red[0] / (float)(B * C);
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) *loss = acc / (float)(B * C);
 }
 
 __global__ void __launch_bounds__(256) rel_l2_grad_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
@@ -96,12 +110,7 @@ __global__ void __launch_bounds__(256) rel_l2_grad_kernel(const float* __restric
   if (i >= rows * C) return;
   const long r = i / C;
   const int c = (int)(i % C);
-  int lo = 0, hi = B - 1;                           // sample of row r
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  dpred[i] = (pred[i] - tgt[i]) * scale[lo * C + c];
+  dpred[i] = (pred[i] - tgt[i]) * scale[sample_of_row(off, B, r) * C + c];
 }
 
 int rel_l2_splits(const long* off_host, int B) {
@@ -139,14 +148,8 @@ __global__ void __launch_bounds__(256) mse_partial_kernel(const float* __restric
       const float d = pred[r * C + c] - tgt[r * C + c];
       num = fmaf(d, d, num);
     }
-    red[threadIdx.x] = num;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[((long)b * nsplit + split) * C + c] = red[0];
-    __syncthreads();
+    num = block_sum(num, red);
+    if (threadIdx.x == 0) partial[((long)b * nsplit + split) * C + c] = num;
   }
 }
 
@@ -162,13 +165,8 @@ __global__ void __launch_bounds__(256) mse_finish_kernel(const float* __restrict
     for (int s = 0; s < nsplit; ++s) num += partial[((long)b * nsplit + s) * C + c];
     acc += num / (float)(off[b + 1] - off[b]);
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *loss = red[0] / (float)(B * C);
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) *loss = acc / (float)(B * C);
 }
 
 // d loss / d pred = 2 (p - t) / (B C N_b)
@@ -177,13 +175,8 @@ __global__ void __launch_bounds__(256) mse_grad_kernel(const float* __restrict__
                                                        float* __restrict__ dpred, long rows) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= rows * C) return;
-  const long r = i / C;
-  int lo = 0, hi = B - 1;                           // sample of row r
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= r) lo = mid; else hi = mid - 1;
-  }
-  dpred[i] = (pred[i] - tgt[i]) * (2.0f / ((float)(B * C) * (float)(off[lo + 1] - off[lo])));
+  const int b = sample_of_row(off, B, i / C);
+  dpred[i] = (pred[i] - tgt[i]) * (2.0f / ((float)(B * C) * (float)(off[b + 1] - off[b])));
 }
 
 // work: B*nsplit*C floats
@@ -234,13 +227,8 @@ __global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict
     const float g = p[head + 4 * body4 + threadIdx.x];
     a1 = fmaf(g, g, a1);
   }
-  red[threadIdx.x] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  const float sum = block_sum((a0 + a1) + (a2 + a3), red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // clip[0] = |grad_scale| sqrt(sum g^2), the norm of the gradient AdamW consumes (hyper[7] scales it);
@@ -252,14 +240,9 @@ __global__ void __launch_bounds__(256) grad_clip_finish_kernel(const float* __re
   __shared__ float red[256];
   float acc = 0.f;
   for (long i = threadIdx.x; i < nparts; i += 256) acc += partial[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  acc = block_sum(acc, red);
   if (threadIdx.x == 0) {
-    const float norm = fabsf(hyper[7]) * sqrtf(red[0]);
+    const float norm = fabsf(hyper[7]) * sqrtf(acc);
     const float c = max_norm / (norm + 1e-6f);
     clip[0] = norm;
     clip[1] = (norm_only || c > 1.0f) ? 1.0f : c;
@@ -286,66 +269,57 @@ hipError_t launch_grad_norm(const float* grad, long n, const float* hyper, float
 }
 
 // ---------------------------------------------------------------- AdamW over a flat arena
-// hyper = {lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, grad_scale}
-__global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ param, const float* __restrict__ grad,
-                                                    float* __restrict__ m, float* __restrict__ v, long n,
-                                                    const float* __restrict__ hyper) {
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
-  const float bc1 = hyper[5], bc2 = hyper[6], gs = hyper[7];
-  const float step_size = lr / bc1;
-  const float bc2_sqrt = sqrtf(bc2);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const float g = grad[i] * gs;
-    float p = param[i] * (1.0f - lr * wd);              // decoupled weight decay
-    float mi = m[i];
-    mi = mi + (1.0f - b1) * (g - mi);                   // exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = v[i] * b2 + (1.0f - b2) * g * g;   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p = p - step_size * (mi / denom);                   // param.addcdiv_(exp_avg, denom, -step_size)
-    param[i] = p;
-    m[i] = mi;
-    v[i] = vi;
-  }
-}
-
-hipError_t launch_adamw(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
-                        hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  const long blocks = std::min<long>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper);
-  return hipGetLastError();
-}
-
-// adamw_kernel on the clipped gradient (grad[i] * grad_scale) * coef over this thread's grid-stride elements: the
-// body of adamw_clipped_kernel and adamw_guarded_kernel.  Everything after g is adamw_kernel's operation
-// order: a coefficient of 1.0f gives its bits whenever grad[i] * grad_scale is exact (a grad_scale of 1, which
-// FlatAdamW writes, or any power of two).
-// kEma: the element's average follows the parameter value just stored, ema = fma(w, p - ema, ema) with
-// w = hyper[8] -- ema_update_kernel's expression on the same operands, so fused and stand-alone agree bit for
-// bit; param / m / v are computed exactly as without it.
+// hyper = {lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, grad_scale[, ema weight]}
+//
+// One kernel for every update: torch's AdamW on the gradient (grad[i] * grad_scale) * coef.
+//   clip   what launch_grad_clip / launch_grad_norm wrote, read from device memory so a captured graph applies
+//          the coefficient of the step it replays; nullptr: no coefficient (the plain update).
+//   guard  the non-finite guard (needs clip): every thread reads the norm clip[0] -- one value for the whole
+//          grid, so the decision is uniform -- and on a NaN or +-inf (exponent bits all ones) no element of
+//          param / m / v / ema is written.  guard = {skipped launches since the caller zeroed it, 1 if this
+//          launch skipped else 0}, written by thread 0 of workgroup 0 alone; launches on one stream are
+//          ordered, so the count needs no atomic.  nullptr: no test.
+//   kEma   the element's average follows the parameter value just stored, ema = fma(w, p - ema, ema) with
+//          w = hyper[8] -- ema_update_kernel's expression on the same operands, so fused and stand-alone agree
+//          bit for bit; param / m / v are computed exactly as without it.
+// The multiply-adds are written out and no others are allowed (which ones a compiler fuses depends on the code
+// around them): they are the fusions the first, plain-only form of this kernel was compiled with, in torch's
+// operation order.  A coefficient of 1.0f multiplies exactly, so every variant computes the same exp_avg_sq,
+// denominator and parameter from the same scaled gradient.
 template <bool kEma>
-__device__ __forceinline__ void adamw_clipped_elements(float* __restrict__ param, const float* __restrict__ grad,
-                                                       float* __restrict__ m, float* __restrict__ v,
-                                                       float* __restrict__ ema, long n,
-                                                       const float* __restrict__ hyper, float coef) {
-  // Which multiply-adds of adamw_kernel's expressions the compiler fuses depends on the code around them
-  // (the extra multiply here moved one), so the fusions it applies there are written out and no others
-  // are allowed: exp_avg_sq = fma(g, (1 - beta2) g, beta2 v), the rest as the expressions read.
+__global__ void __launch_bounds__(256) adamw_update_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           float* __restrict__ ema, long n,
+                                                           const float* __restrict__ hyper,
+                                                           const float* __restrict__ clip, int* __restrict__ guard) {
 #pragma clang fp contract(off)
+  if (guard) {
+    const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (!finite) guard[0] = guard[0] + 1;
+      guard[1] = finite ? 0 : 1;
+    }
+    if (!finite) return;
+  }
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
   const float bc1 = hyper[5], bc2 = hyper[6], gs = hyper[7];
   const float step_size = lr / bc1;
   const float bc2_sqrt = sqrtf(bc2);
-  const float decay = fmaf(-lr, wd, 1.0f);
+  const float decay = fmaf(-lr, wd, 1.0f);               // decoupled weight decay
+  const float coef = clip ? clip[1] : 1.0f;
   const float w = kEma ? hyper[8] : 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float gi = grad[i] * gs;
     const float g = gi * coef;
     float mi = m[i];
-    mi = fmaf(1.0f - b1, fmaf(gi, coef, -mi), mi);       // exp_avg.lerp_(grad, 1 - beta1)
+    // g - exp_avg: the plain update without the average was first compiled with the scaling fused into the
+    // subtraction (grad[i] * grad_scale not rounded), every other variant multiplies the rounded gi by the
+    // coefficient.  The two differ when grad_scale is not a power of two; each entry keeps its own bits.
+    const float inner = (kEma || clip) ? fmaf(gi, coef, -mi) : fmaf(grad[i], gs, -mi);
+    mi = fmaf(1.0f - b1, inner, mi);                        // exp_avg.lerp_(grad, 1 - beta1)
     const float vi = fmaf(g, (1.0f - b2) * g, v[i] * b2);   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float p = fmaf(decay, param[i], -(step_size * (mi / denom)));
+    const float p = fmaf(decay, param[i], -(step_size * (mi / denom)));   // param.addcdiv_(exp_avg, denom, -step_size)
     param[i] = p;
     m[i] = mi;
     v[i] = vi;
@@ -356,52 +330,23 @@ __device__ __forceinline__ void adamw_clipped_elements(float* __restrict__ param
   }
 }
 
-// clip is what launch_grad_clip wrote, read from device memory so a captured graph applies the coefficient of
-// the step it replays.
-__global__ void __launch_bounds__(256) adamw_clipped_kernel(float* __restrict__ param, const float* __restrict__ grad,
-                                                            float* __restrict__ m, float* __restrict__ v, long n,
-                                                            const float* __restrict__ hyper,
-                                                            const float* __restrict__ clip) {
-  adamw_clipped_elements<false>(param, grad, m, v, nullptr, n, hyper, clip[1]);
-}
-
-hipError_t launch_adamw_clipped(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
-                                const float* clip, hipStream_t s) {
+// ema == nullptr: no average (hyper has 8 floats), else hyper has 9.  n >= 1 when there is a guard (the grid's
+// first thread writes it); n <= 0 launches nothing.
+hipError_t launch_adamw_update(float* param, const float* grad, float* m, float* v, float* ema, long n,
+                               const float* hyper, const float* clip, int* guard, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  const long blocks = std::min<long>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(adamw_clipped_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper, clip);
-  return hipGetLastError();
-}
-
-// adamw_clipped_kernel behind the non-finite guard: every thread reads the norm clip[0] (one value for the
-// whole grid, so the decision is uniform); NaN or +-inf (exponent bits all ones) -> no element of param / m / v
-// is written.  guard = {skipped launches since the caller zeroed it, 1 if this launch skipped else 0}, written
-// by thread 0 of workgroup 0 alone; launches on one stream are ordered, so the count needs no atomic.
-__global__ void __launch_bounds__(256) adamw_guarded_kernel(float* __restrict__ param, const float* __restrict__ grad,
-                                                            float* __restrict__ m, float* __restrict__ v, long n,
-                                                            const float* __restrict__ hyper,
-                                                            const float* __restrict__ clip, int* __restrict__ guard) {
-  const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (!finite) guard[0] = guard[0] + 1;
-    guard[1] = finite ? 0 : 1;
-  }
-  if (!finite) return;
-  adamw_clipped_elements<false>(param, grad, m, v, nullptr, n, hyper, clip[1]);
-}
-
-// n >= 1 (the guard is written by the grid's first thread); the grid of launch_adamw
-hipError_t launch_adamw_guarded(float* param, const float* grad, float* m, float* v, long n, const float* hyper,
-                                const float* clip, int* guard, hipStream_t s) {
-  const long blocks = std::min<long>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(adamw_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, n, hyper, clip,
-                     guard);
+  if (ema)
+    hipLaunchKernelGGL(adamw_update_kernel<true>, dim3(flat_grid(n)), dim3(256), 0, s, param, grad, m, v, ema, n, hyper,
+                       clip, guard);
+  else
+    hipLaunchKernelGGL(adamw_update_kernel<false>, dim3(flat_grid(n)), dim3(256), 0, s, param, grad, m, v, ema, n,
+                       hyper, clip, guard);
   return hipGetLastError();
 }
 
 // ---------------------------------------------------------------- weight EMA
 // ema = fma(w, param - ema, ema) over n elements, w = weight[0] from device memory (a captured graph picks up
-// each step's value).  The subtraction is rounded on its own: the expression of adamw_clipped_elements<true>.
+// each step's value).  The subtraction is rounded on its own: the expression of adamw_update_kernel<true>.
 __global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ ema, const float* __restrict__ param,
                                                          long n, const float* __restrict__ weight) {
 #pragma clang fp contract(off)
@@ -412,39 +357,11 @@ __global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ ema
   }
 }
 
-// n >= 1; the grid of launch_adamw
+// n >= 1
 hipError_t launch_ema_update(float* ema, const float* param, long n, const float* weight, hipStream_t s) {
-  const long blocks = std::min<long>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ema, param, n, weight);
-  return hipGetLastError();
-}
-
-// The three updates with the average as a fifth stream, one kernel: clip == nullptr is the plain update (the
-// clipped body with a coefficient of 1.0f, adamw_kernel's bits), guard != nullptr (needs clip) puts
-// adamw_guarded_kernel's test in front -- a skipped step writes no element of ema either.  hyper has 9 floats.
-__global__ void __launch_bounds__(256) adamw_ema_kernel(float* __restrict__ param, const float* __restrict__ grad,
-                                                        float* __restrict__ m, float* __restrict__ v,
-                                                        float* __restrict__ ema, long n,
-                                                        const float* __restrict__ hyper,
-                                                        const float* __restrict__ clip, int* __restrict__ guard) {
-  if (guard) {
-    const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      if (!finite) guard[0] = guard[0] + 1;
-      guard[1] = finite ? 0 : 1;
-    }
-    if (!finite) return;
-  }
-  adamw_clipped_elements<true>(param, grad, m, v, ema, n, hyper, clip ? clip[1] : 1.0f);
-}
-
-// n >= 1; the grid of launch_adamw
-hipError_t launch_adamw_ema(float* param, const float* grad, float* m, float* v, float* ema, long n,
-                            const float* hyper, const float* clip, int* guard, hipStream_t s) {
-  const long blocks = std::min<long>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, grad, m, v, ema, n, hyper, clip,
-                     guard);
+  hipLaunchKernelGGL(ema_update_kernel, dim3(flat_grid(n)), dim3(256), 0, s, ema, param, n, weight);
   return hipGetLastError();
 }
 
 }  // namespace gnot
+

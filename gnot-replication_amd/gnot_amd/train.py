@@ -36,55 +36,34 @@ from . import _lib
 
 
 # ------------------------------------------------------------------ loss (loss.py:14-23)
-class _RelL2(torch.autograd.Function):
+class _NativeLoss(torch.autograd.Function):
+    """loss and d loss / d pred in one pass of the native entry `entry` (gnot_rel_l2_loss or gnot_mse_loss)"""
+
     @staticmethod
-    def forward(ctx, pred, tgt, off_dev, off_host, work):
-        lib = _lib.load()
+    def forward(ctx, pred, tgt, off_dev, off_host, work, entry):
         B = len(off_host) - 1
         C = pred.shape[1]
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
         dpred = torch.empty_like(pred) if pred.requires_grad else None
         oh = (ctypes.c_int64 * (B + 1))(*off_host)
         s = ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-        _lib.check(lib.gnot_rel_l2_loss(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, C,
-                                        work.data_ptr(), loss.data_ptr(),
-                                        dpred.data_ptr() if dpred is not None else None, s))
+        _lib.check(getattr(_lib.load(), entry)(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, C,
+                                               work.data_ptr(), loss.data_ptr(),
+                                               dpred.data_ptr() if dpred is not None else None, s))
         ctx.save_for_backward(dpred) if dpred is not None else None
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
-        return dpred * g, None, None, None, None
-
-
-class _MSE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, tgt, off_dev, off_host, work):
-        lib = _lib.load()
-        B = len(off_host) - 1
-        C = pred.shape[1]
-        loss = torch.empty((), device=pred.device, dtype=torch.float32)
-        dpred = torch.empty_like(pred) if pred.requires_grad else None
-        oh = (ctypes.c_int64 * (B + 1))(*off_host)
-        s = ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-        _lib.check(lib.gnot_mse_loss(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, C,
-                                     work.data_ptr(), loss.data_ptr(),
-                                     dpred.data_ptr() if dpred is not None else None, s))
-        ctx.save_for_backward(dpred) if dpred is not None else None
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dpred,) = ctx.saved_tensors
-        return dpred * g, None, None, None, None
+        return dpred * g, None, None, None, None, None
 
 
 class RelL2Loss(torch.nn.Module):
     """mean over (sample, channel) of sqrt(sum_n (p - t)^2 / sum_n t^2) (reference loss.py:14-23).
     The dgl graph argument of the reference becomes the packed offsets x_off [B+1] (host list)."""
 
-    _fn, _work_floats = _RelL2, "gnot_rel_l2_work_floats"
+    _entry, _work_floats = "gnot_rel_l2_loss", "gnot_rel_l2_work_floats"
 
     def __init__(self):
         super().__init__()
@@ -104,7 +83,8 @@ class RelL2Loss(torch.nn.Module):
             self._cache = {key: (pinned.to(predictions.device, non_blocking=True),
                                  torch.empty(n, dtype=torch.float32, device=predictions.device), pinned)}
         off_dev, work, _ = self._cache[key]
-        return self._fn.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0], work)
+        return _NativeLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0], work,
+                                 self._entry)
 
 
 class MSELoss(RelL2Loss):
@@ -113,7 +93,7 @@ class MSELoss(RelL2Loss):
     the loss and d loss/d pred.  Not torch.nn.MSELoss: every sample weighs the same whatever its size.
     A sample without points is refused (its mean is undefined)."""
 
-    _fn, _work_floats = _MSE, "gnot_mse_work_floats"
+    _entry, _work_floats = "gnot_mse_loss", "gnot_mse_work_floats"
 
 
 # ------------------------------------------------------------------ OneCycleLR (main.py:52)
@@ -337,42 +317,29 @@ class FlatAdamW:
         if grad.numel() != self.flat.numel():
             raise ValueError("gradient buffer does not match the parameter arena")
         s = ctypes.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
-        if self.ema is not None:
-            lib = _lib.load()
+        lib, n, hyper = _lib.load(), self.flat.numel(), self.hyper.data_ptr()
+        clip = guard = None
+        # at most one norm step ...
+        if self.grad_norm is not None:
+            clip = self._clip.data_ptr()
             if self.max_grad_norm is not None:
-                _lib.check(lib.gnot_grad_clip(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
-                                              self.max_grad_norm, self._clip_work.data_ptr(), self._clip.data_ptr(), s))
-            elif self.skip_nonfinite:
-                _lib.check(lib.gnot_grad_norm(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
-                                              self._clip_work.data_ptr(), self._clip.data_ptr(), s))
-            clip = self._clip.data_ptr() if self.grad_norm is not None else None
-            guard = self._guard.data_ptr() if self.skip_nonfinite else None
-            _lib.check(lib.gnot_adamw_step_ema(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
-                                               self.v.data_ptr(), self.ema.ema.data_ptr(), self.flat.numel(),
-                                               self.hyper.data_ptr(), clip, guard, s))
-            return
-        if self.skip_nonfinite:
-            lib = _lib.load()
-            if self.max_grad_norm is not None:
-                _lib.check(lib.gnot_grad_clip(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
-                                              self.max_grad_norm, self._clip_work.data_ptr(), self._clip.data_ptr(), s))
+                _lib.check(lib.gnot_grad_clip(grad.data_ptr(), n, hyper, self.max_grad_norm,
+                                              self._clip_work.data_ptr(), clip, s))
             else:
-                _lib.check(lib.gnot_grad_norm(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(),
-                                              self._clip_work.data_ptr(), self._clip.data_ptr(), s))
-            _lib.check(lib.gnot_adamw_step_guarded(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
-                                                   self.v.data_ptr(), self.flat.numel(), self.hyper.data_ptr(),
-                                                   self._clip.data_ptr(), self._guard.data_ptr(), s))
-            return
-        if self.max_grad_norm is not None:
-            lib = _lib.load()
-            _lib.check(lib.gnot_grad_clip(grad.data_ptr(), grad.numel(), self.hyper.data_ptr(), self.max_grad_norm,
-                                          self._clip_work.data_ptr(), self._clip.data_ptr(), s))
-            _lib.check(lib.gnot_adamw_step_clipped(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
-                                                   self.v.data_ptr(), self.flat.numel(), self.hyper.data_ptr(),
-                                                   self._clip.data_ptr(), s))
-            return
-        _lib.check(_lib.load().gnot_adamw_step(self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(),
-                                               self.v.data_ptr(), self.flat.numel(), self.hyper.data_ptr(), s))
+                _lib.check(lib.gnot_grad_norm(grad.data_ptr(), n, hyper, self._clip_work.data_ptr(), clip, s))
+        if self.skip_nonfinite:
+            guard = self._guard.data_ptr()
+        # ... then one update, through the entry of the options that are on
+        arrays = (self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr())
+        if self.ema is not None:
+            rc = lib.gnot_adamw_step_ema(*arrays, self.ema.ema.data_ptr(), n, hyper, clip, guard, s)
+        elif guard is not None:
+            rc = lib.gnot_adamw_step_guarded(*arrays, n, hyper, clip, guard, s)
+        elif clip is not None:
+            rc = lib.gnot_adamw_step_clipped(*arrays, n, hyper, clip, s)
+        else:
+            rc = lib.gnot_adamw_step(*arrays, n, hyper, s)
+        _lib.check(rc)
 
     def step(self, grad):
         self.prepare()

@@ -4,10 +4,14 @@
     GNOT_LIB=<a.so> python scripts/diag_bitwise_ab.py dump gpurun_out/a.npz
     GNOT_LIB=<b.so> python scripts/diag_bitwise_ab.py dump gpurun_out/b.npz
     python scripts/diag_bitwise_ab.py compare gpurun_out/a.npz gpurun_out/b.npz
+    GNOT_LIB=<a.so> python scripts/diag_bitwise_ab.py record tests/golden/train_step_bits.npz
 
 Each case runs one training forward + backward (sum(out * G)) and stores the output and the flat gradient
 arena: d = 256 / E = 8 (configs[2]'s widths) in fp32, bf16 mode and with MoE recompute, d = 128 / E = 4 /
-two input functions (configs[1]'s) in fp32 and bf16 mode, and d = 64 (chain.hip).
+two input functions (configs[1]'s) in fp32 and bf16 mode, and d = 64 (chain.hip).  Then the training step
+(tests/train_step_util.py step_replay): every AdamW entry, both norm entries and both losses at n = 1, 257, 8195
+and 524291.  `record` writes the inputs and results of the first three sizes as the fixture of
+tests/test_gpu_train_bits.py.
 """
 import os
 import sys
@@ -15,7 +19,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "gnot-replication_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "gnot-replication_amd"), os.path.join(ROOT, "tests")]
 
 CASES = [
     # name, (input, theta, fn, out, L, d, nl, E, H, I), P, precision, recompute
@@ -50,21 +54,33 @@ def dump(path):
         res[name + ".out"] = out.detach().cpu().numpy()
         res[name + ".grad"] = m.engine().grad_flat.detach().cpu().numpy()
         print(name, "done", flush=True)
+    import train_step_util as U
+    res.update({"step." + k: v for k, v in U.step_replay(U.step_inputs(U.NS)).items()})
     np.savez(path, **res)
+
+
+def record(path):
+    import train_step_util as U
+    inp = U.step_inputs(U.NS[:3])
+    out = U.step_replay(inp)
+    np.savez(path, **{"in." + k: v for k, v in inp.items()}, **{"out." + k: v for k, v in out.items()})
 
 
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     bad = 0
+    assert sorted(A.files) == sorted(B.files)
     for k in A.files:
-        same = np.array_equal(A[k], B[k])
-        print(f"{k:24s} {'bitwise equal' if same else 'DIFFERS max %.3e' % np.abs(A[k] - B[k]).max()}")
+        same = A[k].tobytes() == B[k].tobytes()      # bits: a NaN equals itself
+        if not same or not k.startswith("step."):
+            print(f"{k:24s} {'bitwise equal' if same else 'DIFFERS in %d elements' % (A[k] != B[k]).sum()}")
         bad += not same
+    print(f"{len(A.files)} arrays, {bad} differ")
     sys.exit(1 if bad else 0)
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "dump":
-        dump(sys.argv[2])
+    if sys.argv[1] in ("dump", "record"):
+        {"dump": dump, "record": record}[sys.argv[1]](sys.argv[2])
     else:
         compare(sys.argv[2], sys.argv[3])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-step timeline of a rocprofv3 kernel trace: the last `adamw_kernel` delimits steps.
+"""Per-step timeline of a rocprofv3 kernel trace: the last `adamw_update_kernel` delimits steps.
     python scripts/trace_step.py run_kernel_trace.csv [step index from the end, default 1]"""
 import collections
 import csv
@@ -7,7 +7,7 @@ import sys
 
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 back = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-ends = [i for i, r in enumerate(rows) if "adamw_kernel" in r["Kernel_Name"]]
+ends = [i for i, r in enumerate(rows) if "adamw_update_kernel" in r["Kernel_Name"]]
 lo, hi = ends[-back - 1] + 1, ends[-back] + 1
 step = rows[lo:hi]
 t0 = int(step[0]["Start_Timestamp"])

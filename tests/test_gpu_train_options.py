@@ -2,7 +2,6 @@
 gradient vs float64, the device-side global gradient norm / clip coefficient (gnot_grad_clip) vs float64,
 FlatAdamW(max_grad_norm=...) vs torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW, its hipGraph capture,
 train.fit with MSE and clipping vs a stock-torch replica, and the unclipped default left bit for bit."""
-import ctypes
 import os
 import sys
 
@@ -10,11 +9,12 @@ import numpy as np
 import pytest
 import torch
 
-from gnot_amd import _lib, train
+import train_step_util as U
+from gnot_amd import train
+from train_step_util import SMALL
 
 pytestmark = pytest.mark.gpu
 
-SMALL = (2, 1, 3, 1, 1, 32, 2, 32, 32, 2, 4, 1)      # the model of test_train.py / test_gpu_train_loop.py
 TCFG = dict(n_mlp_num_layers=2, n_expert=2, n_head=4, n_attn_layers=1, n_input_functions=1)
 
 
@@ -54,20 +54,9 @@ def test_native_mse_loss_and_grad(sizes, C):
 
 # ------------------------------------------------------------------ norm and coefficient
 def _grad_clip(g, h7, max_norm):
-    """gnot_grad_clip on the device tensor g (any view); returns clip [2] on the host.  The work buffer
-    carries a guard element behind its declared size."""
-    lib = _lib.load()
-    n = g.numel()
-    nw = lib.gnot_grad_clip_work_floats(n)
-    work = torch.full((nw + 1,), -7.0, dtype=torch.float32, device=g.device)
-    hyper = torch.zeros(8, dtype=torch.float32, device=g.device)
-    hyper[7] = h7
-    clip = torch.full((3,), -7.0, dtype=torch.float32, device=g.device)
-    s = ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(lib.gnot_grad_clip(g.data_ptr(), n, hyper.data_ptr(), max_norm, work.data_ptr(), clip.data_ptr(), s))
-    out = clip.cpu()
-    assert float(work[nw]) == -7.0 and float(out[2]) == -7.0
-    return out[:2]
+    """gnot_grad_clip on the device tensor g (any view); returns clip [2] on the host (U.norm checks the
+    elements behind the declared sizes of work and clip)"""
+    return U.norm(g, U.hyper(h7), max_norm).cpu()
 
 
 def _check_clip(g, h7):
@@ -205,17 +194,6 @@ def test_coefficient_one_leaves_the_plain_step_bit_for_bit():
 
 
 # ------------------------------------------------------------------ fit with MSE and clipping
-def _loaders():
-    from gnot_amd import data
-    rng = np.random.default_rng(3)
-    mk_s = lambda k: [data.synthetic_sample(rng, int(rng.integers(40, 120)), fn_points=(int(rng.integers(10, 30)),))
-                      for _ in range(k)]
-    samples, test = mk_s(6), mk_s(4)
-    mk = lambda s: torch.utils.data.DataLoader(data.NS2dData(s), batch_size=2, shuffle=False,
-                                               collate_fn=data.collate_packed)
-    return mk(samples), mk(test)
-
-
 def _replica_out(torch_port, p, b, dev):
     """reference forward of one packed batch: one unpadded B=1 call per sample."""
     outs = []
@@ -267,7 +245,7 @@ def _replica(init, train_loader, test_loader, epochs, dev, max_norm):
 def test_fit_with_mse_and_clipping_matches_torch_reference():
     from gnot_amd import GNOT
     dev = torch.device("cuda")
-    train_loader, test_loader = _loaders()
+    train_loader, test_loader = U.batches(6)
     torch.manual_seed(0)
     model = GNOT(*SMALL).to(dev)
     init = {k: v.detach().clone() for k, v in model.state_dict().items()}

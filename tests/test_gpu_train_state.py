@@ -7,116 +7,31 @@ writes nothing but its guard on a NaN / +inf / -inf one, at n = 1 (one thread), 
 aligned gradient base and one a float off.  FlatAdamW(skip_nonfinite=True): one captured graph replayed on
 a NaN and on a finite gradient, and its state_dict.  train.fit: a run stopped in its second epoch and resumed
 on a fresh module equals the uninterrupted one, and a NaN batch is skipped."""
-import ctypes
 import math
 import os
 
-import numpy as np
 import pytest
 import torch
 
-from gnot_amd import _lib, train
+import train_step_util as U
+from gnot_amd import train
+from train_step_util import BAD, NS, bits
 
 pytestmark = pytest.mark.gpu
-
-SMALL = (2, 1, 3, 1, 1, 32, 2, 32, 32, 2, 4, 1)      # the model of test_train.py / test_gpu_train_loop.py
-NS = [1, 257, 8195, 524291]
-PAD = -7.0                                            # behind every array's declared size
-BAD = [float("nan"), float("inf"), float("-inf")]
-
-bits = lambda t: t.view(torch.int32)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _padded(src):
-    """src on the device with one PAD element behind it: (the view of src's size, the allocation)"""
-    buf = torch.full((src.numel() + 1,), PAD, dtype=torch.float32, device="cuda")
-    buf[:-1].copy_(src)
-    return buf[:-1], buf
-
-
-def _hyper(h7=1.0, t=3):
-    return torch.tensor([1e-3, 0.9, 0.999, 1e-8, 1e-2, 1 - 0.9 ** t, 1 - 0.999 ** t, h7], dtype=torch.float32).cuda()
-
-
-def _grad(n, offset, seed=0):
-    """a gradient of n elements whose base is `offset` floats behind a 16-byte boundary"""
-    buf = torch.full((n + offset + 3,), 1e30, dtype=torch.float32, device="cuda")     # a stray read wrecks the norm
-    assert buf.data_ptr() % 16 == 0
-    g = buf[offset:offset + n]
-    g.copy_(torch.randn(n, generator=torch.Generator().manual_seed(1000 * seed + n)))
-    assert g.data_ptr() % 16 == 4 * offset
-    return g
-
-
-def _norm(g, hyper, max_norm=None):
-    """clip [2] (device) of gnot_grad_clip (max_norm given) or gnot_grad_norm; nothing is written behind
-    the declared sizes of work and clip"""
-    lib, n = _lib.load(), g.numel()
-    nw = lib.gnot_grad_clip_work_floats(n)
-    work = torch.full((nw + 1,), PAD, dtype=torch.float32, device="cuda")
-    clip = torch.full((3,), PAD, dtype=torch.float32, device="cuda")
-    if max_norm is None:
-        _lib.check(lib.gnot_grad_norm(g.data_ptr(), n, hyper.data_ptr(), work.data_ptr(), clip.data_ptr(), _stream()))
-    else:
-        _lib.check(lib.gnot_grad_clip(g.data_ptr(), n, hyper.data_ptr(), max_norm, work.data_ptr(), clip.data_ptr(),
-                                      _stream()))
-    assert float(work[nw]) == PAD and float(clip[2]) == PAD
-    return clip[:2]
-
-
-class _Arrays:
-    """param / exp_avg / exp_avg_sq of n elements in the middle of a run, each with a PAD element behind it"""
-
-    def __init__(self, n):
-        gen = torch.Generator().manual_seed(n)
-        self.n = n
-        (self.p, self.pb), (self.m, self.mb), (self.v, self.vb) = (
-            _padded(torch.randn(n, generator=gen)), _padded(0.1 * torch.randn(n, generator=gen)),
-            _padded(0.01 * torch.rand(n, generator=gen)))
-
-    def copy(self):
-        c = _Arrays.__new__(_Arrays)
-        c.n = self.n
-        (c.p, c.pb), (c.m, c.mb), (c.v, c.vb) = _padded(self.p), _padded(self.m), _padded(self.v)
-        return c
-
-    def same(self, other):
-        return all(torch.equal(bits(a), bits(b)) for a, b in ((self.pb, other.pb), (self.mb, other.mb),
-                                                              (self.vb, other.vb)))
-
-    def step(self, g, hyper, clip=None, guard=None):
-        lib = _lib.load()
-        a = (self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.n, hyper.data_ptr())
-        if guard is not None:
-            _lib.check(lib.gnot_adamw_step_guarded(*a, clip.data_ptr(), guard.data_ptr(), _stream()))
-        elif clip is not None:
-            _lib.check(lib.gnot_adamw_step_clipped(*a, clip.data_ptr(), _stream()))
-        else:
-            _lib.check(lib.gnot_adamw_step(*a, _stream()))
-        assert float(self.pb[-1]) == PAD and float(self.mb[-1]) == PAD and float(self.vb[-1]) == PAD
-
-
-def _guard():
-    return torch.zeros(3, dtype=torch.int32, device="cuda")      # {skipped, skipped now} and an element behind
-
 
 # ------------------------------------------------------------------ the norm alone
 @pytest.mark.parametrize("offset", [0, 1])
 @pytest.mark.parametrize("n", NS)
 def test_grad_norm_carries_the_bits_of_grad_clip(n, offset):
-    g = _grad(n, offset)
+    g = U.grad(n, offset)
     for h7 in (1.0, 0.5):
-        hyper = _hyper(h7)
-        got = _norm(g, hyper).cpu()
+        hyper = U.hyper(h7)
+        got = U.norm(g, hyper).cpu()
         ref64 = abs(h7) * float(g.double().pow(2).sum().sqrt())
         assert abs(float(got[0]) - ref64) <= 1e-5 * ref64
         assert float(got[1]) == 1.0
         for max_norm in (0.5 * ref64, 2.0 * ref64):
-            ref = _norm(g, hyper, max_norm).cpu()
+            ref = U.norm(g, hyper, max_norm).cpu()
             assert torch.equal(bits(got[:1]), bits(ref[:1])), (n, offset, h7, float(got[0]), float(ref[0]))
 
 
@@ -124,14 +39,14 @@ def test_grad_norm_carries_the_bits_of_grad_clip(n, offset):
 @pytest.mark.parametrize("offset", [0, 1])
 @pytest.mark.parametrize("n", NS)
 def test_guarded_step_on_a_finite_gradient_is_the_unguarded_one(n, offset):
-    g, hyper, start = _grad(n, offset), _hyper(), _Arrays(n)
+    g, hyper, start = U.grad(n, offset), U.hyper(), U.Arrays(n)
     norm = float(g.double().pow(2).sum().sqrt())
     for max_norm, clipping in ((0.5 * norm, True), (2.0 * norm, False), (None, False)):
-        clip = _norm(g, hyper, max_norm)
+        clip = U.norm(g, hyper, max_norm)
         assert math.isfinite(float(clip[0])) and (float(clip[1]) < 1.0) == clipping
         if not clipping:
             assert float(clip[1]) == 1.0
-        ref, got, guard = start.copy(), start.copy(), _guard()
+        ref, got, guard = start.copy(), start.copy(), U.guard()
         if max_norm is None:
             ref.step(g, hyper)                         # behind gnot_grad_norm: the plain gnot_adamw_step
         else:
@@ -143,29 +58,23 @@ def test_guarded_step_on_a_finite_gradient_is_the_unguarded_one(n, offset):
 
 
 # ------------------------------------------------------------------ a non-finite gradient: nothing but the guard
-def _bad_index(n, where):
-    """first / last element; "tail": inside the 1 to 3 elements behind the last 16-byte load of an aligned
-    base (n % 4 of them); "head": inside the up to 3 elements in front of the first one of a base a float off"""
-    return {"first": 0, "last": n - 1, "tail": n - 1 - (n % 4) // 2, "head": min(1, n - 1)}[where]
-
-
 @pytest.mark.parametrize("where", ["first", "last", "tail", "head"])
 @pytest.mark.parametrize("n", NS)
 def test_guarded_step_skips_a_nonfinite_gradient(n, where):
-    g, hyper, start = _grad(n, 1 if where == "head" else 0), _hyper(), _Arrays(n)
+    g, hyper, start = U.grad(n, 1 if where == "head" else 0), U.hyper(), U.Arrays(n)
     good = g.clone()
     for k, bad in enumerate(BAD):
         g.copy_(good)
-        g[_bad_index(n, where)] = bad
+        g[U.bad_index(n, where)] = bad
         # the norm through either entry: max_norm / (inf + 1e-6) is a coefficient of 0, NaN stays NaN
-        clip = _norm(g, hyper, None if k % 2 == 0 else 1.0)
+        clip = U.norm(g, hyper, None if k % 2 == 0 else 1.0)
         assert not math.isfinite(float(clip[0])), (n, where, bad, float(clip[0]))
-        got, guard = start.copy(), _guard()
+        got, guard = start.copy(), U.guard()
         got.step(g, hyper, clip, guard)
         assert got.same(start), (n, where, bad)
         assert guard.tolist() == [1, 1, 0]
         # a following finite launch applies the update and keeps the count
-        clip = _norm(good, hyper)
+        clip = U.norm(good, hyper)
         ref = start.copy()
         ref.step(good, hyper, clip)
         got.step(good, hyper, clip, guard)
@@ -176,10 +85,10 @@ def test_guarded_step_skips_a_nonfinite_gradient(n, where):
 def test_a_finite_gradient_whose_squared_sum_overflows_is_skipped():
     n = 257
     g = torch.full((n,), 3e19, dtype=torch.float32, device="cuda")       # finite, but 257 * 9e38 > fp32 max
-    hyper, start = _hyper(), _Arrays(n)
-    clip = _norm(g, hyper)
+    hyper, start = U.hyper(), U.Arrays(n)
+    clip = U.norm(g, hyper)
     assert float(clip[0]) == float("inf")
-    got, guard = start.copy(), _guard()
+    got, guard = start.copy(), U.guard()
     got.step(g, hyper, clip, guard)
     assert got.same(start) and guard.tolist() == [1, 1, 0]
 
@@ -258,51 +167,10 @@ def test_flat_adamw_state_round_trips():
 
 
 # ------------------------------------------------------------------ fit
-class _Stop(Exception):
-    pass
-
-
-_BATCHES = None
-
-
-def _batches():
-    """list-of-batches loaders: four train and two test batches of two meshes of 40 to 120 points"""
-    global _BATCHES
-    if _BATCHES is None:
-        from gnot_amd import data
-        rng = np.random.default_rng(3)
-        mk_s = lambda k: [data.synthetic_sample(rng, int(rng.integers(40, 120)), fn_points=(int(rng.integers(10, 30)),))
-                          for _ in range(k)]
-        mk = lambda s: list(torch.utils.data.DataLoader(data.NS2dData(s), batch_size=2, shuffle=False,
-                                                        collate_fn=data.collate_packed))
-        _BATCHES = mk(mk_s(8)), mk(mk_s(4))
-    return _BATCHES
-
-
-def _model(seed=0):
-    from gnot_amd import GNOT
-    torch.manual_seed(seed)
-    return GNOT(*SMALL).cuda()
-
-
-def _flat_params(model):
-    return torch.cat([t.detach().reshape(-1) for l in model.linears() for t in (l.weight, l.bias)])
-
-
-def _first_grad_norm():
-    """the gradient norm of the first train batch at the initial weights (sizes max_grad_norm)"""
-    model, (tr, _) = _model(), _batches()
-    eng = model.engine()
-    eng.param_grads = False
-    pred, off, y = train._forward_batch(model, tr[0], torch.device("cuda"))
-    train.RelL2Loss()(off, pred, y).backward()
-    return float(eng.grad_flat.norm())
-
-
 def _uninterrupted(path, **kw):
-    model, (tr, te) = _model(), _batches()
+    model, (tr, te) = U.model(), U.batches()
     hist = train.fit(model, tr, te, epochs=4, state_path=path, log=lambda msg: None, **kw)
-    return hist, _flat_params(model).clone()
+    return hist, U.flat_params(model).clone()
 
 
 @pytest.fixture(scope="module")
@@ -313,23 +181,23 @@ def finished(tmp_path_factory):
 
 
 def _stopped_and_resumed(path, **kw):
-    tr, te = _batches()
+    tr, te = U.batches()
     lines = []
 
     def log(msg):
         lines.append(msg)
         if sum("Test Metric" in l for l in lines) == 2:
-            raise _Stop
+            raise U.Stop
 
-    with pytest.raises(_Stop):
-        train.fit(_model(), tr, te, epochs=4, state_path=path, log=log, **kw)
+    with pytest.raises(U.Stop):
+        train.fit(U.model(), tr, te, epochs=4, state_path=path, log=log, **kw)
     first = train.load_training_state(path)["next_epoch"]
     assert 1 <= first <= 2                                  # what was on disk when the run died
-    model = _model(seed=123)                                # a fresh module with other weights
+    model = U.model(seed=123)                                # a fresh module with other weights
     lines.clear()
     hist = train.fit(model, tr, te, epochs=4, state_path=path, resume=True, log=lines.append, **kw)
     assert lines[0].startswith(f"Epoch {first}, Loss") and len(lines) == 2 * (4 - first)
-    return hist, _flat_params(model).clone()
+    return hist, U.flat_params(model).clone()
 
 
 def _assert_same_run(p, q, ref, got):
@@ -354,42 +222,42 @@ def test_resumed_fit_is_the_uninterrupted_fit_bitwise(finished, tmp_path):
 
 
 def test_resumed_fit_with_accumulation_and_clipping_bitwise(tmp_path):
-    kw = dict(accum_steps=2, max_grad_norm=0.5 * _first_grad_norm())
+    kw = dict(accum_steps=2, max_grad_norm=0.5 * U.first_grad_norm())
     p, q = os.path.join(tmp_path, "p.pt"), os.path.join(tmp_path, "q.pt")
     _assert_same_run(p, q, _uninterrupted(p, **kw), _stopped_and_resumed(q, **kw))
 
 
 def test_resume_without_a_file_starts_from_scratch(finished, tmp_path):
     _, ref_hist, ref_flat = finished
-    model, (tr, te) = _model(), _batches()
+    model, (tr, te) = U.model(), U.batches()
     q = os.path.join(tmp_path, "none_yet.pt")
     hist = train.fit(model, tr, te, epochs=4, state_path=q, resume=True, log=lambda msg: None)
-    assert hist == ref_hist and torch.equal(bits(_flat_params(model)), bits(ref_flat))
+    assert hist == ref_hist and torch.equal(bits(U.flat_params(model)), bits(ref_flat))
     # ... and a finished run resumes to nothing left to do: the stored histories, the stored weights
-    again = _model(seed=5)
+    again = U.model(seed=5)
     assert train.fit(again, tr, te, epochs=4, state_path=q, resume=True, log=lambda msg: None) == ref_hist
-    assert torch.equal(bits(_flat_params(again)), bits(ref_flat))
+    assert torch.equal(bits(U.flat_params(again)), bits(ref_flat))
 
 
 def test_resume_refuses_another_trajectory(finished):
     p = finished[0]
-    tr, te = _batches()
+    tr, te = U.batches()
     with pytest.raises(ValueError, match="epochs"):
-        train.fit(_model(), tr, te, epochs=5, state_path=p, resume=True, log=lambda msg: None)
+        train.fit(U.model(), tr, te, epochs=5, state_path=p, resume=True, log=lambda msg: None)
     with pytest.raises(ValueError, match="accum_steps"):
-        train.fit(_model(), tr, te, epochs=4, accum_steps=2, state_path=p, resume=True, log=lambda msg: None)
+        train.fit(U.model(), tr, te, epochs=4, accum_steps=2, state_path=p, resume=True, log=lambda msg: None)
     with pytest.raises(ValueError, match="state_path"):
-        train.fit(_model(), tr, te, epochs=4, resume=True, log=lambda msg: None)
+        train.fit(U.model(), tr, te, epochs=4, resume=True, log=lambda msg: None)
 
 
 def test_fit_skips_a_nan_batch():
-    tr = [dict(b) for b in _batches()[0][:3]]
+    tr = [dict(b) for b in U.batches()[0][:3]]
     tr[1]["y"] = tr[1]["y"].clone()
     tr[1]["y"][5] = float("nan")
     dev = torch.device("cuda")
 
     # by hand over the public pieces: a step for batches 1 and 3, the step number alone for batch 2
-    ref = _model()
+    ref = U.model()
     flat = train.flatten_parameters(ref)
     sched = train.OneCycle(1e-3, 1, 3)
     opt = train.FlatAdamW(flat, lr=1e-3, schedule=sched)
@@ -408,14 +276,14 @@ def test_fit_skips_a_nan_batch():
     torch.cuda.synchronize()
     assert torch.isfinite(flat).all()
 
-    model, lines = _model(), []
+    model, lines = U.model(), []
     hist, _ = train.fit(model, tr, None, epochs=1, skip_nonfinite=True, log=lines.append)
-    assert torch.equal(bits(_flat_params(model)), bits(flat))
+    assert torch.equal(bits(U.flat_params(model)), bits(flat))
     assert hist == [sum(losses) / 2] and math.isfinite(hist[0])
     skipped = [l for l in lines if "Skipped steps" in l]
     assert len(skipped) == 1 and "Skipped steps: 1 " in skipped[0], lines
 
     # the test bites: without the flag the same loader ends with non-finite parameters
-    model = _model()
+    model = U.model()
     train.fit(model, tr, None, epochs=1, log=lambda msg: None)
-    assert not torch.isfinite(_flat_params(model)).all()
+    assert not torch.isfinite(U.flat_params(model)).all()
