@@ -2567,5 +2567,27 @@ extern "C" int gnot_adamw_step_ema(float* param, const float* grad, float* exp_a
   return GNOT_OK;
 }
 
+extern "C" int gnot_gather_rows(const float* src, int C, const int64_t* table_dev, const int64_t* table_host, int B,
+                                float* dst, void* stream) {
+  if (!src || !table_dev || !table_host || !dst) return fail(GNOT_E_INVALID, "gather_rows: null argument");
+  if (B < 1 || C < 1) return fail(GNOT_E_INVALID, "gather_rows: B and C must be at least 1");
+  long rows = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t* T = table_host + (long)b * kGatherCols;      // {src_row0, n, dst_row0, k, key_lo, key_hi}
+    if (T[0] < 0) return fail(GNOT_E_INVALID, "gather_rows: src_row0 must not be negative");
+    if (T[1] < 0 || T[1] >= (1L << 31)) return fail(GNOT_E_INVALID, "gather_rows: n must be in [0, 2^31)");
+    if (T[3] < 0 || T[3] > T[1]) return fail(GNOT_E_INVALID, "gather_rows: k must be in [0, n]");
+    if (T[4] < 0 || T[4] >= (1L << 32) || T[5] < 0 || T[5] >= (1L << 32))
+      return fail(GNOT_E_INVALID, "gather_rows: keys must be in [0, 2^32)");
+    if (T[2] != rows)
+      return fail(GNOT_E_INVALID, "gather_rows: dst_row0 must start at 0 and continue by k from segment to segment");
+    rows += T[3];
+  }
+  if (rows == 0) return GNOT_OK;
+  GNOT_CK(launch_gather_rows(src, C, reinterpret_cast<const long*>(table_dev), B, dst, rows,
+                             static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
 extern "C" const char* gnot_last_error(void) { return g_err.c_str(); }
 extern "C" const char* gnot_version(void) { return "gnot-mi355x 0.1 (gfx950, fp32 MFMA)"; }

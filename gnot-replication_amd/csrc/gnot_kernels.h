@@ -313,4 +313,13 @@ hipError_t launch_ema_update(float* ema, const float* param, long n, const float
 hipError_t launch_adamw_update(float* param, const float* grad, float* m, float* v, float* ema, long n,
                                const float* hyper, const float* clip, int* guard, hipStream_t s);
 
+
+// ------------------------------------------------------------------ batch assembly (gather.hip)
+// table: one row of kGatherCols longs per segment {src_row0, n, dst_row0, k, key_lo, key_hi}; dst row
+// dst_row0 + j = src row src_row0 + j (k == n) or src_row0 + pi(j; n, key) (k < n), 0 <= j < k.
+// rows = sum of k >= 1; the table is validated by the caller (gnot_gather_rows)
+constexpr int kGatherCols = 6;
+hipError_t launch_gather_rows(const float* src, int C, const long* table, int B, float* dst, long rows,
+                              hipStream_t s);
+
 }  // namespace gnot

@@ -477,16 +477,23 @@ def _forward_batch(model, batch, dev):
     return model.forward_packed(x, x_off, theta, fns, fn_offs), x_off, y
 
 
+def _read_back(losses):
+    """the 0-d device losses of many steps as Python floats (each exactly float(loss)): one device read"""
+    return torch.stack(losses).tolist() if losses else []
+
+
 def evaluate(model, loader, loss_fn=None):
     """main.py:108-147: mean RelL2 over the test batches, no_grad (no activations kept).  Batches from
-    collate_padded reproduce main.py's padded evaluation; collate_packed batches the unpadded one."""
+    collate_padded reproduce main.py's padded evaluation; collate_packed batches the unpadded one.
+    The batch losses stay on the device and are read once, behind the last batch."""
     loss_fn = loss_fn or RelL2Loss()
     dev = next(model.parameters()).device
     vals = []
     with torch.no_grad():
         for batch in loader:
             pred, off, y = _forward_batch(model, batch, dev)
-            vals.append(float(loss_fn(off, pred, y)))
+            vals.append(loss_fn(off, pred, y))
+    vals = _read_back(vals)
     return sum(vals) / max(len(vals), 1)
 
 
@@ -521,7 +528,9 @@ def _grouped(loader, k):
 
 
 def _accum_step(model, eng, opt, loss_fn, group, dev):
-    """One optimizer step on a group of micro-batches (fit's accum_steps): returns sum_i (B_i / sum B) loss_i."""
+    """One optimizer step on a group of micro-batches (fit's accum_steps): returns the micro-batches' losses
+    (0-d device tensors, nothing read back) and their weights B_i / sum B; the step's loss is
+    sum_i (B_i / sum B) loss_i."""
     _, (weights,) = accum_groups([_batch_samples(b) for b in group], len(group))
     vals = []
     for i, (batch, w) in enumerate(zip(group, weights)):
@@ -532,7 +541,7 @@ def _accum_step(model, eng, opt, loss_fn, group, dev):
             (loss * w).backward()
         vals.append(loss.detach())
     opt.step(eng.grad_flat)          # the clip (max_grad_norm) and AdamW read the accumulated arena once
-    return sum(float(l) * w for l, w in zip(vals, weights))
+    return vals, weights
 
 
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
@@ -570,6 +579,10 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     parameters: no collective).  The state file keeps the raw weights, carries the average inside the
     optimizer state and names the two arguments in its own entry, "ema_args"; resume refuses a file whose
     entry differs from this call's, an absent one included.  None (default): raw weights throughout.
+    No step reads its loss back: every step's 0-d loss (with accum_steps, every micro-batch's) stays on the
+    device and the epoch reads them all at its end, then does the host arithmetic above on those fp32 values;
+    with a loader whose batches are on the device already (data.DeviceLoader) the host runs ahead of the GPU
+    through a whole epoch.
     Returns (train losses per epoch, test metrics per epoch), the resumed epochs included."""
     accum_steps = int(accum_steps)
     if accum_steps < 1:
@@ -627,12 +640,16 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                     opt.step(eng.grad_flat)
                     if not per_epoch_schedule:
                         sched.step()
-                    losses.append(float(loss))
+                    losses.append(loss.detach())
+                losses = _read_back(losses)
             else:
+                steps = []
                 for group in _grouped(train_loader, accum_steps):
-                    losses.append(_accum_step(model, eng, opt, loss_fn, group, dev))
+                    steps.append(_accum_step(model, eng, opt, loss_fn, group, dev))
                     if not per_epoch_schedule:
                         sched.step()
+                vals = iter(_read_back([l for ls, _ in steps for l in ls]))
+                losses = [sum(next(vals) * w for w in weights) for _, weights in steps]
             if per_epoch_schedule:
                 sched.step()
             if skip_nonfinite:

@@ -314,6 +314,29 @@ int gnot_ema_update(float* ema, const float* param, int64_t n, const float* weig
 int gnot_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                         const float* hyper, const float* clip, int32_t* guard, void* stream);
 
+/* Batch assembly from a dataset that lives in device memory (no reference counterpart: main.py:57-58 batches
+ * on the host).  src [rows, C] and dst [sum k, C] are fp32; the table has one row of six int64 per segment b,
+ * {src_row0, n, dst_row0, k, key_lo, key_hi} (table_dev on the device, table_host the same on the host, for
+ * validation before the launch).  For 0 <= j < k the kernel copies row src_row0 + sigma(j) of src to row
+ * dst_row0 + j of dst:
+ *   k == n: sigma(j) = j, the segment whole and in its own order;
+ *   k <  n: sigma(j) = pi(j; n, key_lo, key_hi), the first k values of a keyed permutation of [0, n): a uniform
+ *           subsample without replacement, a pure function of (key, n) -- no device random state.
+ * pi is a cycle-walking Feistel permutation, all arithmetic uint32 (mod 2^32):
+ *   fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *   n <= 1: pi(0) = 0.  n >= 2: bits = bit_length(n - 1), h = (bits + 1) / 2, mask = 2^h - 1
+ *   rk_r = fmix32(key_lo ^ (r * 0x9E3779B9)) + key_hi, r = 0..5
+ *   E(x): L = x >> h, R = x & mask; for r = 0..5: (L, R) = (R, L ^ (fmix32(R ^ rk_r) & mask)); (L << h) | R
+ *   pi(j) = the first of E(j), E(E(j)), ... that is < n
+ * The same table with another C gathers a second array's corresponding rows (x and y of a mesh); segments of
+ * n = k = 1 gather single rows (theta).  GNOT_E_INVALID before any launch for: null pointers; B < 1 or C < 1;
+ * src_row0 < 0, n < 0, n >= 2^31, k < 0 or k > n; a key outside [0, 2^32); dst_row0[0] != 0 or
+ * dst_row0[b+1] != dst_row0[b] + k[b].  That src holds src_row0 + n rows and dst sum k rows is the caller's to
+ * ensure.  sum k == 0 launches nothing.  One kernel launch whatever B is; stateless, stream-ordered, no
+ * allocation. */
+int gnot_gather_rows(const float* src, int C, const int64_t* table_dev, const int64_t* table_host, int B, float* dst,
+                     void* stream);
+
 /* Live kernel timing for the bench's roofline: while enabled, every launch of kernel class `kind`
  * ("moe_fwd" fused expert chains forward, "moe_bwd" their backward, "wgrad" weight-gradient GEMMs;
  * "" disables) is bracketed by hipEvents on its stream.  gnot_profile_read synchronizes on those

@@ -3,6 +3,8 @@
 main.py:15-23, batch 4, AdamW lr 1e-3, OneCycleLR stepped per epoch, RelL2 metric, best checkpoint)
 with plain tensors instead of dgl graphs.  Batches are zero-padded exactly like main.py:60-89 by
 default (the pad rows enter the attention sums, as in the reference); --packed uses packed offsets.
+--device-data keeps the datasets in device memory and gathers the packed batches there; --points-per-mesh K
+trains on K randomly chosen points of every mesh per step.
 
     python scripts/train_ns2d.py --train train.pkl --test test.pkl [--epochs 100 ...]
     python scripts/train_ns2d.py --synthetic 64 --epochs 2          # generated meshes, same format
@@ -58,7 +60,15 @@ def main():
                          "evaluate and checkpoint it instead of the raw weights (default: off)")
     ap.add_argument("--no-ema-warmup", action="store_true",
                     help="use --ema-decay from the first step on (default: min(decay, (1 + t) / (10 + t)) at step t)")
+    ap.add_argument("--device-data", action="store_true",
+                    help="keep both datasets in device memory and assemble the (packed) batches there "
+                         "(data.DeviceLoader; implies --packed)")
+    ap.add_argument("--points-per-mesh", type=int, default=None, metavar="K",
+                    help="train on a fresh uniform subsample of K points of every mesh per step (meshes of fewer "
+                         "points whole); input functions stay whole and the test set is evaluated at full "
+                         "resolution (implies --device-data)")
     args = ap.parse_args()
+    args.device_data = args.device_data or args.points_per_mesh is not None
     if args.synthetic:
         rng = np.random.default_rng(0)
         tr = data.NS2dData([data.synthetic_sample(rng, int(rng.integers(1000, 4000))) for _ in range(args.synthetic)])
@@ -73,7 +83,13 @@ def main():
     dl = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=args.batch, shuffle=sh,
                                                     collate_fn=data.collate_packed if args.packed
                                                     else data.collate_padded)
-    _, test = train.fit(model, dl(tr, True), dl(te, False), epochs=args.epochs,
+    if args.device_data:       # the test set stays at full resolution
+        loaders = (data.DeviceLoader(data.DeviceDataset(tr, dev), args.batch, shuffle=True,
+                                     points_per_mesh=args.points_per_mesh),
+                   data.DeviceLoader(data.DeviceDataset(te, dev), args.batch))
+    else:
+        loaders = dl(tr, True), dl(te, False)
+    _, test = train.fit(model, *loaders, epochs=args.epochs,
                         per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint,
                         loss_fn=train.MSELoss() if args.loss == "mse" else train.RelL2Loss(),
                         max_grad_norm=args.grad_clip, accum_steps=args.accum_steps,
