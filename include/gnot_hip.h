@@ -77,6 +77,11 @@ int gnot_plan_bind_params(gnot_plan* plan, const float* const* weights, const fl
  * x_off[b] .. x_off[b+1]-1); fn_off: host array [n_input_functions * (B+1)] of the same for every
  * input function.  A zero-padded batch (main.py:60-82) is simply x_off = {0, N, 2N, ...}.
  * training != 0 keeps the activations the backward needs.
+ * A sample may have no query points, and an input-function segment no points, as long as the batch has
+ * a query point: an empty sample contributes no output rows, a zero d theta row and zero d fn rows
+ * (tests/test_gpu_geometry.py).  A sample that HAS query points but an input function with no points is
+ * not supported: the reference divides by a zero key sum there (model.py LinearAttention, 1 / (q . sum k))
+ * and returns NaN, so the case has no reference and is untested.
  * Limits: fewer than 2^29 points per plan (query points, and points of each input function: the
  * kernels' job tables hold 32-bit point indices; their buffer resources are based per workgroup or per
  * split-K range, so no activation array size bounds a plan).  GNOT_E_INVALID beyond it; the real bound

@@ -109,6 +109,10 @@ def _rank(rank, world, port, cfg, Ns, Ms, q, backend="gloo", fx=None, env=None):
     (3, dict(cfg=dict(input_dim=2, theta_dim=1, input_func_dim=3, out_dim=1, n_attn_layers=1, d=32,
                       n_mlp_num_layers=2, n_expert=2, n_head=8, n_input_functions=2),
              Ns=[64, 5], Ms=[[20, 9], [7, 12]])),
+    # a 2-point sample over 3 ranks: rank 0's slice of it is empty (floor(2 / 3) = 0)
+    (3, dict(cfg=dict(input_dim=2, theta_dim=1, input_func_dim=3, out_dim=1, n_attn_layers=1, d=32,
+                      n_mlp_num_layers=2, n_expert=2, n_head=8, n_input_functions=1),
+             Ns=[70, 2], Ms=[[20, 9]])),
 ])
 def test_point_sharded_gnot_matches_oracle(world, case):
     _run_sharded_case(world, case)

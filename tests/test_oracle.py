@@ -75,3 +75,61 @@ def test_torch_port_matches_fixtures(name):
     errs = check_parity(np.concatenate(outs), grads, fx, rtol=1e-9, slack=0.0)
     errs = [e for e in errs if not any(t in e for t in ("key", "query"))]
     assert not errs, errs
+
+
+def _split(fx):
+    B = len(fx["x_off"]) - 1
+    cut = lambda a, o: [a[o[b]:o[b + 1]] for b in range(B)]
+    fns_ps = [[f[o[b]:o[b + 1]] for f, o in zip(fx["fns"], fx["fn_offs"])] for b in range(B)]
+    return cut(fx["x"], fx["x_off"]), list(fx["theta"]), fns_ps, cut(fx["G"], fx["x_off"])
+
+
+def test_port_reference_matches_fixture():
+    """golden_util.port_reference (the per-sample float64 reference of tests/test_gpu_geometry.py: one B = 1
+    port call per sample, parameter gradients summed over the samples) reproduces the reference's packed
+    fixture: output rows per sample and every parameter gradient."""
+    from golden_util import port_reference
+    fx = load("cross2_packed")
+    samples, grads, e32 = port_reference(fx["cfg"], fx["params"], *_split(fx))
+    out = np.concatenate([s["out"] for s in samples])
+    errs = check_parity(out, grads, fx, rtol=1e-9, slack=0.0)
+    errs = [e for e in errs if not any(t in e for t in ("key", "query"))]
+    assert not errs, errs
+    assert [s["N"] for s in samples] == np.diff(fx["x_off"]).tolist()
+    assert all(0 < e32[k] < 1e-3 * max(np.linalg.norm(grads[k]), 1e-6) for k in grads)
+
+
+def test_per_sample_rule_sees_what_the_whole_batch_norm_misses():
+    """check_parity_per_sample on the geometry suite's `empties` batch (Ns = [65, 0, 1, 0, 128]): the
+    reference itself passes; 0.05 % of error confined to the 1-point sample passes the whole-batch rule and
+    fails the per-sample one, naming the sample and the row; an error in one sample's dtheta row or a NaN in
+    a dfns segment fails; the empty samples' reference rows are exact zeros."""
+    from golden_util import check_parity_per_sample
+    from test_gpu_geometry import _case
+    fx = _case("A", "empties")
+    S = fx["samples"]
+
+    def got():
+        return dict(out=fx["out"].copy(), grads=fx["grads"], dx=np.concatenate([s["dx"] for s in S]),
+                    dtheta=np.stack([s["dtheta"] for s in S]),
+                    dfns=[np.concatenate([s["dfns"][i] for s in S]) for i in range(len(fx["fns"]))])
+
+    assert not check_parity_per_sample(got(), fx)
+    assert [s["N"] for s in S] == [65, 0, 1, 0, 128]
+    for b in (1, 3):
+        assert not S[b]["dtheta"].any() and not any(f.any() for f in S[b]["dfns"])
+    g = got()
+    g["out"][65] *= 1.0005                      # the 1-point sample's only row
+    assert not check_parity(g["out"], g["grads"], fx)
+    errs = check_parity_per_sample(g, fx)
+    assert errs and all("sample 2 (N=1, M=[1, 1])" in e for e in errs) and "worst row 0 of 1" in errs[0], errs
+    g = got()
+    g["out"][66 + 127] *= 1.002                 # the last row of the last sample's last (full) chunk
+    errs = check_parity_per_sample(g, fx)
+    assert any("worst row 127 of 128 (point 63 of a 64-point chunk 1)" in e for e in errs), errs
+    g = got()
+    g["dtheta"][0] *= 1.001
+    assert any("sample 0" in e and "dtheta" in e for e in check_parity_per_sample(g, fx))
+    g = got()
+    g["dfns"][1][0] = np.nan
+    assert any("dfn1" in e for e in check_parity_per_sample(g, fx))
