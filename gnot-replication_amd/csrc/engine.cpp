@@ -2589,5 +2589,11 @@ extern "C" int gnot_gather_rows(const float* src, int C, const int64_t* table_de
   return GNOT_OK;
 }
 
+extern "C" int gnot_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, int64_t n, void* stream) {
+  if (!x || !y || !dy || !y2 || !dy2 || n < 1) return fail(GNOT_E_INVALID, "bad debug_gelu arguments");
+  GNOT_CK(launch_debug_gelu(x, y, dy, y2, dy2, n, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
 extern "C" const char* gnot_last_error(void) { return g_err.c_str(); }
 extern "C" const char* gnot_version(void) { return "gnot-mi355x 0.1 (gfx950, fp32 MFMA)"; }

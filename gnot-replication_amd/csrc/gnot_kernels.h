@@ -280,6 +280,8 @@ hipError_t launch_add_cols(const float* a, long lda, const float* b, long ldb, i
 // out[b][t] = sum over rows [off[b], off[b+1]) of a[row][c0 + t], t < ncols (fixed order)
 hipError_t launch_seg_colsum(const float* a, long lda, int c0, int ncols, const long* off, int B, float* out,
                              hipStream_t s);
+// test hook: y = gelu(x), dy = gelu_grad(x), (y2, dy2) = gelu_and_grad(x) over n contiguous floats
+hipError_t launch_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, long n, hipStream_t s);
 // segmented copy: dst[seg.dst + i] = src[seg.src + i], i < seg.len (floats); reverse swaps the roles of
 // src/dst offsets.  unit 4: every offset and length a multiple of 4 (float4 copies), unit 1: any.  prefix:
 // prefix sums of the lengths in units [nseg + 1], total = prefix[nseg].

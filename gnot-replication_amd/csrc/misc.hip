@@ -8,6 +8,8 @@
 //   input grads  : d x = d x_in[:, :in] + d x_gate (x feeds the encoder through cat and the gating MLP,
 //                  model.py:155, 158-161), d theta[b] = sum over sample b's points of d x_in[:, in:]
 //                  (the broadcast of model.py:158), d fn = the encoder chain's input gradient
+#include <algorithm>
+
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
@@ -177,6 +179,28 @@ hipError_t launch_seg_colsum(const float* a, long lda, int c0, int ncols, const 
                              hipStream_t s) {
   if (B <= 0 || ncols <= 0) return hipSuccess;
   hipLaunchKernelGGL(seg_colsum_kernel, dim3(B, ncols), dim3(256), 0, s, a, lda, c0, ncols, off, out);
+  return hipGetLastError();
+}
+
+// Test hook (gnot_debug_gelu): the three GELU forms of gnot_common.h, which every chain epilogue and weight-
+// gradient loader inlines, evaluated elementwise: y = gelu(x), dy = gelu_grad(x), (y2, dy2) = gelu_and_grad(x)
+__global__ void __launch_bounds__(256) debug_gelu_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                         float* __restrict__ dy, float* __restrict__ y2,
+                                                         float* __restrict__ dy2, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float v = x[i];
+    y[i] = gelu(v);
+    dy[i] = gelu_grad(v);
+    float d;
+    y2[i] = gelu_and_grad(v, d);
+    dy2[i] = d;
+  }
+}
+
+hipError_t launch_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, long n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const unsigned grid = (unsigned)std::min<long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(debug_gelu_kernel, dim3(grid), dim3(256), 0, s, x, y, dy, y2, dy2, n);
   return hipGetLastError();
 }
 

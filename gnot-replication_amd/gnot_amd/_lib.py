@@ -33,7 +33,7 @@ EXPORTS = [
     "gnot_rel_l2_work_floats", "gnot_rel_l2_loss", "gnot_adamw_step",
     "gnot_mse_work_floats", "gnot_mse_loss", "gnot_grad_clip_work_floats", "gnot_grad_clip", "gnot_adamw_step_clipped",
     "gnot_plan_set_grad_arena", "gnot_backward_ex", "gnot_grad_norm", "gnot_adamw_step_guarded",
-    "gnot_ema_update", "gnot_adamw_step_ema", "gnot_gather_rows",
+    "gnot_ema_update", "gnot_adamw_step_ema", "gnot_gather_rows", "gnot_debug_gelu",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -133,6 +133,7 @@ def _declare(lib):
     lib.gnot_ema_update.argtypes = [P, P, i64, P, P]
     lib.gnot_adamw_step_ema.argtypes = [P, P, P, P, P, i64, P, P, P, P]
     lib.gnot_gather_rows.argtypes = [P, i32, P, ctypes.POINTER(i64), i32, P, P]
+    lib.gnot_debug_gelu.argtypes = [P, P, P, P, P, i64, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p

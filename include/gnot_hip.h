@@ -354,6 +354,11 @@ int gnot_profile_read(gnot_plan* plan, double* ms_total, int64_t* launches, doub
  * ("scores", "query0", "out_h0", ...); returns GNOT_E_INVALID for unknown names. */
 int gnot_debug_buffer(const gnot_plan* plan, const char* name, float** ptr, int64_t* ld);
 
+/* Debug/test hook: the device GELU every chain epilogue and weight-gradient loader inlines, evaluated
+ * elementwise over n >= 1 contiguous floats (one launch on `stream`): y = gelu(x), dy = gelu'(x), and (y2, dy2)
+ * the fused value-and-derivative form, bitwise equal to (y, dy).  No plan; the hot path never calls it. */
+int gnot_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, int64_t n, void* stream);
+
 const char* gnot_last_error(void);
 const char* gnot_version(void);
 

@@ -1,7 +1,9 @@
 """Fixture loading + the parity tolerance rule shared by the CPU and GPU tests."""
+import contextlib
 import glob
 import json
 import os
+import re
 
 import numpy as np
 
@@ -112,11 +114,17 @@ def port_reference(cfg, params, xs, thetas, fns_ps, Gs, groups=None):
     rows)) with the float64 values and the norms of the reference's fp32-minus-fp64 differences (rows: one
     norm per output row); grads / e32: parameter gradients summed over samples and their fp32 error norms,
     the form check_parity takes."""
-    B, I = len(xs), cfg["n_input_functions"]
     if groups is None:
-        groups = [[b] for b in range(B) if len(xs[b]) > 0]
-    r64, g64 = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float64")
-    r32, g32 = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float32")
+        groups = [[b] for b in range(len(xs)) if len(xs[b]) > 0]
+    p64 = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float64")
+    p32 = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float32")
+    return _port_compare(cfg, xs, thetas, fns_ps, Gs, p64, p32)
+
+
+def _port_compare(cfg, xs, thetas, fns_ps, Gs, p64, p32):
+    """port_reference's result from a float64 pass and a float32 pass of _port_pass"""
+    B, I = len(xs), cfg["n_input_functions"]
+    (r64, g64), (r32, g32) = p64, p32
     nrm = lambda a, b: float(np.linalg.norm(a - b))
     samples = []
     for b in range(B):
@@ -224,3 +232,289 @@ def check_parity_per_sample(got, fx, rtol=RTOL, slack=SLACK):
         if bad.any():
             errs.append(f"{tag}: {int(bad.sum())} output rows off, {where}: |err| {rows['err'][w]:.3e} > {lim_r[w]:.3e}")
     return errs
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Trained-scale value ranges (tests/test_gpu_value_range.py).  At nn.Linear's default init no GELU
+# pre-activation leaves [-2, 2] and no softmax sees a logit spread above 0.5; scaling three groups of
+# parameters reaches the ranges of a trained model while the float64 reference stays well conditioned.
+_QK = re.compile(r"\.(query|key)(\.\d+)?\.(weight|bias)$")
+
+# regime: (a, b, c) and the ranges its reference must reach: max |GELU pre-activation|, largest softmax
+# logit spread, share of pre-activations beyond 3, largest logit inside a q / k head softmax.
+# `overflow` is `sharp` with q / k logits past ln(FLT_MAX) = 88.72: softmax(h) = exp(h) / sum exp(h) is the same
+# function with and without the max subtracted until exp(h) itself overflows, so only a logit up there tells
+# `__expf(h - m)` from `__expf(h)` (a spread of 100 around zero does not).
+REGIMES = {
+    "moderate": dict(abc=(1.6, 8.0, 3.0), max_h=6.0, spread=8.0, share=0.005, head_logit=0.0),
+    "sharp": dict(abc=(2.0, 16.0, 4.0), max_h=10.0, spread=30.0, share=0.005, head_logit=0.0),
+    "saturated": dict(abc=(2.2, 30.0, 5.0), max_h=16.0, spread=88.0, share=0.005, head_logit=0.0),
+    "qk_only": dict(abc=(1.0, 60.0, 1.0), max_h=0.0, spread=15.0, share=0.0, head_logit=0.0),
+    "overflow": dict(abc=(2.0, 100.0, 4.0), max_h=10.0, spread=30.0, share=0.005, head_logit=95.0),
+}
+
+
+def param_group(key):
+    """'a': the weight of an MLP Linear outside the gating MLP; 'b': weight or bias of an attention query / key
+    projection; 'c': any gating tensor; None: everything else (MLP biases, value projections, fc_out)"""
+    if key.startswith("gating."):
+        return "c"
+    if _QK.search(key):
+        return "b"
+    if ".layers." in key and key.endswith("weight"):
+        return "a"
+    return None
+
+
+def scaled_params(cfg, seed, a, b, c):
+    """float64 state-dict of GNOT(*model_args(cfg)) under torch.manual_seed(seed) with the groups of
+    param_group multiplied by a, b and c"""
+    import torch
+    from gnot_amd import GNOT
+    torch.manual_seed(seed)
+    f = {"a": a, "b": b, "c": c, None: 1.0}
+    return {k: v.double().numpy() * f[param_group(k)] for k, v in GNOT(*model_args(cfg)).state_dict().items()}
+
+
+class _Shim:
+    """a module with some attributes replaced"""
+    def __init__(self, base, **over):
+        self._base = base
+        self.__dict__.update(over)
+
+    def __getattr__(self, name):
+        return getattr(self._base, name)
+
+
+@contextlib.contextmanager
+def port_hooks(gelu=None, softmax=None, linear=None):
+    """Inside the context oracle.torch_port calls these in place of F.gelu / torch.softmax / F.linear.  Only
+    the names the port's own module looks up are replaced (torch itself is untouched) and both are restored
+    on exit, so the port's arithmetic outside the context cannot change."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import torch_port
+    pick = lambda **kw: {k: v for k, v in kw.items() if v is not None}
+    saved = torch_port.F, torch_port.torch
+    torch_port.F = _Shim(F, **pick(gelu=gelu, linear=linear))
+    torch_port.torch = _Shim(torch, **pick(softmax=softmax))
+    try:
+        yield
+    finally:
+        torch_port.F, torch_port.torch = saved
+
+
+class RangeProbe:
+    """What the port's float64 pass really reaches: max |GELU pre-activation|, the share of pre-activations
+    beyond 3, the largest (max - min) logit inside any softmax (feature softmax of q / k, expert gate), and the
+    largest logit inside a q / k head softmax."""
+    def __init__(self):
+        self.max_h, self.n_h, self.n_big, self.spread, self.head_logit = 0.0, 0, 0, 0.0, 0.0
+
+    @property
+    def share(self):
+        return self.n_big / max(self.n_h, 1)
+
+    def hooks(self):
+        import torch
+        import torch.nn.functional as F
+
+        def gelu(h):
+            if h.dtype == torch.float64 and h.numel():
+                a = h.detach().abs()
+                self.max_h = max(self.max_h, float(a.max()))
+                self.n_h += a.numel()
+                self.n_big += int((a > 3.0).sum())
+            return F.gelu(h)
+
+        def softmax(t, dim):
+            if t.dtype == torch.float64 and t.numel():
+                d = t.detach()
+                self.spread = max(self.spread, float((d.max(dim).values - d.min(dim).values).max()))
+                if d.dim() == 4:            # [B, H, L, dh]: a feature softmax over a head of q or k
+                    self.head_logit = max(self.head_logit, float(d.max()))
+            return torch.softmax(t, dim)
+
+        return port_hooks(gelu=gelu, softmax=softmax)
+
+
+def port_reference_ranges(cfg, params, xs, thetas, fns_ps, Gs):
+    """port_reference plus what its float64 pass reached and a second fp32 pass with denormals flushed.
+    Returns (samples, grads, e32, probe, flushed): flushed = (samples, e32) measured with the fp32 pass under
+    torch.set_flush_denormal(True), or None where the machine cannot flush."""
+    import torch
+    groups = [[b] for b in range(len(xs)) if len(xs[b]) > 0]
+    probe = RangeProbe()
+    with probe.hooks():
+        p64 = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float64")
+    p32 = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float32")
+    samples, grads, e32 = _port_compare(cfg, xs, thetas, fns_ps, Gs, p64, p32)
+    flushed = None
+    if torch.set_flush_denormal(True):
+        try:
+            pf = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float32")
+        finally:
+            torch.set_flush_denormal(False)
+        sf, _, ef = _port_compare(cfg, xs, thetas, fns_ps, Gs, p64, pf)
+        flushed = (sf, ef)
+    return samples, grads, e32, probe, flushed
+
+
+def reference_sharpness(samples):
+    """(worst SLACK * e32 / (RTOL * ||out||) over the non-empty samples, the same per output row with the
+    floor max(row norm, sample rms) of check_parity_per_sample)"""
+    ws, wr = 0.0, 0.0
+    for s in samples:
+        if s["N"] == 0:
+            continue
+        ws = max(ws, SLACK * s["e32"]["out"] / (RTOL * float(np.linalg.norm(s["out"]))))
+        rown = np.linalg.norm(s["out"], axis=1)
+        floor = np.maximum(rown, np.sqrt(np.mean(rown ** 2)))
+        wr = max(wr, float((SLACK * np.asarray(s["e32"]["rows"]) / (RTOL * floor)).max()))
+    return ws, wr
+
+
+def value_range_conditions(fx, regime):
+    """The conditions a value-range case must meet on its reference alone (fx: samples, probe, flushed of
+    port_reference_ranges); a list of what is missed.  The regime is really reached; the reference is sharp
+    (SLACK * e32 at most 0.5 of the RTOL term per sample, 1.5 per row); the same with denormals flushed."""
+    R, pr = REGIMES[regime], fx["probe"]
+    bad = []
+    if not pr.max_h >= R["max_h"]:
+        bad.append(f"max |h| {pr.max_h:.2f} < {R['max_h']}")
+    if not pr.spread >= R["spread"]:
+        bad.append(f"softmax spread {pr.spread:.2f} < {R['spread']}")
+    if not pr.share >= R["share"]:
+        bad.append(f"share of |h| > 3 {pr.share:.4f} < {R['share']}")
+    if not pr.head_logit >= R["head_logit"]:
+        bad.append(f"largest q / k softmax logit {pr.head_logit:.1f} < {R['head_logit']}")
+    passes = [("", fx["samples"])] + ([(" (denormals flushed)", fx["flushed"][0])] if fx["flushed"] else [])
+    for tag, samples in passes:
+        ws, wr = reference_sharpness(samples)
+        if not ws <= 0.5:
+            bad.append(f"reference e32 term per sample{tag}: {ws:.2f} of the RTOL term > 0.5")
+        if not wr <= 1.5:
+            bad.append(f"reference e32 term per row{tag}: {wr:.2f} of the RTOL term > 1.5")
+    return bad
+
+
+def port_stages(cfg, params, xs, thetas):
+    """The port's intermediates the engine exposes, per packed row: name -> dict(ref [P, cols] float64, e32
+    [P] the row norms of the port's fp32-minus-fp64 difference, floor [P] max(row norm, its sample's rms row
+    norm)).  "scores": the expert-gate softmax; "query0": the trunk MLP's output."""
+    import torch
+    from oracle import torch_port
+    n_lin = max(cfg["n_mlp_num_layers"], 1) + 1
+
+    def run(dt):
+        p = {k: torch.tensor(np.asarray(v), dtype=dt) for k, v in params.items()}
+        sc, q0 = [], []
+        for x, th in zip(xs, thetas):
+            x, th = torch.tensor(np.asarray(x), dtype=dt)[None], torch.tensor(np.asarray(th), dtype=dt)[None]
+            sc.append(torch.softmax(torch_port._mlp(p, "gating", x, n_lin), -1)[0].double().numpy())
+            xin = torch.cat([x, th[:, None, :].expand(-1, x.shape[1], -1)], -1)
+            q0.append(torch_port._mlp(p, "x", xin, n_lin)[0].double().numpy())
+        return dict(scores=sc, query0=q0)
+
+    r64, r32 = run(torch.float64), run(torch.float32)
+    res = {}
+    for name in r64:
+        floor = []
+        for a in r64[name]:
+            rown = np.linalg.norm(a, axis=1)
+            floor.append(np.maximum(rown, np.sqrt(np.mean(rown ** 2))))
+        ref = np.concatenate(r64[name])
+        res[name] = dict(ref=ref, e32=np.linalg.norm(np.concatenate(r32[name]) - ref, axis=1), floor=np.concatenate(floor))
+    return res
+
+
+def port_bf16_emulated(cfg, params, xs, thetas, fns_ps, Gs):
+    """(out [P, out], grads) of the float64 port with the weight and the input of every Linear rounded to bf16
+    (round to nearest even) before each F.linear, accumulation in float64: what one bf16 operand piece per
+    MFMA costs, without the bf16 storage of saved activations and the fp32 accumulation order."""
+    import torch
+    import torch.nn.functional as F
+    bf = lambda t: t.to(torch.bfloat16).to(t.dtype)
+    groups = [[b] for b in range(len(xs)) if len(xs[b]) > 0]
+    with port_hooks(linear=lambda x, w, b=None: F.linear(bf(x), bf(w), b)):
+        res, grads = _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, "float64")
+    return np.concatenate([r["out"] for r in res if r is not None]), grads
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The device GELU's formula (csrc/gnot_common.h gelu_tail / gelu / gelu_grad) on the CPU: in float64, and
+# operation by operation in float32 with correctly rounded 1/x and exp2 (tests/test_gpu_gelu.py).
+AS_P = 0.3275911
+AS_A = (0.254829592, -0.284496736, 1.421413741, -1.453152027, 1.061405429)
+
+
+def gelu_exact64(x):
+    """(gelu(x), gelu'(x)) with the exact erf, float64"""
+    import torch
+    x = np.asarray(x, np.float64)
+    Phi = 0.5 * (1.0 + torch.special.erf(torch.from_numpy(x / np.sqrt(2.0))).numpy())
+    phi = np.exp(-0.5 * x * x) / np.sqrt(2.0 * np.pi)
+    # x Phi(x) for x < 0 from the complementary function: 1 + erf cancels there
+    tail = 0.5 * torch.special.erfc(torch.from_numpy(np.abs(x) / np.sqrt(2.0))).numpy()
+    Phi = np.where(x < 0, tail, Phi)
+    return x * Phi, Phi + x * phi
+
+
+def gelu_formula64(x):
+    """the kernels' Abramowitz-Stegun 7.1.26 form in float64: (gelu, gelu')"""
+    x = np.asarray(x, np.float64)
+    ax = np.abs(x)
+    t = 1.0 / (1.0 + AS_P * ax / np.sqrt(2.0))
+    P = np.zeros_like(x)
+    for c in AS_A[::-1]:
+        P = P * t + 0.5 * c
+    e = np.exp(-0.5 * x * x)
+    q = P * t * e
+    Phi = 0.5 + np.copysign(0.5 - q, x)
+    return np.maximum(x, 0.0) - ax * q, Phi + x * e / np.sqrt(2.0 * np.pi)
+
+
+def gelu_formula32(x):
+    """gnot_common.h's operation sequence in numpy float32: every constant as the compiler folds it, every fmaf
+    as one rounding (its exact float64 product plus the addend, rounded once more to float32), 1/x and exp2
+    correctly rounded where the device's v_rcp_f32 / v_exp_f32 are 1-ulp approximations: (gelu, gelu')"""
+    f32 = np.float32
+    x = np.asarray(x, f32)
+    f64 = lambda v: np.asarray(v, np.float64)
+    fma = lambda a, b, c: (f64(a) * f64(b) + f64(c)).astype(f32)
+    ax = np.abs(x)
+    k = f32(f32(AS_P) * f32(0.70710678118654752440))
+    t = (f32(1.0) / fma(ax, k, f32(1.0))).astype(f32)
+    h = [f32(f32(0.5) * f32(c)) for c in AS_A]
+    P = fma(t, h[4], h[3])
+    P = fma(t, P, h[2])
+    P = fma(t, P, h[1])
+    P = fma(t, P, h[0])
+    arg = (x * (x * f32(-0.72134752044448170368))).astype(f32)
+    e = np.exp2(arg.astype(np.float64)).astype(f32)
+    q = ((P * t).astype(f32) * e).astype(f32)
+    y = fma(-ax, q, np.maximum(x, f32(0.0)))
+    Phi = (f32(0.5) + np.copysign((f32(0.5) - q).astype(f32), x)).astype(f32)
+    dy = fma((x * f32(0.39894228040143267794)).astype(f32), e, Phi)
+    return y, dy
+
+
+def ulp32(v):
+    """the float32 ulp at |v| (of the smallest normal below it)"""
+    a = np.maximum(np.abs(np.asarray(v, np.float64)), float(np.finfo(np.float32).tiny))
+    return np.exp2(np.floor(np.log2(a)) - 23.0)
+
+
+def gelu_test_inputs():
+    """float32 inputs of the pointwise GELU tests: a grid of 2^20 + 3 points on [-12, 12] (the odd count leaves
+    a grid-stride tail), +-0, +-1e-30, +-1e-40 (a denormal), +-2^k for k = -20 .. 5, and the 200 float32
+    neighbours on each side of +-3.0834 and +-2.4639, where the formula's error peaks"""
+    f32 = np.float32
+    parts = [np.linspace(-12.0, 12.0, 2 ** 20 + 3).astype(f32)]
+    sp = [0.0, 1e-30, 1e-40] + [2.0 ** k for k in range(-20, 6)]
+    parts.append(np.array(sp + [-v for v in sp], f32))
+    for c in (3.0834, 2.4639):
+        bits = int(np.array(c, f32).view(np.int32))
+        nb = (bits + np.arange(-200, 201, dtype=np.int64)).astype(np.int32).view(f32)
+        parts += [nb, -nb]
+    return np.concatenate(parts)

@@ -177,6 +177,19 @@ def test_plan_accepts_meshes_past_the_old_32bit_offset_limit():
         lib.gnot_plan_destroy(plan)
 
 
+def test_debug_gelu_refuses_bad_arguments():
+    """gnot_debug_gelu's checks return before any launch, so dummy device pointers do"""
+    from gnot_amd import _lib
+    lib = _lib.load()
+    D = ctypes.c_void_p(4096)
+    assert lib.gnot_debug_gelu(D, D, D, D, D, 0, None) == -1
+    assert b"debug_gelu" in lib.gnot_last_error()
+    for k in range(5):
+        ptrs = [D] * 5
+        ptrs[k] = None
+        assert lib.gnot_debug_gelu(*ptrs, 16, None) == -1
+
+
 def test_forward_refuses_cpu_tensors():
     from gnot_amd import GNOT
     m = GNOT(2, 1, 3, 1, 1, 32, 2, 32, 32, 2, 4, 0)
