@@ -4,6 +4,7 @@
 // precision switches, workspace sizing, gradient offsets, the caller-owned gradient arena, the flag
 // validation of gnot_backward_ex, the point-shard exchange tables and the error paths -- so heap overflows / use-after-free in engine.cpp's table building show up on the CPU.
 // Run by tests/test_asan.py; exit status 0 = every check passed and ASan reported nothing.
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -20,6 +21,15 @@ static int g_fail = 0;
       ++g_fail;                                                                          \
     }                                                                                    \
   } while (0)
+
+// FNV-1a over every workspace size the program sees, in order: two builds of the planning code that print the
+// same digest lay every geometry below out in the same number of bytes
+static uint64_t g_digest = 0xcbf29ce484222325ull;
+static size_t ws_bytes(const gnot_plan* p) {
+  const size_t v = gnot_plan_workspace_bytes(p);
+  for (int k = 0; k < 8; ++k) g_digest = (g_digest ^ ((uint64_t)v >> (8 * k) & 0xff)) * 0x100000001b3ull;
+  return v;
+}
 
 static int fake_allreduce(void*, float*, int64_t, void*) { return 0; }
 static int fake_alltoallv(void*, const float*, const int64_t*, float*, const int64_t*, void*) { return 0; }
@@ -65,7 +75,7 @@ static void exercise(const gnot_config& cfg, std::mt19937& rng) {
             continue;
           }
           CHECK(st == GNOT_OK);
-          CHECK(gnot_plan_workspace_bytes(p) > 0);
+          CHECK(ws_bytes(p) > 0);
           std::vector<int64_t> go(2 * nlin);
           CHECK(gnot_plan_grad_offsets(p, go.data()) == GNOT_OK);
           int64_t expect = 0;
@@ -91,6 +101,7 @@ static void exercise(const gnot_config& cfg, std::mt19937& rng) {
       const auto lo = offsets(loc);
       const int st = gnot_plan_set_batch(p, B, lo.data(), I ? fo.data() : nullptr, 1);
       CHECK(st == GNOT_OK || lo.back() == 0);
+      if (st == GNOT_OK) CHECK(ws_bytes(p) > 0);
       // a geometry that does not match the declared shard is refused
       if (lo.back() > 0) {
         auto bad = lo;
@@ -116,30 +127,30 @@ static void exercise(const gnot_config& cfg, std::mt19937& rng) {
       fo.insert(fo.end(), o.begin(), o.end());
     }
     CHECK(gnot_plan_set_batch(p, 2, xo.data(), I ? fo.data() : nullptr, 1) == GNOT_OK);
-    const size_t ws = gnot_plan_workspace_bytes(p);
+    const size_t ws = ws_bytes(p);
     std::vector<float> host(gf + 8);
     float* arena = host.data();
     while (reinterpret_cast<uintptr_t>(arena) & 15) ++arena;
     CHECK(gnot_plan_set_grad_arena(p, arena, gf - 1) == GNOT_E_INVALID);
     CHECK(gnot_plan_set_grad_arena(p, arena + 1, gf) == GNOT_E_INVALID);
     CHECK(gnot_plan_set_grad_arena(nullptr, arena, gf) == GNOT_E_INVALID);
-    CHECK(gnot_plan_workspace_bytes(p) == ws);               // the refusals changed nothing
+    CHECK(ws_bytes(p) == ws);               // the refusals changed nothing
     // the flag validation of gnot_backward_ex fails before any launch
     float dout = 0.f;
     CHECK(gnot_backward_ex(p, &dout, 4, nullptr) == GNOT_E_INVALID);
     CHECK(gnot_backward_ex(p, &dout, GNOT_BWD_ACCUMULATE | 8, nullptr) == GNOT_E_INVALID);
     CHECK(gnot_backward_ex(p, &dout, GNOT_BWD_ACCUMULATE, nullptr) == GNOT_E_STATE);   // no caller arena
     CHECK(gnot_plan_set_grad_arena(p, arena, gf) == GNOT_OK);
-    CHECK(gnot_plan_workspace_bytes(p) == 0);                // batch invalidated
+    CHECK(ws_bytes(p) == 0);                // batch invalidated
     CHECK(gnot_plan_set_batch(p, 2, xo.data(), I ? fo.data() : nullptr, 1) == GNOT_OK);
-    CHECK(gnot_plan_workspace_bytes(p) == ws);               // same layout with a caller arena
+    CHECK(ws_bytes(p) == ws);               // same layout with a caller arena
     std::vector<int64_t> go(2 * nlin);
     CHECK(gnot_plan_grad_offsets(p, go.data()) == GNOT_OK);
     CHECK(go[0] == 0 && go[2 * nlin - 1] + dims[2 * nlin - 2] == gf);
     CHECK(gnot_plan_set_grad_arena(p, arena, gf) == GNOT_OK);   // the same arena again: nothing invalidated
-    CHECK(gnot_plan_workspace_bytes(p) == ws);
+    CHECK(ws_bytes(p) == ws);
     CHECK(gnot_plan_set_grad_arena(p, nullptr, 0) == GNOT_OK);  // back to the workspace arena
-    CHECK(gnot_plan_workspace_bytes(p) == 0);
+    CHECK(ws_bytes(p) == 0);
     CHECK(gnot_backward_ex(p, &dout, GNOT_BWD_ACCUMULATE | GNOT_BWD_SKIP_GRAD_COMM, nullptr) == GNOT_E_STATE);
   }
   gnot_plan_destroy(p);
@@ -191,9 +202,13 @@ static void exchange(std::mt19937& rng) {
 
 int main() {
   std::mt19937 rng(12345);
-  const int widths[] = {16, 32, 48, 64, 96, 128, 144, 192, 256};
-  for (int d : widths)
+  // {width, heads}: 96 / 192 have head widths 12 / 24; 320 runs chainw.hip, 576 (internal width 640) the
+  // K-split tables, 100 (heads of 25) padded heads
+  const int widths[][2] = {{16, 4}, {32, 4}, {48, 3}, {64, 8}, {96, 8}, {128, 8}, {144, 3}, {192, 8}, {256, 8},
+                           {320, 10}, {576, 9}, {100, 4}};
+  for (const auto& wh : widths)
     for (int I = 0; I <= 2; ++I) {
+      const int d = wh[0];
       gnot_config c{};
       c.input_dim = 2 + (d & 1);
       c.theta_dim = 1;
@@ -203,7 +218,7 @@ int main() {
       c.n_attn_hidden_dim = c.n_mlp_hidden_dim = c.n_input_hidden_dim = d;
       c.n_mlp_num_layers = 2 + (d % 3);
       c.n_expert = d == 32 ? 2 : d == 48 ? 3 : d == 256 ? 8 : 4;
-      c.n_head = d == 48 || d == 144 ? 3 : d >= 64 ? 8 : 4;   // 96 / 192: head width 12 / 24
+      c.n_head = wh[1];
       c.n_input_functions = I;
       exercise(c, rng);
     }
@@ -215,6 +230,7 @@ int main() {
   gnot_plan* p = nullptr;
   CHECK(gnot_plan_create(&bad, &p) == GNOT_E_INVALID);
   exchange(rng);
+  std::printf("layout digest: %016llx\n", (unsigned long long)g_digest);
   std::printf("asan_plan_check: %s (%d failed checks)\n", g_fail ? "FAILED" : "ok", g_fail);
   return g_fail ? 1 : 0;
 }

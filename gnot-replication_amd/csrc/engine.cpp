@@ -80,11 +80,26 @@ struct WgradGroup {
   int* d_seg_start = nullptr;
 };
 
-struct ChainTable {
-  std::vector<ChainLayer> host;
-  ChainLayer* dev = nullptr;
-  int KT0 = 1, OTL = 1, nchains = 1, in_dim = 0, out_dim = 0;
+// One MLP chain call site: gating, the query encoder, an input-function encoder, one soft-MoE call of a block
+// or the decoder.  build_chains states each once; plan_images, the device tables, the weight-gradient groups
+// and the forward / backward launches read it from here
+struct Chain {
+  std::vector<int> firsts;           // the first canonical Linear of each parallel chain
+  int in_dim = 0, out_dim = 0;
+  int KT0 = 1, OTL = 1;              // input / last-output tile counts (1 up to 16 columns, else D / 16)
+  int kcall = 0;                     // backward slot: its dZ goes to dz_name(kcall)
+  long rows = 0;                     // P, or Q[i] of an input-function encoder
+  std::string x, save;               // input buffer (row pitch: its ld) and saved pre-activations
+  int mode = CH_STORE;
+  std::vector<ChainLayer> layers;    // [firsts.size() * NL] layer table, filled at bind
+  ChainLayer* d_layers = nullptr;
+  WgradGroup wg;                     // the weight gradients of its Linears
 };
+
+// b + off, or null while b is unbound: the sizing pass of set_batch builds every job table for its size
+// only and forms no address
+template <typename T>
+static inline T* at(T* b, long off) { return b ? b + off : nullptr; }
 
 }  // namespace gnot
 
@@ -144,16 +159,22 @@ struct gnot_plan {
   std::vector<long> grad_off;           // 2 per linear
   long grad_floats = 0;
 
+  // the MLP chain call sites in build_chains' order: x, gating, input functions, (ffn1, ffn2) per block, decoder
+  std::vector<Chain> chains;
+  Chain& ch_x() { return chains[0]; }
+  Chain& ch_gate() { return chains[1]; }
+  Chain& ch_fn(int i) { return chains[2 + i]; }
+  Chain& ch_moe(int l, bool m1) { return chains[2 + I + 2 * l + (m1 ? 0 : 1)]; }
+  Chain& ch_out() { return chains.back(); }
+  long per_state() const { return (long)H * (dh * dh + dh); }   // floats of one sample's attention state (S, z)
+  long Qmax() const { return Q.empty() ? 0 : *std::max_element(Q.begin(), Q.end()); }
+
   // device tables
-  ChainTable ch_gate, ch_x, ch_out;
-  std::vector<ChainTable> ch_fn, ch_m1, ch_m2;
   std::vector<int4> qchunks;
   std::vector<int> qchunk_off;
   std::vector<std::vector<int4>> fchunks;
   std::vector<std::vector<int>> fchunk_off;
-  WgradGroup wg_out, wg_x, wg_gate;
-  std::vector<WgradGroup> wg_fn;
-  std::vector<WgradGroup> wg_m1, wg_m2, wg_self, wg_cross;
+  std::vector<WgradGroup> wg_self, wg_cross;
   // attention states as point-reduction GEMM jobs (one job per sample)
   std::vector<std::vector<WgradGroup>> st_c, dst_c;   // [l][source i]
   // cross attention with input functions: the input-function side of EVERY block is batched
@@ -316,8 +337,8 @@ struct gnot_plan {
   std::string dqkv_buf(bool cross) const { return cross ? "dqkv1" : "dqkv0"; }
   std::string dkv_buf(int l, int i) const { return "dkv" + std::to_string(l) + "_" + std::to_string(i); }
   std::string dstate_fn(int l, int i) const { return "dstate" + std::to_string(l) + "_" + std::to_string(i); }
-  float* P_(const char* name) const { return bufs.at(name).p; }
-  float* P_(const std::string& name) const { return bufs.at(name).p; }
+  // a named buffer's address (+ an element offset); null until the workspace is bound
+  float* P_(const std::string& name, long off = 0) const { return at(bufs.at(name).p, off); }
 };
 
 // ====================================================================== construction
@@ -477,6 +498,37 @@ void make_chunks(const std::vector<long>& off, std::vector<int4>& ch, std::vecto
 
 }  // namespace
 
+// the chain call sites of the current batch, in the one order gnot_plan::ch_x() .. ch_out() index
+static void build_chains(gnot_plan* p) {
+  const int D = p->D, NL = p->NL;
+  p->chains.clear();
+  auto add = [&](std::vector<int> firsts, int in_dim, int out_dim, int kcall, long rows, const std::string& x,
+                 const std::string& save, int mode) {
+    Chain C;
+    C.in_dim = in_dim; C.out_dim = out_dim;
+    C.KT0 = in_dim <= 16 ? 1 : p->DT;
+    C.OTL = out_dim <= 16 ? 1 : p->DT;
+    C.kcall = kcall; C.rows = rows; C.x = x; C.save = save; C.mode = mode;
+    C.layers.assign(firsts.size() * NL, ChainLayer{nullptr, nullptr, nullptr});
+    C.firsts = std::move(firsts);
+    p->chains.push_back(std::move(C));
+  };
+  add({p->lin_x(0)}, p->in + p->th, D, p->k_x(), p->P, "xin", "x_save", CH_STORE);
+  add({p->lin_g(0)}, p->in, p->E, p->k_gate(), p->P, "x", "gate_save", CH_SOFTMAX);
+  for (int i = 0; i < p->I; ++i) {
+    const std::string si = std::to_string(i);
+    add({p->lin_fn(i, 0)}, p->F, D, p->k_fn(i), p->Q[i], "fn" + si, "fn_save" + si, CH_STORE);
+  }
+  for (int l = 0; l < p->L; ++l) {
+    const std::string s = "b" + std::to_string(l) + ".";
+    std::vector<int> f1, f2;
+    for (int e = 0; e < p->E; ++e) { f1.push_back(p->lin_f1(l, e, 0)); f2.push_back(p->lin_f2(l, e, 0)); }
+    add(f1, D, D, p->k_m1(l), p->P, s + "a", p->msave(l, true), CH_MOE);
+    add(f2, D, D, p->k_m2(l), p->P, s + "bb", p->msave(l, false), CH_MOE);
+  }
+  add({p->lin_out(0)}, D, p->out, p->k_out(), p->P, p->final_query(), "out_save", CH_STORE);
+}
+
 // build the packed-weight images and pack jobs (offsets relative to the packed arena)
 static void plan_images(gnot_plan* p) {
   const int DT = p->DT, NL = p->NL;
@@ -543,11 +595,11 @@ static void plan_images(gnot_plan* p) {
   // d > 256 (chainw.hip: each Linear on linear.hip): fp32 fragment images in both directions
   const bool cw = p->D > 256;
   const bool b1 = !c2 && !cw && p->npk() == 1;      // d <= 192 in the bf16 mode
-  auto chain_imgs = [&](int first, int KT0, int OTL) {
+  auto chain_imgs = [&](const Chain& C, int c) {     // the images of parallel chain c of call site C
     for (int j = 0; j < NL; ++j) {
-      const int li = first + j;
-      const int KTp = (j == 0) ? KT0 : DT;
-      const int OTp = (j == NL - 1) ? OTL : DT;
+      const int li = C.firsts[c] + j;
+      const int KTp = (j == 0) ? C.KT0 : DT;
+      const int OTp = (j == NL - 1) ? C.OTL : DT;
       Img f = cw ? new_img(OTp, KTp) : new_img_x6(OTp, KTp, c2 ? c2np : b1 ? 1 : 3);
       const size_t bo = new_bias(16 * OTp);
       job(li, f, 0, 0, OTp, KTp, 0, (long)bo, cw ? 0 : c2 ? c2x6 : b1 ? 4 : 1);
@@ -560,10 +612,11 @@ static void plan_images(gnot_plan* p) {
       p->fwd_bias[li] = bo;
     }
   };
-  auto kt_of = [&](int w) { return w <= 16 ? 1 : DT; };
-  chain_imgs(p->lin_x(0), kt_of(p->in + p->th), DT);
-  chain_imgs(p->lin_g(0), kt_of(p->in), kt_of(p->E));
-  for (int i = 0; i < p->I; ++i) chain_imgs(p->lin_fn(i, 0), kt_of(p->F), DT);
+  // the order images are created in IS the packed arena's layout: encoders, then per block the attention
+  // images and per expert ffn1_e, ffn2_e, then the decoder
+  chain_imgs(p->ch_x(), 0);
+  chain_imgs(p->ch_gate(), 0);
+  for (int i = 0; i < p->I; ++i) chain_imgs(p->ch_fn(i), 0);
   p->cross_img.assign(p->L, gnot_plan::AttnImgs());
   p->self_img.assign(p->L, gnot_plan::AttnImgs());
   // attention projections: at d = 256 the q | q|k|v | fc_out images and the backward-data images that
@@ -620,11 +673,11 @@ static void plan_images(gnot_plan* p) {
     attn_imgs(p->cross_img[l], p->lin_cq(l), p->lin_co(l), ck, cv, p->I == 0);
     attn_imgs(p->self_img[l], p->lin_sq(l), p->lin_so(l), {p->lin_sk(l)}, {p->lin_sv(l)}, true);
     for (int e = 0; e < p->E; ++e) {
-      chain_imgs(p->lin_f1(l, e, 0), DT, DT);
-      chain_imgs(p->lin_f2(l, e, 0), DT, DT);
+      chain_imgs(p->ch_moe(l, true), e);
+      chain_imgs(p->ch_moe(l, false), e);
     }
   }
-  chain_imgs(p->lin_out(0), DT, kt_of(p->out));
+  chain_imgs(p->ch_out(), 0);
   p->pack_prefix.clear();
   int acc = 0;
   for (auto& J : p->pack_jobs) {
@@ -648,7 +701,7 @@ static bool balanced_wgrad(const WgradGroup& G) {
 static void finish_group(gnot_plan* p, WgradGroup& G) {
   G.x6 = true;
   for (const auto& J : G.jobs)
-    if (J.w != nullptr || J.state_dh > 0 || J.diag_only) G.x6 = false;
+    if (J.ldw > 0 || J.state_dh > 0 || J.diag_only) G.x6 = false;   // ldw > 0: per-point weights
   // the x6 kernel holds ~240 registers per lane: one workgroup per CU leaves the other half of
   // every SIMD's register file to the concurrent main-stream kernels
   constexpr long x6_wgs = 256;
@@ -771,7 +824,7 @@ static void finish_state_group(gnot_plan* p, WgradGroup& G) {
     G.state_pts = state_pts(G.state_mfma, d);
     G.state_nw = 0;
     for (const auto& J : G.jobs)
-      if (J.w != nullptr) G.state_nw = d / J.state_dh;
+      if (J.ldw > 0) G.state_nw = d / J.state_dh;
   }
   G.wg_prefix.clear();
   G.red_prefix.clear();
@@ -795,9 +848,8 @@ static void finish_state_group(gnot_plan* p, WgradGroup& G) {
 template <typename F>
 static void for_each_group(gnot_plan* p, F&& f) {
   if (p->training) {
-    f(p->wg_out); f(p->wg_x); f(p->wg_gate);
-    for (auto& G : p->wg_fn) f(G);
-    for (int l = 0; l < p->L; ++l) { f(p->wg_m1[l]); f(p->wg_m2[l]); f(p->wg_self[l]); f(p->wg_cross[l]); }
+    for (Chain& C : p->chains) f(C.wg);
+    for (int l = 0; l < p->L; ++l) { f(p->wg_self[l]); f(p->wg_cross[l]); }
     f(p->wg_fnkv);
   }
   f(p->st_fn);
@@ -811,30 +863,30 @@ static void for_each_group(gnot_plan* p, F&& f) {
   }
 }
 
-// (Re)build every job list from the current buffer pointers (null before bind: sizing only).
+// (Re)build every job list from the current buffer pointers.  Before bind every buffer is null and so is every
+// pointer in the jobs (P_ / at): that pass is for the table and slab sizes, which depend on shapes alone.
 static void build_groups(gnot_plan* p) {
   p->slab_wgrad_floats = 0;
   p->slab_state_floats = 0;
   const long P = p->P;
-  const int D = p->D, NL = p->NL, E = p->E, I = p->I, KI = p->KI, dh = p->dh;
+  const int D = p->D, NL = p->NL, I = p->I, KI = p->KI, dh = p->dh;
   const bool tr = p->training;
-  const long per_state = (long)p->H * (dh * dh + dh);
-  p->wg_out = {}; p->wg_x = {}; p->wg_gate = {};
-  p->wg_fn.assign(I, {});
-  p->wg_m1.assign(p->L, {}); p->wg_m2.assign(p->L, {});
+  const long per_state = p->per_state();
+  float* const grads = p->grads();
+  for (Chain& C : p->chains) C.wg = {};
   p->wg_self.assign(p->L, {}); p->wg_cross.assign(p->L, {});
+  p->wg_fnkv = {};
   p->st_c.assign(p->L, std::vector<WgradGroup>(KI));
   p->dst_c.assign(p->L, std::vector<WgradGroup>(KI));
   p->st_s.assign(p->L, {}); p->dst_s.assign(p->L, {});
 
   auto lin_job = [&](WgradGroup& G, int li, const float* dz, long lddz, const float* x, long ldx, int gelu,
                      long rows) {
-    float* grads = p->grads();
     WgradJob J{};
     J.dz = dz; J.lddz = lddz; J.x = x; J.ldx = ldx; J.x_gelu = gelu;
     J.out = p->lin_o[li]; J.in = p->lin_i[li];
-    J.dW = grads + p->grad_off[2 * li];
-    J.db = grads + p->grad_off[2 * li + 1];
+    J.dW = at(grads, p->grad_off[2 * li]);
+    J.db = at(grads, p->grad_off[2 * li + 1]);
     J.P = (int)rows;
     G.jobs.push_back(J);
     G.lins.push_back(li);
@@ -846,55 +898,57 @@ static void build_groups(gnot_plan* p) {
       lin_job(G, li, dz, lddz, x, ldx, 0, rows);
       return;
     }
-    float* grads = p->grads();
     const int in = p->lin_i[li];
     for (int h = 0; h < p->H; ++h) {
       WgradJob J{};
-      J.dz = dz ? dz + (long)h * dh : nullptr; J.lddz = lddz; J.x = x; J.ldx = ldx; J.x_gelu = 0;
+      J.dz = at(dz, (long)h * dh); J.lddz = lddz; J.x = x; J.ldx = ldx; J.x_gelu = 0;
       J.out = p->dhr; J.in = in;
-      J.dW = grads + p->grad_off[2 * li] + (long)h * p->dhr * in;
-      J.db = grads + p->grad_off[2 * li + 1] + (long)h * p->dhr;
+      J.dW = at(grads, p->grad_off[2 * li] + (long)h * p->dhr * in);
+      J.db = at(grads, p->grad_off[2 * li + 1] + (long)h * p->dhr);
       J.P = (int)rows;
       G.jobs.push_back(J);
     }
     G.lins.push_back(li);
   };
-  // chain c of a group: Linear j reads dZ_j from dz[(c*NL + j)*rows*D] and its input from the
+  // chain c of a call site: Linear j reads dZ_j from dz[(c*NL + j)*rows*D] and its input from the
   // chain input (j = 0) or gelu(saved pre-activation j-1)
-  auto chain_group = [&](WgradGroup& G, int kcall, const std::vector<int>& firsts, long rows, const float* x0,
-                         long ldx0, const float* save) {
-    const float* dz = p->P_(p->dz_name(kcall));
-    for (size_t c = 0; c < firsts.size(); ++c)
+  auto chain_group = [&](Chain& C) {
+    const float* dz = p->P_(p->dz_name(C.kcall));
+    const float* save = p->P_(C.save);
+    const Buf& x0 = p->bufs.at(C.x);
+    const long rows = C.rows;
+    for (size_t c = 0; c < C.firsts.size(); ++c)
       for (int j = 0; j < NL; ++j) {
-        const float* dzp = dz + ((long)c * NL + j) * rows * D;
-        if (j == 0) lin_job(G, firsts[c] + j, dzp, D, x0, ldx0, 0, rows);
-        else lin_job(G, firsts[c] + j, dzp, D, save + ((long)c * NL + j - 1) * rows * D, D, 1, rows);
+        const float* dzp = at(dz, ((long)c * NL + j) * rows * D);
+        if (j == 0) lin_job(C.wg, C.firsts[c] + j, dzp, D, x0.p, x0.ld, 0, rows);
+        else lin_job(C.wg, C.firsts[c] + j, dzp, D, at(save, ((long)c * NL + j - 1) * rows * D), D, 1, rows);
       }
-    finish_group(p, G);
+    finish_group(p, C.wg);
   };
   // bf16-storage soft-MoE group (bf16 mode): dZ_j of chain c at dz + (c NL + j) lay, the input of Linear
   // j > 0 in save slot NL + j of chain c, Linear 0's (the shared MoE input) in chain 0's slot NL
-  auto moe_group_b16 = [&](WgradGroup& G, int kcall, const std::vector<int>& firsts, const float* save) {
-    const float* dz = p->P_(p->dz_name(kcall));
+  auto moe_group_b16 = [&](Chain& C) {
+    const float* dz = p->P_(p->dz_name(C.kcall));
+    const float* save = p->P_(C.save);
     const long lay = P * D / 2;
-    for (size_t c = 0; c < firsts.size(); ++c)
+    for (size_t c = 0; c < C.firsts.size(); ++c)
       for (int j = 0; j < NL; ++j) {
-        const float* x = j == 0 ? save + NL * lay : save + ((long)c * 2 * NL + NL + j) * lay;
-        lin_job(G, firsts[c] + j, dz + ((long)c * NL + j) * lay, D, x, D, 0, P);
+        const float* x = at(save, (j == 0 ? NL : (long)c * 2 * NL + NL + j) * lay);
+        lin_job(C.wg, C.firsts[c] + j, at(dz, ((long)c * NL + j) * lay), D, x, D, 0, P);
       }
-    G.b16 = true;
-    finish_group(p, G);
+    C.wg.b16 = true;
+    finish_group(p, C.wg);
   };
   auto state_group = [&](WgradGroup& G, const float* A, long lda, const float* Bm, long ldb, const float* w,
                          long ldw, const std::vector<long>& off, float* state) {
     for (int b = 0; b < p->B; ++b) {
       WgradJob J{};
-      J.dz = A + off[b] * lda; J.lddz = lda;
-      J.x = Bm + off[b] * ldb; J.ldx = ldb;
+      J.dz = at(A, off[b] * lda); J.lddz = lda;
+      J.x = at(Bm, off[b] * ldb); J.ldx = ldb;
       J.out = p->hd(); J.in = p->hd();            // H heads of dh (the internal head width)
-      J.dW = state + b * per_state;
+      J.dW = at(state, b * per_state);
       J.db = J.dW;
-      J.w = w ? w + off[b] * ldw : nullptr; J.ldw = ldw; J.wdh = dh;
+      J.w = at(w, off[b] * ldw); J.ldw = ldw; J.wdh = dh;
       J.state_dh = dh; J.diag_only = 1;
       J.P = (int)(off[b + 1] - off[b]);
       G.jobs.push_back(J);
@@ -904,17 +958,12 @@ static void build_groups(gnot_plan* p) {
 
   for (int l = 0; l < p->L; ++l) {
     const std::string s = "b" + std::to_string(l) + ".";
-    // forward states
-    if (I > 0) {
-      // (all blocks' input-function states are one group: st_fn, below)
-    } else {
-      float* qkv = p->P_(s + "cq");
-      state_group(p->st_c[l][0], qkv + D, 3 * D, qkv + 2 * D, 3 * D, nullptr, 0, p->xoff, p->P_(s + "cstate0"));
-    }
-    {
-      float* qkv = p->P_(s + "sq");
-      state_group(p->st_s[l], qkv + D, 3 * D, qkv + 2 * D, 3 * D, nullptr, 0, p->xoff, p->P_(s + "sstate"));
-    }
+    // forward states (with input functions, all blocks' cross states are one group: st_fn, below)
+    if (I == 0)
+      state_group(p->st_c[l][0], p->P_(s + "cq", D), 3 * D, p->P_(s + "cq", 2 * D), 3 * D, nullptr, 0, p->xoff,
+                  p->P_(s + "cstate0"));
+    state_group(p->st_s[l], p->P_(s + "sq", D), 3 * D, p->P_(s + "sq", 2 * D), 3 * D, nullptr, 0, p->xoff,
+                p->P_(s + "sstate"));
     if (!tr) continue;
     // backward states dS = sum q^T du, dz = sum dden q
     for (int i = 0; i < KI; ++i) {
@@ -937,8 +986,8 @@ static void build_groups(gnot_plan* p) {
         for (int b = 0; b < p->B; ++b) {
           WgradJob J{};
           const long o = p->fnoff[i][b];
-          J.dz = kv + o * 2 * D; J.lddz = 2 * D; J.x = kv + D + o * 2 * D; J.ldx = 2 * D;
-          J.out = p->hd(); J.in = p->hd(); J.dW = st + b * per_state; J.db = J.dW; J.wdh = dh;
+          J.dz = at(kv, o * 2 * D); J.lddz = 2 * D; J.x = at(kv, D + o * 2 * D); J.ldx = 2 * D;
+          J.out = p->hd(); J.in = p->hd(); J.dW = at(st, b * per_state); J.db = J.dW; J.wdh = dh;
           J.state_dh = dh; J.diag_only = 1; J.P = (int)(p->fnoff[i][b + 1] - o);
           p->st_fn.jobs.push_back(J);
         }
@@ -947,60 +996,44 @@ static void build_groups(gnot_plan* p) {
   }
   if (!tr) return;
 
-  p->wg_fnkv = {};
   if (I > 0) {
     for (int l = 0; l < p->L; ++l)
       for (int i = 0; i < I; ++i) {
-        float* dkv = p->P_(p->dkv_buf(l, i));
+        const std::string dkv = p->dkv_buf(l, i);
         const float* enc = p->P_("fnenc" + std::to_string(i));
-        lin_job_heads(p->wg_fnkv, p->lin_ck(l, i), dkv, 2 * D, enc, D, p->Q[i]);
-        lin_job_heads(p->wg_fnkv, p->lin_cv(l, i), dkv + D, 2 * D, enc, D, p->Q[i]);
+        lin_job_heads(p->wg_fnkv, p->lin_ck(l, i), p->P_(dkv), 2 * D, enc, D, p->Q[i]);
+        lin_job_heads(p->wg_fnkv, p->lin_cv(l, i), p->P_(dkv, D), 2 * D, enc, D, p->Q[i]);
       }
     finish_group(p, p->wg_fnkv);
   }
 
-  chain_group(p->wg_out, p->k_out(), {p->lin_out(0)}, P, p->P_(p->final_query()), D, p->P_("out_save"));
-  chain_group(p->wg_x, p->k_x(), {p->lin_x(0)}, P, p->P_("xin"), p->bufs.at("xin").ld, p->P_("x_save"));
-  chain_group(p->wg_gate, p->k_gate(), {p->lin_g(0)}, P, p->P_("x"), p->bufs.at("x").ld, p->P_("gate_save"));
-  for (int i = 0; i < I; ++i) {
-    const std::string si = std::to_string(i);
-    chain_group(p->wg_fn[i], p->k_fn(i), {p->lin_fn(i, 0)}, p->Q[i], p->P_("fn" + si), p->bufs.at("fn" + si).ld,
-                p->P_("fn_save" + si));
+  for (Chain& C : p->chains) {
+    if (C.mode == CH_MOE && p->b16s()) moe_group_b16(C);
+    else chain_group(C);
   }
   for (int l = 0; l < p->L; ++l) {
     const std::string s = "b" + std::to_string(l) + ".";
-    std::vector<int> f1, f2;
-    for (int e = 0; e < E; ++e) { f1.push_back(p->lin_f1(l, e, 0)); f2.push_back(p->lin_f2(l, e, 0)); }
-    if (p->b16s()) {
-      moe_group_b16(p->wg_m1[l], p->k_m1(l), f1, p->P_(p->msave(l, true)));
-      moe_group_b16(p->wg_m2[l], p->k_m2(l), f2, p->P_(p->msave(l, false)));
-    } else {
-      chain_group(p->wg_m1[l], p->k_m1(l), f1, P, p->P_(s + "a"), D, p->P_(p->msave(l, true)));
-      chain_group(p->wg_m2[l], p->k_m2(l), f2, P, p->P_(s + "bb"), D, p->P_(p->msave(l, false)));
-    }
     {
-      float* dsum = p->P_(p->dsum_buf(false));
-      float* dqkv = p->P_(p->dqkv_buf(false));
+      const std::string dqkv = p->dqkv_buf(false);
       WgradGroup& G = p->wg_self[l];
       const float* q1 = p->P_(s + "query1");
-      lin_job(G, p->lin_so(l), dsum, D, p->P_(s + "sres"), p->Dr, 0, P);
-      lin_job_heads(G, p->lin_sq(l), dqkv, 3 * D, q1, D, P);
-      lin_job_heads(G, p->lin_sk(l), dqkv + D, 3 * D, q1, D, P);
-      lin_job_heads(G, p->lin_sv(l), dqkv + 2 * D, 3 * D, q1, D, P);
+      lin_job(G, p->lin_so(l), p->P_(p->dsum_buf(false)), D, p->P_(s + "sres"), p->Dr, 0, P);
+      lin_job_heads(G, p->lin_sq(l), p->P_(dqkv), 3 * D, q1, D, P);
+      lin_job_heads(G, p->lin_sk(l), p->P_(dqkv, D), 3 * D, q1, D, P);
+      lin_job_heads(G, p->lin_sv(l), p->P_(dqkv, 2 * D), 3 * D, q1, D, P);
       finish_group(p, G);
     }
     {
-      float* dsum = p->P_(p->dsum_buf(true));
-      float* dqkv = p->P_(p->dqkv_buf(true));
+      const std::string dqkv = p->dqkv_buf(true);
       WgradGroup& G = p->wg_cross[l];
       const float* qin = p->P_(p->block_query(l));
-      lin_job(G, p->lin_co(l), dsum, D, p->P_(s + "cres"), p->Dr, 0, P);
+      lin_job(G, p->lin_co(l), p->P_(p->dsum_buf(true)), D, p->P_(s + "cres"), p->Dr, 0, P);
       if (I > 0) {
-        lin_job_heads(G, p->lin_cq(l), dqkv, D, qin, D, P);   // key/value grads: wg_fnkv
+        lin_job_heads(G, p->lin_cq(l), p->P_(dqkv), D, qin, D, P);   // key/value grads: wg_fnkv
       } else {
-        lin_job_heads(G, p->lin_cq(l), dqkv, 3 * D, qin, D, P);
-        lin_job_heads(G, p->lin_ck(l, 0), dqkv + D, 3 * D, qin, D, P);
-        lin_job_heads(G, p->lin_cv(l, 0), dqkv + 2 * D, 3 * D, qin, D, P);
+        lin_job_heads(G, p->lin_cq(l), p->P_(dqkv), 3 * D, qin, D, P);
+        lin_job_heads(G, p->lin_ck(l, 0), p->P_(dqkv, D), 3 * D, qin, D, P);
+        lin_job_heads(G, p->lin_cv(l, 0), p->P_(dqkv, 2 * D), 3 * D, qin, D, P);
       }
       finish_group(p, G);
     }
@@ -1016,8 +1049,8 @@ static void ksplit_job(const gnot_plan* p, LinearArgs& a) {
   LinearArgs b = a;
   b.nseg = 2 * a.nseg;
   for (int k = 0; k < b.nseg; ++k) {
-    b.X[k] = a.X[k / 2] + (k % 2) * Kh;
-    b.Wp[k] = a.Wp[k / 2] + (k % 2) * half4;
+    b.X[k] = at(a.X[k / 2], (k % 2) * Kh);
+    b.Wp[k] = at(a.Wp[k / 2], (k % 2) * half4);
   }
   b.K = Kh;
   b.dblk = p->D;
@@ -1032,14 +1065,13 @@ static void build_attn_tables(gnot_plan* p) {
   p->kvbwd_jobs.clear();
   p->dfn_jobs.clear();
   if (I == 0 || L == 0) return;
-  float* pbias = p->P_("pbias");
   for (int l = 0; l < L; ++l)
     for (int i = 0; i < I; ++i) {
       const std::string s = "b" + std::to_string(l) + ".", si = std::to_string(i);
       const gnot_plan::AttnImgs& A = p->cross_img[l];
       LinearArgs a{};
       a.nseg = 1; a.X[0] = p->P_("fnenc" + si); a.ldx = D; a.Wp[0] = A.kv[i].p; a.nsum = 1; a.K = D;
-      a.bias = pbias + A.bkv[i]; a.Y = p->P_(s + "ckv" + si); a.ldy = 2 * D; a.NO = 2 * D; a.P = (int)p->Q[i];
+      a.bias = p->P_("pbias", A.bkv[i]); a.Y = p->P_(s + "ckv" + si); a.ldy = 2 * D; a.NO = 2 * D; a.P = (int)p->Q[i];
       a.epi = EPI_STORE; a.nsoft = D; a.dh = p->dh; a.dreal = p->attn_dreal();
       a.dhr = p->head_padded() ? p->dhr : 0;
       ksplit_job(p, a);
@@ -1052,10 +1084,10 @@ static void build_attn_tables(gnot_plan* p) {
       const float* kv = p->P_(s + "ckv" + std::to_string(i));
       float* dkv = p->P_(p->dkv_buf(l, i));
       AttnKVBwdArgs kb{};
-      kb.k = kv; kb.v = kv + D; kb.ldkv = 2 * D; kb.dstate = p->P_(p->dstate_fn(l, i));
-      kb.chunks = p->d_fchunks.empty() ? nullptr : p->d_fchunks[i];
+      kb.k = kv; kb.v = at(kv, D); kb.ldkv = 2 * D; kb.dstate = p->P_(p->dstate_fn(l, i));
+      kb.chunks = p->d_fchunks[i];               // (walk_tables places the chunk tables before these jobs)
       kb.nchunks = (int)p->fchunks[i].size(); kb.H = p->H; kb.dh = p->dh;
-      kb.dk = dkv; kb.dv = dkv + D; kb.lddkv = 2 * D;
+      kb.dk = dkv; kb.dv = at(dkv, D); kb.lddkv = 2 * D;
       p->kvbwd_jobs.push_back(kb);
     }
   // d(fn encoding i) = sum_l dK_{l,i} Wk_{l,i} + dV_{l,i} Wv_{l,i}: 2L K-segments, <= kMaxSeg per launch (half
@@ -1069,7 +1101,7 @@ static void build_attn_tables(gnot_plan* p) {
       a.nseg = std::min(per, nseg - k0);
       for (int sg = 0; sg < a.nseg; ++sg) {
         const int l = (k0 + sg) / 2, kv = (k0 + sg) % 2;
-        a.X[sg] = p->P_(p->dkv_buf(l, i)) + kv * D;
+        a.X[sg] = p->P_(p->dkv_buf(l, i), kv * D);
         a.Wp[sg] = p->T_img[kv ? p->lin_cv(l, i) : p->lin_ck(l, i)].p;
       }
       a.ldx = 2 * D; a.nsum = 1; a.K = D; a.bias = nullptr; a.Y = p->P_("dfn" + std::to_string(i)); a.ldy = D;
@@ -1079,6 +1111,98 @@ static void build_attn_tables(gnot_plan* p) {
     }
     p->dfn_jobs.push_back(launch);
   }
+}
+
+// ====================================================================== device tables
+// The tables lie one after another in the workspace's "__tables" region, each rounded up to 256 bytes.
+// set_batch walks them unbound (no host image, no device base) to add up the region's size; bind walks them
+// again to fill the host image that is uploaded and to set every device pointer.
+struct TableWalk {
+  char* host = nullptr;      // the region's host image (cap bytes), or null: sizing only
+  char* dev = nullptr;       // the region's device address
+  size_t cap = 0, cur = 0;
+  void* put(const void* src, size_t bytes) {
+    void* d = dev ? dev + cur : nullptr;
+    if (host && bytes && cur + bytes <= cap) std::memcpy(host + cur, src, bytes);
+    cur += ((bytes + 255) / 256) * 256;
+    return d;
+  }
+  template <typename T>
+  void operator()(const std::vector<T>& v, T*& d) { d = static_cast<T*>(put(v.data(), v.size() * sizeof(T))); }
+};
+
+// every device table once: its host data and where its device pointer goes.  The job lists are (re)built
+// here from the current buffer pointers, after the chunk tables they point into
+static void walk_tables(gnot_plan* p, TableWalk& w) {
+  const int I = p->I, NL = p->NL;
+  // pack jobs with real pointers (the plan's own hold offsets and the Linear's index in W), resolved images
+  std::vector<PackJob> jobs = p->pack_jobs;
+  if (w.host) {
+    float4* packed = reinterpret_cast<float4*>(p->P_("packed"));
+    float* pbias = p->P_("pbias");
+    for (size_t k = 0; k < jobs.size(); ++k) {
+      const int li = (int)reinterpret_cast<intptr_t>(jobs[k].W);
+      jobs[k].W = p->W[li];
+      jobs[k].b = p->b[li];
+      jobs[k].dst = packed + p->pack_dst_off4[k];
+      jobs[k].bias_dst = (p->pack_bias_off[k] == (size_t)-1) ? nullptr : pbias + p->pack_bias_off[k];
+    }
+    auto rimg = [&](Img& im) { im.p = packed + im.off4; };
+    for (auto& im : p->fwd_img) rimg(im);
+    for (auto& im : p->T_img) rimg(im);
+    for (auto* v : {&p->cross_img, &p->self_img})
+      for (auto& A : *v) {
+        rimg(A.qkv); rimg(A.q); rimg(A.o);
+        for (auto& k : A.kv) rimg(k);
+      }
+    for (Chain& C : p->chains) {
+      C.layers.clear();
+      for (int f : C.firsts)
+        for (int li = f; li < f + NL; ++li)
+          C.layers.push_back(ChainLayer{p->fwd_img[li].p, p->T_img[li].p, pbias + p->fwd_bias[li]});
+    }
+  }
+  w(jobs, p->d_pack_jobs);
+  w(p->pack_prefix, p->d_pack_prefix);
+  for (Chain& C : p->chains) w(C.layers, C.d_layers);
+  w(p->qchunks, p->d_qchunks);
+  w(p->qchunk_off, p->d_qchunk_off);
+  p->d_fchunks.assign(I, nullptr);
+  p->d_fchunk_off.assign(I, nullptr);
+  for (int i = 0; i < I; ++i) {
+    w(p->fchunks[i], p->d_fchunks[i]);
+    w(p->fchunk_off[i], p->d_fchunk_off[i]);
+  }
+  {
+    std::vector<long> offs(p->xoff);
+    for (int i = 0; i < I; ++i) offs.insert(offs.end(), p->fnoff[i].begin(), p->fnoff[i].end());
+    w(offs, p->d_xoff);
+    p->d_fnoff.assign(I, nullptr);
+    for (int i = 0; i < I; ++i) p->d_fnoff[i] = at(p->d_xoff, (long)(p->B + 1) * (i + 1));
+  }
+  build_groups(p);
+  for_each_group(p, [&](WgradGroup& G) {
+    w(G.jobs, G.d_jobs);
+    std::vector<int> pre(G.wg_prefix);
+    pre.insert(pre.end(), G.red_prefix.begin(), G.red_prefix.end());
+    w(pre, G.d_wg_prefix);
+    G.d_red_prefix = at(G.d_wg_prefix, (long)G.jobs.size());
+    G.d_segs = nullptr;              // null: the launch is not a balanced one (finish_group)
+    G.d_seg_start = nullptr;
+    if (!G.segs.empty()) {
+      w(G.segs, G.d_segs);
+      w(G.seg_start, G.d_seg_start);
+    }
+  });
+  build_attn_tables(p);
+  w(p->fwd_kv_jobs, p->d_fwd_kv_jobs);
+  w(p->kvbwd_jobs, p->d_kvbwd_jobs);
+  p->d_dfn_jobs.assign(p->dfn_jobs.size(), nullptr);
+  for (size_t k = 0; k < p->dfn_jobs.size(); ++k) w(p->dfn_jobs[k], p->d_dfn_jobs[k]);
+  w(p->xsend, p->d_xsend);
+  w(p->xrecv, p->d_xrecv);
+  w(p->xsend_prefix, p->d_xsend_prefix);
+  w(p->xrecv_prefix, p->d_xrecv_prefix);
 }
 
 // ====================================================================== point sharding
@@ -1304,15 +1428,14 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
   }
 
   // ---------------- workspace carve
+  build_chains(p);
   plan_images(p);
   p->bufs.clear();
   p->buf_order.clear();
   Carver C{0, p};
   const long P = p->P, D = p->D, E = p->E, NL = p->NL, H = p->H;
-  const long per_state = (long)p->H * (p->dh * p->dh + p->dh);
+  const long per_state = p->per_state(), Qmax = p->Qmax();
   const int I = p->I, KI = p->KI;
-  long Qmax = 0;
-  for (long q : p->Q) Qmax = std::max(Qmax, q);
   C.add("packed", p->packed4 * 4, 0);
   C.add("pbias", p->pbias, 0);
   // gradient arena
@@ -1411,62 +1534,11 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
     if (I > 0) C.add("dzf", NL * Qmax * D, D);
   }
 
-  // ---------------- device tables (host images; uploaded at bind)
-  p->table_bytes = 0;
-  p->ch_gate = {}; p->ch_x = {}; p->ch_out = {};
-  p->ch_fn.assign(I, {});
-  p->ch_m1.assign(p->L, {});
-  p->ch_m2.assign(p->L, {});
-  const int DT = p->DT;
-  auto kt_of = [&](int w) { return w <= 16 ? 1 : DT; };
-  auto chain = [&](ChainTable& T, std::vector<int> firsts, int in_dim, int out_dim) {
-    T.nchains = (int)firsts.size();
-    T.in_dim = in_dim;
-    T.out_dim = out_dim;
-    T.KT0 = kt_of(in_dim);
-    T.OTL = kt_of(out_dim);
-    T.host.clear();
-    T.host.assign(firsts.size() * NL, ChainLayer{nullptr, nullptr, nullptr});   // filled at bind
-  };
-  chain(p->ch_gate, {p->lin_g(0)}, p->in, E);
-  chain(p->ch_x, {p->lin_x(0)}, p->in + p->th, (int)D);
-  chain(p->ch_out, {p->lin_out(0)}, (int)D, p->out);
-  for (int i = 0; i < I; ++i) chain(p->ch_fn[i], {p->lin_fn(i, 0)}, p->F, (int)D);
-  for (int l = 0; l < p->L; ++l) {
-    std::vector<int> f1, f2;
-    for (int e = 0; e < E; ++e) { f1.push_back(p->lin_f1(l, e, 0)); f2.push_back(p->lin_f2(l, e, 0)); }
-    chain(p->ch_m1[l], f1, (int)D, (int)D);
-    chain(p->ch_m2[l], f2, (int)D, (int)D);
-  }
-  auto tbl = [&](size_t bytes) { p->table_bytes += ((bytes + 255) / 256) * 256; };
-  tbl(p->pack_jobs.size() * sizeof(PackJob));
-  tbl(p->pack_prefix.size() * sizeof(int));
-  auto tbl_chain = [&](const ChainTable& T) { tbl(T.host.size() * sizeof(ChainLayer)); };
-  tbl_chain(p->ch_gate); tbl_chain(p->ch_x); tbl_chain(p->ch_out);
-  for (auto& T : p->ch_fn) tbl_chain(T);
-  for (auto& T : p->ch_m1) tbl_chain(T);
-  for (auto& T : p->ch_m2) tbl_chain(T);
-  tbl(p->qchunks.size() * sizeof(int4));
-  tbl(p->qchunk_off.size() * sizeof(int));
-  for (int i = 0; i < I; ++i) { tbl(p->fchunks[i].size() * sizeof(int4)); tbl(p->fchunk_off[i].size() * sizeof(int)); }
-  tbl((p->B + 1) * sizeof(long) * (1 + I));
-  tbl(p->xsend.size() * sizeof(CopySeg)); tbl(p->xrecv.size() * sizeof(CopySeg));
-  tbl(p->xsend_prefix.size() * sizeof(int)); tbl(p->xrecv_prefix.size() * sizeof(int));
-
-  // point-reduction GEMM groups: built with null buffer pointers now (sizes only), rebuilt with
-  // real pointers at bind
-  build_groups(p);
-  auto tbl_group = [&](const WgradGroup& G) {
-    tbl(G.jobs.size() * sizeof(WgradJob));
-    tbl(G.jobs.size() * sizeof(int) * 2);
-    tbl(G.segs.size() * sizeof(int4));
-    tbl(G.seg_start.size() * sizeof(int));
-  };
-  for_each_group(p, tbl_group);
-  build_attn_tables(p);
-  tbl(p->fwd_kv_jobs.size() * sizeof(LinearArgs));
-  tbl(p->kvbwd_jobs.size() * sizeof(AttnKVBwdArgs));
-  for (auto& v : p->dfn_jobs) tbl(v.size() * sizeof(LinearArgs));
+  // ---------------- device tables: sized now (every buffer still unbound), filled and uploaded at bind; the
+  // same walk builds the point-reduction GEMM groups, whose split-K slabs are carved here
+  TableWalk sizing;
+  walk_tables(p, sizing);
+  p->table_bytes = sizing.cur;
   C.add("slab_wgrad", p->slab_wgrad_floats, 0);
   if (I > 0 && tr) C.add("slab_wgrad2", p->slab_wgrad_floats, 0);   // weight grads on side2
   C.add("slab_state", p->slab_state_floats, 0);
@@ -1507,103 +1579,17 @@ extern "C" int gnot_plan_bind_workspace_async(gnot_plan* p, void* workspace, siz
   if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(GNOT_E_WORKSPACE, "workspace must be 256-byte aligned");
   p->ws = static_cast<char*>(workspace);
   for (auto& kv : p->bufs) kv.second.p = reinterpret_cast<float*>(p->ws + kv.second.off);
-  const int NL = p->NL;
 
-  // ---- tables in the workspace tail
+  // ---- tables in the workspace tail: the walk set_batch sized, now with every buffer bound
   char* tp = p->ws + p->bufs["__tables"].off;
   std::vector<char> host(p->table_bytes, 0);
-  size_t cur = 0;
-  auto put = [&](const void* src, size_t bytes) -> void* {
-    void* dev = tp + cur;
-    if (bytes) std::memcpy(host.data() + cur, src, bytes);
-    cur += ((bytes + 255) / 256) * 256;
-    return dev;
-  };
-  // pack jobs with real pointers
-  float4* packed = reinterpret_cast<float4*>(p->P_("packed"));
-  float* pbias = p->P_("pbias");
-  std::vector<PackJob> jobs = p->pack_jobs;
-  for (size_t k = 0; k < jobs.size(); ++k) {
-    const int li = (int)reinterpret_cast<intptr_t>(jobs[k].W);
-    jobs[k].W = p->W[li];
-    jobs[k].b = p->b[li];
-    jobs[k].dst = packed + p->pack_dst_off4[k];
-    jobs[k].bias_dst = (p->pack_bias_off[k] == (size_t)-1) ? nullptr : pbias + p->pack_bias_off[k];
-  }
-  p->d_pack_jobs = static_cast<PackJob*>(put(jobs.data(), jobs.size() * sizeof(PackJob)));
-  p->d_pack_prefix = static_cast<int*>(put(p->pack_prefix.data(), p->pack_prefix.size() * sizeof(int)));
-  // resolve images
-  auto rimg = [&](Img& im) { im.p = packed + im.off4; };
-  for (auto& im : p->fwd_img) rimg(im);
-  for (auto& im : p->T_img) rimg(im);
-  for (auto* v : {&p->cross_img, &p->self_img})
-    for (auto& A : *v) {
-      rimg(A.qkv); rimg(A.q); rimg(A.o);
-      for (auto& k : A.kv) rimg(k);
-    }
-  // chain tables
-  auto fill_chain = [&](ChainTable& T, const std::vector<int>& firsts) {
-    T.host.clear();
-    for (int f : firsts)
-      for (int j = 0; j < NL; ++j) {
-        const int li = f + j;
-        T.host.push_back(ChainLayer{p->fwd_img[li].p, p->T_img[li].p, pbias + p->fwd_bias[li]});
-      }
-    T.dev = static_cast<ChainLayer*>(put(T.host.data(), T.host.size() * sizeof(ChainLayer)));
-  };
-  fill_chain(p->ch_gate, {p->lin_g(0)});
-  fill_chain(p->ch_x, {p->lin_x(0)});
-  fill_chain(p->ch_out, {p->lin_out(0)});
-  for (int i = 0; i < p->I; ++i) fill_chain(p->ch_fn[i], {p->lin_fn(i, 0)});
-  for (int l = 0; l < p->L; ++l) {
-    std::vector<int> f1, f2;
-    for (int e = 0; e < p->E; ++e) { f1.push_back(p->lin_f1(l, e, 0)); f2.push_back(p->lin_f2(l, e, 0)); }
-    fill_chain(p->ch_m1[l], f1);
-    fill_chain(p->ch_m2[l], f2);
-  }
-  p->d_qchunks = static_cast<int4*>(put(p->qchunks.data(), p->qchunks.size() * sizeof(int4)));
-  p->d_qchunk_off = static_cast<int*>(put(p->qchunk_off.data(), p->qchunk_off.size() * sizeof(int)));
-  p->d_fchunks.assign(p->I, nullptr);
-  p->d_fchunk_off.assign(p->I, nullptr);
-  for (int i = 0; i < p->I; ++i) {
-    p->d_fchunks[i] = static_cast<int4*>(put(p->fchunks[i].data(), p->fchunks[i].size() * sizeof(int4)));
-    p->d_fchunk_off[i] = static_cast<int*>(put(p->fchunk_off[i].data(), p->fchunk_off[i].size() * sizeof(int)));
-  }
-  {
-    std::vector<long> offs(p->xoff);
-    for (int i = 0; i < p->I; ++i) offs.insert(offs.end(), p->fnoff[i].begin(), p->fnoff[i].end());
-    long* d = static_cast<long*>(put(offs.data(), offs.size() * sizeof(long)));
-    p->d_xoff = d;
-    p->d_fnoff.assign(p->I, nullptr);
-    for (int i = 0; i < p->I; ++i) p->d_fnoff[i] = d + (p->B + 1) * (i + 1);
-  }
-  // point-reduction GEMM groups with real pointers
-  {
-    const size_t slab_need = p->slab_wgrad_floats, slab_state_need = p->slab_state_floats;
-    build_groups(p);
-    if (p->slab_wgrad_floats != slab_need || p->slab_state_floats != slab_state_need)
-      return fail(GNOT_E_INVALID, "internal: slab size changed at bind");
-    for_each_group(p, [&](WgradGroup& G) {
-      G.d_jobs = static_cast<WgradJob*>(put(G.jobs.data(), G.jobs.size() * sizeof(WgradJob)));
-      std::vector<int> pre(G.wg_prefix);
-      pre.insert(pre.end(), G.red_prefix.begin(), G.red_prefix.end());
-      int* d = static_cast<int*>(put(pre.data(), pre.size() * sizeof(int)));
-      G.d_wg_prefix = d;
-      G.d_red_prefix = d + G.jobs.size();
-      G.d_segs = G.segs.empty() ? nullptr : static_cast<int4*>(put(G.segs.data(), G.segs.size() * sizeof(int4)));
-      G.d_seg_start = G.segs.empty() ? nullptr : static_cast<int*>(put(G.seg_start.data(), G.seg_start.size() * sizeof(int)));
-    });
-  }
-  build_attn_tables(p);
-  p->d_fwd_kv_jobs = static_cast<LinearArgs*>(put(p->fwd_kv_jobs.data(), p->fwd_kv_jobs.size() * sizeof(LinearArgs)));
-  p->d_kvbwd_jobs = static_cast<AttnKVBwdArgs*>(put(p->kvbwd_jobs.data(), p->kvbwd_jobs.size() * sizeof(AttnKVBwdArgs)));
-  p->d_dfn_jobs.clear();
-  for (auto& v : p->dfn_jobs) p->d_dfn_jobs.push_back(static_cast<LinearArgs*>(put(v.data(), v.size() * sizeof(LinearArgs))));
-  p->d_xsend = static_cast<CopySeg*>(put(p->xsend.data(), p->xsend.size() * sizeof(CopySeg)));
-  p->d_xrecv = static_cast<CopySeg*>(put(p->xrecv.data(), p->xrecv.size() * sizeof(CopySeg)));
-  p->d_xsend_prefix = static_cast<int*>(put(p->xsend_prefix.data(), p->xsend_prefix.size() * sizeof(int)));
-  p->d_xrecv_prefix = static_cast<int*>(put(p->xrecv_prefix.data(), p->xrecv_prefix.size() * sizeof(int)));
-  if (cur > p->table_bytes) return fail(GNOT_E_INVALID, "internal: table overflow");
+  TableWalk fill{host.data(), tp, host.size(), 0};
+  const size_t slab_need = p->slab_wgrad_floats, slab_state_need = p->slab_state_floats;
+  walk_tables(p, fill);
+  if (p->slab_wgrad_floats != slab_need || p->slab_state_floats != slab_state_need)
+    return fail(GNOT_E_INVALID, "internal: slab size changed at bind");
+  if (fill.cur != p->table_bytes) return fail(GNOT_E_INVALID, "internal: table overflow (the walk changed at bind)");
+  const size_t cur = fill.cur;
   {
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int k = p->stage_next;
@@ -1725,12 +1711,38 @@ ChainArgs& cw_scratch(gnot_plan* p, ChainArgs& a, hipStream_t s) {
   return a;
 }
 
-ChainArgs chain_args(gnot_plan* p, const ChainTable& T, long P) {
+// What a launch of chain call C takes from its description: shape, layer tables, mode, the forward's input
+// (X) or the backward's d scores, the gating scores a soft-MoE (and the gating's backward) reads, and the save
+// buffer with its layout.  `save` null: a forward that keeps no pre-activations.  The forward adds Y, the
+// backward dY / dX (and chain_bwd_launch the dZ slot)
+ChainArgs chain_args(gnot_plan* p, const Chain& C, bool bwd, float* save) {
+  const long D = p->D, NL = p->NL;
   ChainArgs a{};
-  a.D = p->D; a.KT0 = T.KT0; a.OTL = T.OTL; a.nlin = p->NL;
-  a.layers_host = T.host.data();
-  a.in_dim = T.in_dim; a.out_dim = T.out_dim; a.P = (int)P; a.nchains = T.nchains; a.layers = T.dev;
+  a.D = p->D; a.KT0 = C.KT0; a.OTL = C.OTL; a.nlin = p->NL;
+  a.layers_host = C.layers.data();
+  a.in_dim = C.in_dim; a.out_dim = C.out_dim; a.P = (int)C.rows; a.nchains = (int)C.firsts.size();
+  a.layers = C.d_layers;
   a.np = p->npk();
+  a.mode = C.mode;
+  if (!bwd) {
+    const Buf& x = p->bufs.at(C.x);
+    a.X = x.p; a.ldx = x.ld;
+  }
+  if (C.mode == CH_MOE || (bwd && C.mode == CH_SOFTMAX)) {
+    a.scores = p->P_("scores"); a.ldsc = (int)p->bufs.at("scores").ld;
+    if (bwd) a.dscore = p->P_("dscore");
+  }
+  a.save = save;
+  if (C.mode == CH_MOE) {
+    // a soft-MoE call's saves (and dZ): fp32 [NL][P][D] per expert, or in bf16 mode 2 NL bf16 layers per
+    // expert (ChainArgs::b16s: bf16 expert terms with or without saves) and bf16 stage rows
+    a.b16s = a.stage_b16 = p->b16s() ? 1 : 0;
+    a.save_layer_stride = a.b16s ? C.rows * D / 2 : C.rows * D;
+    a.save_chain_stride = NL * C.rows * D;
+  } else if (save) {
+    a.save_layer_stride = C.rows * D;
+    a.save_chain_stride = NL * C.rows * D;
+  }
   return a;
 }
 
@@ -1813,6 +1825,21 @@ int grad_allreduce(gnot_plan* p, const WgradGroup& G, hipEvent_t done) {
   return GNOT_OK;
 }
 
+// one weight-gradient group in order on c's stream with split-K slab `slab`, then its gradient all-reduce
+int run_wgrad_here(Ctx& c, const WgradGroup& G, float* slab) {
+  if (G.jobs.empty()) return GNOT_OK;
+  {
+    ProfScope ps(c, G.b16 ? "wgrad_b16" : "wgrad", group_flops(G));
+    GNOT_RUN(launch_group(c.p, G, slab, c.s));
+  }
+  if (c.p->grad_comm_live) {
+    hipEvent_t done = next_event(c.p);
+    GNOT_CK(hipEventRecord(done, c.s));
+    GNOT_RUN(grad_allreduce(c.p, G, done));
+  }
+  return GNOT_OK;
+}
+
 // weight gradients: on the caller's stream (plans of >= 65,536 points), or forked onto the side stream;
 // `reads` are the main-stream buffers the group consumes, guarded until it finishes
 int run_wgrad_side(Ctx& c, const WgradGroup& G, std::initializer_list<const float*> reads) {
@@ -1830,19 +1857,7 @@ int run_wgrad_side(Ctx& c, const WgradGroup& G, std::initializer_list<const floa
   // gradients therefore run in order on side2 with their own slab: they are the input-function
   // encoders' and the cross K/V Linears' (M ~ 10^3 points: tens of microseconds).  DESIGN.md
   // "capture fault".
-  if (serial || c.s == p->side2) {
-    float* slab = c.s == p->side2 ? p->P_("slab_wgrad2") : p->P_("slab_wgrad");
-    {
-      ProfScope ps(c, G.b16 ? "wgrad_b16" : "wgrad", group_flops(G));
-      GNOT_RUN(launch_group(c.p, G, slab, c.s));
-    }
-    if (p->grad_comm_live) {
-      hipEvent_t done = next_event(p);
-      GNOT_CK(hipEventRecord(done, c.s));
-      GNOT_RUN(grad_allreduce(p, G, done));
-    }
-    return GNOT_OK;
-  }
+  if (serial || c.s == p->side2) return run_wgrad_here(c, G, p->P_(c.s == p->side2 ? "slab_wgrad2" : "slab_wgrad"));
   // forked: the side stream waits for what the caller's stream has issued so far (the fork event is
   // recorded now), but its launches are captured only after the caller's NEXT kernel (flush_deferred).  A
   // captured graph keeps a node's first-captured child on the node's own hardware queue; with the side
@@ -1904,6 +1919,13 @@ int shard_exchange(Ctx& c, float* hm, float* tok, bool reverse) {
   return GNOT_OK;
 }
 
+// what every attention apply pass over the query points takes: their segments and the head geometry
+AttnApplyArgs apply_args(const gnot_plan* p) {
+  AttnApplyArgs ap{};
+  ap.chunks = p->d_qchunks; ap.nchunks = (int)p->qchunks.size(); ap.off = p->d_xoff;
+  ap.H = p->H; ap.dh = p->dh; ap.dhr = p->head_padded() ? p->dhr : 0;
+  return ap;
+}
 
 // one LinearAttention call (model.py:53-107). q_in: the query rows [P, D].
 int attn_forward(Ctx& c, int l, bool cross, const float* q_in, float* res_out, float* out) {
@@ -1913,29 +1935,23 @@ int attn_forward(Ctx& c, int l, bool cross, const float* q_in, float* res_out, f
   const std::string s = "b" + std::to_string(l) + ".";
   const gnot_plan::AttnImgs& A = cross ? p->cross_img[l] : p->self_img[l];
   float* pbias = p->P_("pbias");
-  const int nq = (int)p->qchunks.size();
+  AttnApplyArgs ap = apply_args(p);
+  ap.res = p->sharded ? p->P_("xb") : res_out;
   if (cross && p->I > 0) {
     float* q = p->P_(s + "cq");
     GNOT_RUN(run_linear(c, q_in, D, D, A.q, pbias + A.bq, q, D, D, P, EPI_STORE, D));
-    AttnApplyArgs ap{};
     // keys/values/states of the input functions were computed for every block up front
     for (int i = 0; i < p->I; ++i) ap.state[i] = p->P_(s + "cstate" + std::to_string(i));
-    ap.q = q; ap.ldq = D; ap.nsrc = p->I; ap.chunks = p->d_qchunks; ap.nchunks = nq; ap.off = p->d_xoff;
-    ap.H = p->H; ap.dh = p->dh; ap.res = p->sharded ? p->P_("xb") : res_out;
-    ap.dhr = p->head_padded() ? p->dhr : 0;
-    GNOT_CK(launch_attn_apply_fwd(ap, c.s));
+    ap.q = q; ap.ldq = D; ap.nsrc = p->I;
   } else {
     float* qkv = p->P_(cross ? s + "cq" : s + "sq");
     GNOT_RUN(run_linear(c, q_in, D, D, A.qkv, pbias + A.bqkv, qkv, 3 * D, 3 * D, P, EPI_STORE, 2 * D));
     float* st = p->P_(cross ? s + "cstate0" : s + "sstate");
     GNOT_RUN(run_state(c, cross ? p->st_c[l][0] : p->st_s[l]));
-    GNOT_RUN(shard_allreduce(c, st, (long)p->B * p->H * (p->dh * p->dh + p->dh)));   // S, z over all ranks
-    AttnApplyArgs ap{};
-    ap.q = qkv; ap.ldq = 3 * D; ap.nsrc = 1; ap.state[0] = st; ap.chunks = p->d_qchunks; ap.nchunks = nq;
-    ap.off = p->d_xoff; ap.H = p->H; ap.dh = p->dh; ap.res = p->sharded ? p->P_("xb") : res_out;
-    ap.dhr = p->head_padded() ? p->dhr : 0;
-    GNOT_CK(launch_attn_apply_fwd(ap, c.s));
+    GNOT_RUN(shard_allreduce(c, st, p->B * p->per_state()));   // S, z over all ranks
+    ap.q = qkv; ap.ldq = 3 * D; ap.nsrc = 1; ap.state[0] = st;
   }
+  GNOT_CK(launch_attn_apply_fwd(ap, c.s));
   if (p->sharded) GNOT_RUN(shard_exchange(c, p->P_("xb"), res_out, false));   // the scramble, across ranks
   // fc_out over the scramble rows: Dr columns per token (the head-major apply output viewed as rows of
   // H * dh = Dr floats, model.py:81-83), read zero-filled to the padded width
@@ -1956,7 +1972,6 @@ int attn_backward(Ctx& c, int l, bool cross) {
   float* dres = p->P_("dres");
   float* dquery = p->P_("dquery");
   float* dqkv = p->P_(p->dqkv_buf(cross));
-  const int nq = (int)p->qchunks.size();
   GNOT_RUN(guard_write(c, dqkv));
   // fc_out backward-data: dres = dout W_o (token order); sharded: back to this rank's head-major rows
   GNOT_RUN(run_linear(c, dsum, D, D, p->T_img[lo], nullptr, dres, p->Dr, D, P, EPI_STORE, 0, p->Dr));
@@ -1964,12 +1979,10 @@ int attn_backward(Ctx& c, int l, bool cross) {
     GNOT_RUN(shard_exchange(c, p->P_("xb"), dres, true));
     dres = p->P_("xb");
   }
+  AttnApplyArgs ap = apply_args(p);
+  ap.dres = dres; ap.dq_pre = dqkv; ap.lddu = D;
   if (cross && p->I > 0) {
-    const float* q = p->P_(s + "cq");
-    AttnApplyArgs ap{};
-    ap.q = q; ap.ldq = D; ap.nsrc = p->I; ap.chunks = p->d_qchunks; ap.nchunks = nq; ap.off = p->d_xoff;
-    ap.H = p->H; ap.dh = p->dh; ap.dres = dres; ap.dq_pre = dqkv; ap.lddq = D; ap.lddu = D;
-    ap.dhr = p->head_padded() ? p->dhr : 0;
+    ap.q = p->P_(s + "cq"); ap.ldq = D; ap.nsrc = p->I; ap.lddq = D;
     for (int i = 0; i < p->I; ++i) {
       const std::string si = std::to_string(i);
       ap.state[i] = p->P_(s + "cstate" + si);
@@ -1985,19 +1998,15 @@ int attn_backward(Ctx& c, int l, bool cross) {
     const float* qkv = p->P_(cross ? s + "cq" : s + "sq");
     const int lk = cross ? p->lin_ck(l, 0) : p->lin_sk(l);
     const int lv = cross ? p->lin_cv(l, 0) : p->lin_sv(l);
-    AttnApplyArgs ap{};
     ap.q = qkv; ap.ldq = 3 * D; ap.nsrc = 1; ap.state[0] = p->P_(cross ? s + "cstate0" : s + "sstate");
-    ap.chunks = p->d_qchunks; ap.nchunks = nq; ap.off = p->d_xoff; ap.H = p->H; ap.dh = p->dh;
-    ap.dres = dres; ap.dq_pre = dqkv; ap.lddq = 3 * D; ap.du[0] = p->P_("du0"); ap.lddu = D;
-    ap.dden[0] = p->P_("dden0");
-    ap.dhr = p->head_padded() ? p->dhr : 0;
+    ap.lddq = 3 * D; ap.du[0] = p->P_("du0"); ap.dden[0] = p->P_("dden0");
     GNOT_CK(launch_attn_apply_bwd(ap, c.s));
     float* dst = p->P_("dstate0");
     GNOT_RUN(run_state(c, cross ? p->dst_c[l][0] : p->dst_s[l]));
-    GNOT_RUN(shard_allreduce(c, dst, (long)p->B * p->H * (p->dh * p->dh + p->dh)));   // dS, dz over all ranks
+    GNOT_RUN(shard_allreduce(c, dst, p->B * p->per_state()));   // dS, dz over all ranks
     AttnKVBwdArgs kb{};
-    kb.k = qkv + D; kb.v = qkv + 2 * D; kb.ldkv = 3 * D; kb.dstate = dst; kb.chunks = p->d_qchunks;
-    kb.nchunks = nq; kb.H = p->H; kb.dh = p->dh; kb.dk = dqkv + D; kb.dv = dqkv + 2 * D; kb.lddkv = 3 * D;
+    kb.k = qkv + D; kb.v = qkv + 2 * D; kb.ldkv = 3 * D; kb.dstate = dst; kb.chunks = ap.chunks;
+    kb.nchunks = ap.nchunks; kb.H = p->H; kb.dh = p->dh; kb.dk = dqkv + D; kb.dv = dqkv + 2 * D; kb.lddkv = 3 * D;
     GNOT_CK(launch_attn_kv_bwd(kb, c.s));
     GNOT_RUN(run_linear_seg(c, {{dqkv, &p->T_img[lq]}, {dqkv + D, &p->T_img[lk]}, {dqkv + 2 * D, &p->T_img[lv]}},
                             3 * D, dquery, D, P, EPI_ACCUM));
@@ -2011,7 +2020,6 @@ int attn_backward(Ctx& c, int l, bool cross) {
 // the soft-MoE experts of one call: the expert grid writes the [E, P, d] stage (bf16 mode at d = 256: bf16
 // stage rows), a moe_combine pass sums residual + experts in expert order (chain2.hip names the forms that
 // were measured slower and removed)
-static bool moe_stage_b16(gnot_plan* p) { return p->b16s(); }
 // stage_stride: floats between two experts' stage rows (the stage buffer's P * D; the bf16 training forward's
 // stage rows are its save slot nl-1, one save chain apart)
 static hipError_t launch_moe_pass(gnot_plan* p, const float* base, const float* stage, float* out, hipStream_t s,
@@ -2021,24 +2029,14 @@ static hipError_t launch_moe_pass(gnot_plan* p, const float* base, const float* 
   return p->b16s() ? launch_moe_combine_b16(base, stage, stage_stride, p->E, out, P, s)
                    : launch_moe_combine(base, stage, stage_stride, p->E, out, P * D, s);
 }
-// save (and dZ) layout of a soft-MoE chain call: fp32 [NL][P][D] per expert, or in bf16 mode 2 NL bf16
-// layers per expert (ChainArgs::b16s)
-static void moe_save_strides(gnot_plan* p, ChainArgs& a) {
-  const long P = p->P, D = p->D, NL = p->NL;
-  a.b16s = p->b16s() ? 1 : 0;
-  a.save_layer_stride = a.b16s ? P * D / 2 : P * D;
-  a.save_chain_stride = NL * P * D;
-}
 
-static int moe_forward(Ctx& c, const ChainTable& T, const float* in, const float* qin, float* qout, float* save) {
+// qout = qin + sum_e s_e ffn_e(C's input); save: the call's saves, or null (inference, MoE recompute)
+static int moe_forward(Ctx& c, const Chain& C, const float* qin, float* qout, float* save) {
   gnot_plan* p = c.p;
   const long P = p->P;
   const int D = p->D, E = p->E, NL = p->NL;
-  ChainArgs a = chain_args(p, T, P);
-  a.X = in; a.ldx = D; a.ldy = D;
-  a.scores = p->P_("scores"); a.ldsc = (int)p->bufs["scores"].ld; a.mode = CH_MOE;
-  moe_save_strides(p, a);                 // bf16 mode: bf16 expert terms with or without saves
-  a.save = save;
+  ChainArgs a = chain_args(p, C, false, save);
+  a.ldy = D;
   a.Y = p->P_("stage"); a.y_chain_stride = P * D;
   if (p->b16s() && save) {
     // bf16 training: the experts' bf16 score-scaled terms are kept in save slot nl-1 (the backward's d score
@@ -2046,7 +2044,6 @@ static int moe_forward(Ctx& c, const ChainTable& T, const float* in, const float
     a.Y = save + (NL - 1) * a.save_layer_stride;
     a.y_chain_stride = a.save_chain_stride;
   }
-  a.stage_b16 = moe_stage_b16(p) ? 1 : 0;
   {
     ProfScope ps(c, "moe_fwd", 2.0 * E * P * NL * (double)D * D);
     GNOT_CK(launch_chain_fwd(cw_scratch(p, a, c.s), c.s));
@@ -2101,7 +2098,7 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   if (!x || !theta || !out || (p->I > 0 && !fns)) return fail(GNOT_E_INVALID, "null input");
   Ctx c{p, static_cast<hipStream_t>(stream)};
   const long P = p->P;
-  const int D = p->D, NL = p->NL;
+  const int D = p->D;
   const bool tr = p->training;
   // the input-function branch (encoders, every block's K/V projections and states) depends only on
   // the input functions: it runs on side2 while the query branch (gating, x encoder) runs here.  The
@@ -2118,22 +2115,16 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   GNOT_CK(hipMemcpyAsync(p->P_("theta"), theta, (size_t)p->B * p->th * 4, hipMemcpyDeviceToDevice, c.s));
   GNOT_CK(launch_concat_theta(p->P_("x"), p->bufs["x"].ld, p->in, p->P_("theta"), p->th, p->d_xoff, p->B,
                               p->P_("xin"), p->bufs["xin"].ld, (int)P, c.s));
-  // gating (model.py:155-156)
-  {
-    ChainArgs a = chain_args(p, p->ch_gate, P);
-    a.X = p->P_("x"); a.ldx = p->bufs["x"].ld;
-    a.Y = p->P_("scores"); a.ldy = p->bufs["scores"].ld; a.mode = CH_SOFTMAX;
-    if (tr) { a.save = p->P_("gate_save"); a.save_layer_stride = P * D; a.save_chain_stride = NL * P * D; }
-    GNOT_CK(launch_chain_fwd(cw_scratch(p, a, c.s), c.s));
-  }
-  // query encoder (model.py:158-161)
-  {
-    ChainArgs a = chain_args(p, p->ch_x, P);
-    a.X = p->P_("xin"); a.ldx = p->bufs["xin"].ld;
-    a.Y = p->P_("query0"); a.ldy = D; a.mode = CH_STORE;
-    if (tr) { a.save = p->P_("x_save"); a.save_layer_stride = P * D; a.save_chain_stride = NL * P * D; }
-    GNOT_CK(launch_chain_fwd(cw_scratch(p, a, c.s), c.s));
-  }
+  // one encoder / decoder chain: C's input -> Y, keeping the pre-activations when training
+  auto chain_fwd = [&](Ctx& cc, const Chain& C, float* Y, long ldy) -> int {
+    ChainArgs a = chain_args(p, C, false, tr ? p->P_(C.save) : nullptr);
+    a.Y = Y; a.ldy = ldy;
+    GNOT_CK(launch_chain_fwd(cw_scratch(p, a, cc.s), cc.s));
+    return GNOT_OK;
+  };
+  // gating (model.py:155-156) and query encoder (model.py:158-161)
+  GNOT_RUN(chain_fwd(c, p->ch_gate(), p->P_("scores"), p->bufs["scores"].ld));
+  GNOT_RUN(chain_fwd(c, p->ch_x(), p->P_("query0"), D));
   for (int i = 0; i < p->I; ++i) {
     const std::string n = "fn" + std::to_string(i);
     if (p->Q[i] > 0)
@@ -2141,21 +2132,12 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
                                hipMemcpyDeviceToDevice, cf.s));
   }
   // input-function encoders (model.py:164-166)
-  for (int i = 0; i < p->I; ++i) {
-    const std::string si = std::to_string(i);
-    ChainArgs a = chain_args(p, p->ch_fn[i], p->Q[i]);
-    a.X = p->P_("fn" + si); a.ldx = p->bufs["fn" + si].ld;
-    a.Y = p->P_("fnenc" + si); a.ldy = D; a.mode = CH_STORE;
-    if (tr) { a.save = p->P_("fn_save" + si); a.save_layer_stride = p->Q[i] * D; a.save_chain_stride = NL * p->Q[i] * D; }
-    GNOT_CK(launch_chain_fwd(cw_scratch(p, a, cf.s), cf.s));
-  }
+  for (int i = 0; i < p->I; ++i) GNOT_RUN(chain_fwd(cf, p->ch_fn(i), p->P_("fnenc" + std::to_string(i)), D));
   // key/value projections (model.py:67-75) and states (model.py:77-79) of every (block, input
   // function): they depend only on the input-function encodings, so all L*I of them run batched here
   if (p->I > 0 && p->L > 0) {
-    long Qmax = 0;
-    for (long q : p->Q) Qmax = std::max(Qmax, q);
-    GNOT_CK(launch_linear_batch(p->d_fwd_kv_jobs, (int)p->fwd_kv_jobs.size(), (int)Qmax, 2 * D, D > 512 ? D / 2 : D,
-                                p->dh, cf.s));
+    GNOT_CK(launch_linear_batch(p->d_fwd_kv_jobs, (int)p->fwd_kv_jobs.size(), (int)p->Qmax(), 2 * D,
+                                D > 512 ? D / 2 : D, p->dh, cf.s));
     GNOT_RUN(run_state(cf, p->st_fn));
   }
   if (br) {                                // join the input-function branch
@@ -2169,20 +2151,15 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
     const float* qin = p->P_(p->block_query(l));
     GNOT_RUN(attn_forward(c, l, true, qin, p->P_(s + "cres"), p->P_(s + "a")));
     // ffn1 experts: query1 = query + sum_e s_e ffn1_e(a)   (model.py:128-131)
-    GNOT_RUN(moe_forward(c, p->ch_m1[l], p->P_(s + "a"), qin, p->P_(s + "query1"),
-                         tr && !p->moe_recompute ? p->P_(s + "m1save") : nullptr));
+    const bool keep = tr && !p->moe_recompute;   // recompute: the backward re-runs the call into "mrsave"
+    const Chain &m1 = p->ch_moe(l, true), &m2 = p->ch_moe(l, false);
+    GNOT_RUN(moe_forward(c, m1, qin, p->P_(s + "query1"), keep ? p->P_(m1.save) : nullptr));
     GNOT_RUN(attn_forward(c, l, false, p->P_(s + "query1"), p->P_(s + "sres"), p->P_(s + "bb")));
     // ffn2 experts: query2 = query1 + sum_e s_e ffn2_e(bb)   (model.py:134-137)
-    GNOT_RUN(moe_forward(c, p->ch_m2[l], p->P_(s + "bb"), p->P_(s + "query1"), p->P_(s + "query2"),
-                         tr && !p->moe_recompute ? p->P_(s + "m2save") : nullptr));
+    GNOT_RUN(moe_forward(c, m2, p->P_(s + "query1"), p->P_(s + "query2"), keep ? p->P_(m2.save) : nullptr));
   }
   // decoder (model.py:171)
-  {
-    ChainArgs a = chain_args(p, p->ch_out, P);
-    a.X = p->P_(p->final_query()); a.ldx = D; a.Y = out; a.ldy = p->out; a.mode = CH_STORE;
-    if (tr) { a.save = p->P_("out_save"); a.save_layer_stride = P * D; a.save_chain_stride = NL * P * D; }
-    GNOT_CK(launch_chain_fwd(cw_scratch(p, a, c.s), c.s));
-  }
+  GNOT_RUN(chain_fwd(c, p->ch_out(), out, p->out));
   p->fwd_done = true;
   p->bwd_done = false;
   return GNOT_OK;
@@ -2210,67 +2187,66 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
   GNOT_CK(hipMemcpy2DAsync(p->P_("dout"), p->bufs["dout"].ld * 4, dout, p->out * 4, p->out * 4, P,
                            hipMemcpyDeviceToDevice, c.s));
   GNOT_CK(hipMemsetAsync(p->P_("dscore"), 0, P * p->bufs["dscore"].ld * 4, c.s));
-  // one chain backward: dZ of every Linear into the chain call's dz slot, then its weight gradients
-  // are forked to the side stream
-  auto chain_bwd_on = [&](Ctx& cc, ChainArgs& a, int kcall, long rows, const WgradGroup& G, const char* prof) -> int {
-    float* dz = p->P_(p->dz_name(kcall));
+  // the backward's ChainArgs of call site C: the saves of its forward, the incoming gradient dY and, where
+  // asked for (dxbuf: a buffer's name), the gradient of its input
+  auto bwd_args = [&](const Chain& C, const float* dY, long lddy, const std::string& dxbuf = std::string()) {
+    ChainArgs a = chain_args(p, C, true, p->P_(C.save));
+    a.dY = dY; a.lddy = lddy;
+    if (!dxbuf.empty()) { a.dX = p->P_(dxbuf); a.lddx = p->bufs.at(dxbuf).ld; a.dx_chain_stride = 0; }
+    return a;
+  };
+  // launch one chain backward: dZ of every Linear into the chain call's dz slot
+  auto chain_bwd_launch = [&](Ctx& cc, const Chain& C, ChainArgs& a, const char* prof) -> int {
+    float* dz = p->P_(p->dz_name(C.kcall));
     GNOT_RUN(guard_write(cc, dz));
-    a.dz = dz; a.dz_layer_stride = rows * D; a.dz_chain_stride = NL * rows * D;
+    a.dz = dz; a.dz_layer_stride = C.rows * D; a.dz_chain_stride = NL * C.rows * D;
     if (a.b16s) { a.dz_layer_stride /= 2; a.dz_chain_stride /= 2; }   // bf16 dZ layers
     {
-      ProfScope ps(cc, prof, 2.0 * a.nchains * rows * NL * (double)D * D);
+      ProfScope ps(cc, prof, 2.0 * a.nchains * C.rows * NL * (double)D * D);
       GNOT_CK(launch_chain_bwd(cw_scratch(p, a, cc.s), cc.s));
     }
     if (cc.s == c.s) GNOT_RUN(flush_deferred(cc));   // earlier groups' side launches after this kernel
+    return GNOT_OK;
+  };
+  // ... and dispatch its weight gradients: in order, or forked to the side stream
+  auto chain_bwd = [&](Ctx& cc, const Chain& C, ChainArgs& a, const char* prof) -> int {
+    GNOT_RUN(chain_bwd_launch(cc, C, a, prof));
     // the weight gradients read the saved pre-activations too: a recomputed (shared) save buffer
     // must not be overwritten by the next MoE's recompute before they finish.  That guard is the
     // readers map, which only run_wgrad_side from the capture-origin stream registers (side2 runs its
     // groups in order without it): the MoE chains must therefore stay on the origin stream
     if (p->moe_recompute && a.mode == CH_MOE) {
       if (cc.s != c.s) return fail(GNOT_E_STATE, "internal: MoE recompute backward off the origin stream");
-      return run_wgrad_side(cc, G, {dz, a.save});
+      return run_wgrad_side(cc, C.wg, {a.dz, a.save});
     }
-    return run_wgrad_side(cc, G, {dz});
-  };
-  auto chain_bwd = [&](ChainArgs& a, int kcall, long rows, const WgradGroup& G, const char* prof) -> int {
-    return chain_bwd_on(c, a, kcall, rows, G, prof);
+    return run_wgrad_side(cc, C.wg, {a.dz});
   };
   // decoder (model.py:171)
   {
-    ChainArgs a = chain_args(p, p->ch_out, P);
-    a.dY = p->P_("dout"); a.lddy = p->bufs["dout"].ld; a.mode = CH_STORE;
-    a.save = p->P_("out_save"); a.save_layer_stride = P * D; a.save_chain_stride = NL * P * D;
-    a.dX = dquery; a.lddx = D; a.dx_chain_stride = 0;
-    GNOT_RUN(chain_bwd(a, p->k_out(), P, p->wg_out, "chain_bwd"));
+    ChainArgs a = bwd_args(p->ch_out(), p->P_("dout"), p->bufs["dout"].ld, "dquery");
+    GNOT_RUN(chain_bwd(c, p->ch_out(), a, "chain_bwd"));
   }
   for (int l = p->L - 1; l >= 0; --l) {
-    const std::string s = "b" + std::to_string(l) + ".";
     // ffn2 experts: query2 = query1 + sum_e s_e ffn2_e(bb)   (model.py:134-137)
     for (int m = 2; m >= 1; --m) {
       const bool m1 = (m == 1);
+      const Chain& C = p->ch_moe(l, m1);
       if (p->moe_recompute) {
         // re-run this call's expert forward (inputs kept: "a" / "bb") into the shared save buffer
-        float* mr = p->P_("mrsave");
+        float* mr = p->P_(C.save);
         GNOT_RUN(guard_write(c, mr));
-        ChainArgs f = chain_args(p, m1 ? p->ch_m1[l] : p->ch_m2[l], P);
-        f.X = p->P_(s + (m1 ? "a" : "bb")); f.ldx = D; f.ldy = D;
-        f.scores = p->P_("scores"); f.ldsc = (int)p->bufs["scores"].ld; f.mode = CH_MOE;
-        f.save = mr; moe_save_strides(p, f);
+        ChainArgs f = chain_args(p, C, false, mr);
         // only the saves are needed: no output (Y = null), no combine
-        f.Y = nullptr; f.y_chain_stride = P * D;
+        f.ldy = D; f.Y = nullptr; f.y_chain_stride = P * D;
         ProfScope ps(c, "moe_recompute", 2.0 * E * P * NL * (double)D * D);
         GNOT_CK(launch_chain_fwd(cw_scratch(p, f, c.s), c.s));
       }
-      ChainArgs a = chain_args(p, m1 ? p->ch_m1[l] : p->ch_m2[l], P);
-      a.dY = dquery; a.lddy = D; a.mode = CH_MOE;
-      a.scores = p->P_("scores"); a.ldsc = (int)p->bufs["scores"].ld; a.dscore = p->P_("dscore");
-      a.save = p->P_(p->msave(l, m1)); moe_save_strides(p, a);
+      ChainArgs a = bwd_args(C, dquery, D);
       float* dsum = p->P_(p->dsum_buf(m1));
       // d(MoE input) = sum_e W_e0^T dz_e0: each expert's term into the stage, summed by moe_combine
       GNOT_RUN(guard_write(c, dsum));
       a.dX = stage; a.lddx = D; a.dx_chain_stride = P * D;
-      a.stage_b16 = moe_stage_b16(p) ? 1 : 0;
-      GNOT_RUN(chain_bwd(a, m1 ? p->k_m1(l) : p->k_m2(l), P, m1 ? p->wg_m1[l] : p->wg_m2[l], "moe_bwd"));
+      GNOT_RUN(chain_bwd(c, C, a, "moe_bwd"));
       GNOT_CK(launch_moe_pass(p, nullptr, stage, dsum, c.s));
       GNOT_RUN(flush_deferred(c));            // the chain's weight gradients: side launch after the pass
       // m2: self attention (model.py:133) ; m1: cross attention (model.py:127)
@@ -2292,15 +2268,11 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
   // dK, dV of every (block, input function), the encodings' gradient and the key/value weight
   // gradients, batched over blocks
   if (p->I > 0 && p->L > 0) {
-    long Qmax = 0;
     int maxch = 0;
-    for (int i = 0; i < p->I; ++i) {
-      Qmax = std::max(Qmax, p->Q[i]);
-      maxch = std::max(maxch, (int)p->fchunks[i].size());
-    }
+    for (int i = 0; i < p->I; ++i) maxch = std::max(maxch, (int)p->fchunks[i].size());
     GNOT_CK(launch_attn_kv_bwd_batch(p->d_kvbwd_jobs, (int)p->kvbwd_jobs.size(), maxch, p->H, p->dh, cf.s));
     for (size_t k = 0; k < p->d_dfn_jobs.size(); ++k)
-      GNOT_CK(launch_linear_batch(p->d_dfn_jobs[k], p->I, (int)Qmax, D, D > 512 ? D / 2 : D, p->dh, cf.s));
+      GNOT_CK(launch_linear_batch(p->d_dfn_jobs[k], p->I, (int)p->Qmax(), D, D > 512 ? D / 2 : D, p->dh, cf.s));
     GNOT_RUN(run_wgrad_side(cf, p->wg_fnkv, {}));
   }
   if (p->I > 0 && p->L == 0)   // encodings unused by the output: zero gradients
@@ -2309,19 +2281,13 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
   // input-function encoders (their inputs need no gradient)
   for (int i = 0; i < p->I; ++i) {
     const std::string si = std::to_string(i);
-    ChainArgs a = chain_args(p, p->ch_fn[i], p->Q[i]);
-    a.dY = p->P_("dfn" + si); a.lddy = D; a.mode = CH_STORE;
-    a.save = p->P_("fn_save" + si); a.save_layer_stride = p->Q[i] * D; a.save_chain_stride = NL * p->Q[i] * D;
-    if (p->input_grads) { a.dX = p->P_("dfnin" + si); a.lddx = p->bufs["dfnin" + si].ld; a.dx_chain_stride = 0; }
-    GNOT_RUN(chain_bwd_on(cf, a, p->k_fn(i), p->Q[i], p->wg_fn[i], "chain_bwd"));
+    ChainArgs a = bwd_args(p->ch_fn(i), p->P_("dfn" + si), D, p->input_grads ? "dfnin" + si : std::string());
+    GNOT_RUN(chain_bwd(cf, p->ch_fn(i), a, "chain_bwd"));
   }
   // query encoder
   {
-    ChainArgs a = chain_args(p, p->ch_x, P);
-    a.dY = dquery; a.lddy = D; a.mode = CH_STORE;
-    a.save = p->P_("x_save"); a.save_layer_stride = P * D; a.save_chain_stride = NL * P * D;
-    if (p->input_grads) { a.dX = p->P_("dxin"); a.lddx = p->bufs["dxin"].ld; a.dx_chain_stride = 0; }
-    GNOT_RUN(chain_bwd(a, p->k_x(), P, p->wg_x, "chain_bwd"));
+    ChainArgs a = bwd_args(p->ch_x(), dquery, D, p->input_grads ? "dxin" : "");
+    GNOT_RUN(chain_bwd(c, p->ch_x(), a, "chain_bwd"));
   }
   // gating: d scores accumulated over every MoE above -> softmax backward -> chain.  With the weight
   // gradients forked and an input-function branch, the gating's own group runs HERE after the branch has
@@ -2329,40 +2295,18 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
   // side stream and ended the step ~45 us later (configs[1] trace); its all-reduce keeps its place, last
   const bool gate_here = br && !p->serial_wgrad();
   {
-    ChainArgs a = chain_args(p, p->ch_gate, P);
-    a.mode = CH_SOFTMAX; a.scores = p->P_("scores"); a.ldsc = (int)p->bufs["scores"].ld;
-    a.dscore = p->P_("dscore");
-    a.save = p->P_("gate_save"); a.save_layer_stride = P * D; a.save_chain_stride = NL * P * D;
-    if (p->input_grads) { a.dX = p->P_("dxg"); a.lddx = p->bufs["dxg"].ld; a.dx_chain_stride = 0; }
-    if (gate_here) {
-      float* dz = p->P_(p->dz_name(p->k_gate()));
-      GNOT_RUN(guard_write(c, dz));
-      a.dz = dz; a.dz_layer_stride = P * D; a.dz_chain_stride = NL * P * D;
-      {
-        ProfScope ps(c, "chain_bwd", 2.0 * a.nchains * P * NL * (double)D * D);
-        GNOT_CK(launch_chain_bwd(cw_scratch(p, a, c.s), c.s));
-      }
-      GNOT_RUN(flush_deferred(c));           // the query encoder's group: side launch after this kernel
-    } else {
-      GNOT_RUN(chain_bwd(a, p->k_gate(), P, p->wg_gate, "chain_bwd"));
-    }
+    // (its incoming gradient is dscore, no dY)
+    ChainArgs a = bwd_args(p->ch_gate(), nullptr, 0, p->input_grads ? "dxg" : "");
+    // gate_here: the launch alone (its flush is the query encoder's group: side launch after this kernel)
+    if (gate_here) GNOT_RUN(chain_bwd_launch(c, p->ch_gate(), a, "chain_bwd"));
+    else GNOT_RUN(chain_bwd(c, p->ch_gate(), a, "chain_bwd"));
   }
   if (br) {                                // join the input-function branch
     hipEvent_t joinf = next_event(p);
     GNOT_CK(hipEventRecord(joinf, cf.s));
     GNOT_CK(hipStreamWaitEvent(c.s, joinf, 0));
   }
-  if (gate_here && !p->wg_gate.jobs.empty()) {
-    {
-      ProfScope ps(c, "wgrad", group_flops(p->wg_gate));
-      GNOT_RUN(launch_group(p, p->wg_gate, p->P_("slab_wgrad2"), c.s));
-    }
-    if (p->grad_comm_live) {
-      hipEvent_t done = next_event(p);
-      GNOT_CK(hipEventRecord(done, c.s));
-      GNOT_RUN(grad_allreduce(p, p->wg_gate, done));
-    }
-  }
+  if (gate_here) GNOT_RUN(run_wgrad_here(c, p->ch_gate().wg, p->P_("slab_wgrad2")));
   GNOT_RUN(flush_deferred(c));
   // join the side stream: every gradient is complete when the caller's stream moves on
   hipEvent_t join = next_event(p);

@@ -8,7 +8,9 @@
 
 Each case runs one training forward + backward (sum(out * G)) and stores the output and the flat gradient
 arena: d = 256 / E = 8 (configs[2]'s widths) in fp32, bf16 mode and with MoE recompute, d = 128 / E = 4 /
-two input functions (configs[1]'s) in fp32 and bf16 mode, and d = 64 (chain.hip).  Then the training step
+two input functions (configs[1]'s) in fp32 and bf16 mode, d = 64 (chain.hip; once more with x.requires_grad_(),
+storing x.grad), and five widths of tests/test_gpu_widths.py (WIDTH_CASES).  Every case also stores the packed
+weight images and biases as they lie in the workspace (layout and content).  Then the training step
 (tests/train_step_util.py step_replay): every AdamW entry, both norm entries and both losses at n = 1, 257, 8195
 and 524291.  `record` writes the inputs and results of the first three sizes as the fixture of
 tests/test_gpu_train_bits.py.
@@ -29,7 +31,28 @@ CASES = [
     ("d128_fp32", (2, 1, 3, 1, 2, 128, 4, 4, 8, 2), 10000, "fp32", False),
     ("d128_bf16", (2, 1, 3, 1, 2, 128, 4, 4, 8, 2), 10000, "bf16", False),
     ("d64_fp32", (2, 1, 3, 2, 2, 64, 3, 3, 4, 1), 3000, "fp32", False),
+    ("d64_xgrad", (2, 1, 3, 2, 2, 64, 3, 3, 4, 1), 3000, "fp32", False),   # x.requires_grad_(): x.grad is stored too
 ]
+# tests/test_gpu_widths.py CASES at that file's point counts: the narrowest width, no input functions, padded
+# heads, chainw.hip and the K-split tables
+WIDTH_CASES = ["d16_h4", "d80_h5", "d100_h4", "d320_h10", "d576_h9"]
+WIDTH_POINTS, WIDTH_FN_POINTS = [300, 173], [[120, 77], [64, 31]]
+
+
+def _offsets(counts):
+    return [0] + [sum(counts[: k + 1]) for k in range(len(counts))]
+
+
+def _cases():
+    """name, model arguments, x offsets, offsets per input function, precision, recompute"""
+    for name, args, P, prec, rec in CASES:
+        yield name, args, [0, P // 3, P], [[0, 200, 500]] * args[-1], prec, rec
+    from test_gpu_widths import CASES as W
+    for name in WIDTH_CASES:
+        c = W[name]
+        args = (c["input_dim"], c["theta_dim"], c["input_func_dim"], c["out_dim"], c["n_attn_layers"], c["d"],
+                c["n_mlp_num_layers"], c["n_expert"], c["n_head"], c["n_input_functions"])
+        yield name, args, _offsets(WIDTH_POINTS), [_offsets(m) for m in WIDTH_FN_POINTS[: args[-1]]], "fp32", False
 
 
 def dump(path):
@@ -37,22 +60,30 @@ def dump(path):
     from gnot_amd import GNOT
     dev = torch.device("cuda")
     res = {}
-    for name, (i, t, f, o, L, d, nl, E, H, I), P, prec, rec in CASES:
+    for name, (i, t, f, o, L, d, nl, E, H, I), x_off, fn_offs, prec, rec in _cases():
         torch.manual_seed(5)
         m = GNOT(i, t, f, o, L, d, nl, d, d, E, H, I).to(dev)
         m.set_precision(prec)
         m.set_moe_recompute(rec)
         g = torch.Generator(device="cpu").manual_seed(6)
-        x_off = [0, P // 3, P]
+        P = x_off[-1]
         x = torch.rand(P, i, generator=g).to(dev)
-        th = torch.rand(2, t, generator=g).to(dev)
-        fns = [torch.rand(500, f, generator=g).to(dev) for _ in range(I)]
+        if name.endswith("_xgrad"):
+            x.requires_grad_()
+        th = torch.rand(len(x_off) - 1, t, generator=g).to(dev)
+        fns = [torch.rand(fo[-1], f, generator=g).to(dev) for fo in fn_offs]
         G = torch.randn(P, o, generator=g).to(dev)
-        out = m.forward_packed(x, x_off, th, fns, [[0, 200, 500]] * I)
+        out = m.forward_packed(x, x_off, th, fns, fn_offs)
         (out * G).sum().backward()
         torch.cuda.synchronize()
         res[name + ".out"] = out.detach().cpu().numpy()
         res[name + ".grad"] = m.engine().grad_flat.detach().cpu().numpy()
+        if x.grad is not None:
+            res[name + ".xgrad"] = x.grad.cpu().numpy()
+        # the packed weight images and biases: the workspace from buffer "packed" up to "grads"
+        eng = m.engine()
+        lo, hi = (eng.debug_ptr(n)[0] - eng.ws.data_ptr() for n in ("packed", "grads"))
+        res[name + ".packed"] = eng.ws[lo:hi].view(torch.float32).cpu().numpy()
         print(name, "done", flush=True)
     import train_step_util as U
     res.update({"step." + k: v for k, v in U.step_replay(U.step_inputs(U.NS)).items()})

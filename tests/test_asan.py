@@ -1,9 +1,10 @@
 """Host AddressSanitizer run of the native planning code ("debug build with
--fsanitize=address for host code").  `make asan` compiles every source with ASan on the HOST side only
-(-Xarch_host -fsanitize=address, -fno-gpu-sanitize) into gnot-replication_amd/lib/asan_plan_check,
+-fsanitize=address for host code").  `make asan` compiles the planning code with ASan and UBSan on the HOST
+side only (-Xarch_host -fsanitize=address,undefined, -fno-gpu-sanitize) into gnot-replication_amd/lib/asan_plan_check,
 a CPU-only driver (csrc/asan_plan_check.cpp) over gnot_plan_create / set_batch / set_moe_recompute /
 set_precision / workspace_bytes / grad_offsets / set_shard / shard_range / shard_exchange and their
-error paths.  Any heap overflow, use-after-free or leak aborts it with an ASan report."""
+error paths.  Any heap overflow, use-after-free, leak or undefined behaviour (an address formed from an unbound
+buffer, say) aborts it with a sanitizer report."""
 import os
 import shutil
 import subprocess
@@ -24,5 +25,6 @@ def test_planning_code_is_asan_clean():
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=23")
     r = subprocess.run([EXE], capture_output=True, text=True, env=env, timeout=600)
     assert "ERROR: AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
+    assert "runtime error:" not in r.stderr, r.stderr[-4000:]        # UndefinedBehaviorSanitizer
     assert r.returncode == 0, (r.stdout, r.stderr[-4000:])
     assert "asan_plan_check: ok" in r.stdout

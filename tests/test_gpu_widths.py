@@ -128,7 +128,7 @@ def test_padded_256_width_bf16_mode(name):
 
 
 # wide input / output widths at d > 256: the first and last Linears of the chains run the projection kernel
-# at the plan's full padded width (engine.cpp kt_of: one tile, or every tile of the hidden width)
+# at the plan's full padded width (engine.cpp Chain::KT0 / OTL: one tile, or every tile of the hidden width)
 CASES["d320_wide_io"] = dict(input_dim=150, theta_dim=60, input_func_dim=200, out_dim=200, n_attn_layers=1, d=320,
                              n_mlp_num_layers=2, n_expert=2, n_head=10, n_input_functions=1)
 
