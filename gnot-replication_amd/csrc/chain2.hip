@@ -652,8 +652,9 @@ __global__ void __launch_bounds__(64 * kC2Waves, 2) chain2_bwd_kernel(ChainArgs 
   } else {
     load_rows<OTL>(dy, a.dY, a.lddy, p, valid, a.out_dim, lane);
   }
+  // skip_dz_last (fp32 CH_MOE): the last Linear's weight gradients form s_e dq from dq themselves
   if constexpr (B16) store_rows_b16<OTL>(dy, rz(nl - 1), rowb, lane);
-  else store_rows<OTL>(dy, dz + (nl - 1) * a.dz_layer_stride, D, p, valid, 16 * OTL, lane);
+  else if (!a.skip_dz_last) store_rows<OTL>(dy, dz + (nl - 1) * a.dz_layer_stride, D, p, valid, 16 * OTL, lane);
 
   float nx[DT][4];
   u32x4 bp[KB][NP];

@@ -66,6 +66,7 @@ struct WgradGroup {
   bool wide = false;                 // ... on the 256 x 256-tile kernel (d = 256: one workgroup per job split)
   int tw = 256;                      // wide geometry's output edge: 256, or 128 (d <= 128, jobs within 128 x 128)
   bool b16 = false;                  // bf16-storage jobs (bf16 mode soft-MoE): pgemm_b16_kernel, wide geometry
+  bool scaled = false;               // some job has a per-point scale (WgradJob::scale): the wide kernel's scaled form
   std::vector<int> lins;             // weight-gradient groups: the canonical Linears whose (dW, db) they write
   int state_pts = 0, state_nw = 0;
   bool state_mfma = false;   // state groups: points per workgroup, per-point weights (0 or H)
@@ -204,6 +205,18 @@ struct gnot_plan {
   hipStream_t side2 = nullptr;          // input-function branch, concurrent with the query branch
   int wgrad_overlap_env = -1;
   bool serial_wgrad() const { return wgrad_overlap_env >= 0 ? wgrad_overlap_env == 0 : P >= kWgradSerialPoints; }
+  // The two row streams a fp32 d = 256 soft-MoE call does without; said once here, read by
+  // moe_forward, the backward's chain launch and the call's weight-gradient jobs (chain_group):
+  //   moe_direct_out: the training forward writes no [E, P, d] stage; the combine forms s_e y_e from the saved
+  //                   y_e (save slot NL-1) and the scores -- the bits of the stage rows;
+  //   moe_direct_dz:  the backward stores no dz_{NL-1} = s_e dq; the last Linear's jobs read dquery with the
+  //                   expert's score column as their scale.  Only where the group runs on the caller's stream
+  //                   right after the chain backward: a forked group reads later, beside main-stream kernels
+  //                   that accumulate into dquery, and keeps the stored rows.
+  // env GNOT_MOE_STORED_STREAMS=1 (read when the plan is created) restores both stored forms (bitwise equal)
+  bool moe_stored_env = false;
+  bool moe_direct_out() const { return !moe_stored_env && D == 256 && npk() == 3; }
+  bool moe_direct_dz() const { return moe_direct_out() && serial_wgrad(); }
   std::vector<hipEvent_t> evs;
   size_t ev_next = 0;
   // pinned staging ring for the table uploads of gnot_plan_bind_workspace_async: slot k is rewritten
@@ -418,6 +431,7 @@ extern "C" int gnot_plan_create(const gnot_config* cfg, gnot_plan** out) {
   p->W.assign(p->n_lin(), nullptr);
   p->b.assign(p->n_lin(), nullptr);
   if (const char* ov = std::getenv("GNOT_WGRAD_OVERLAP")) p->wgrad_overlap_env = ov[0] == '1' ? 1 : 0;
+  if (const char* ov = std::getenv("GNOT_MOE_STORED_STREAMS")) p->moe_stored_env = ov[0] == '1';
   *out = p;
   return GNOT_OK;
 }
@@ -732,6 +746,9 @@ static void finish_group(gnot_plan* p, WgradGroup& G) {
     if (fits) { G.wide = true; G.tw = 128; }
   }
   if (G.b16) G.wide = true;          // the bf16-storage kernel has the wide kernel's geometry
+  G.scaled = false;
+  for (const auto& J : G.jobs)
+    if (J.scale != nullptr || J.ldscale != 0) G.scaled = true;   // (ldscale: the sizing pass has null pointers)
   const long target = G.wide ? (G.tw == 128 ? w128_wgs : wide_wgs) : G.x6 ? x6_wgs : kTargetWGs;
   long tiles = 0;
   for (auto& J : G.jobs) {
@@ -917,11 +934,21 @@ static void build_groups(gnot_plan* p) {
     const float* save = p->P_(C.save);
     const Buf& x0 = p->bufs.at(C.x);
     const long rows = C.rows;
+    // moe_direct_dz: expert c's last Linear reads dquery scaled by its score column instead of a stored dz
+    const bool direct = C.mode == CH_MOE && p->moe_direct_dz();
+    const Buf& sc = p->bufs.at("scores");
     for (size_t c = 0; c < C.firsts.size(); ++c)
       for (int j = 0; j < NL; ++j) {
         const float* dzp = at(dz, ((long)c * NL + j) * rows * D);
-        if (j == 0) lin_job(C.wg, C.firsts[c] + j, dzp, D, x0.p, x0.ld, 0, rows);
-        else lin_job(C.wg, C.firsts[c] + j, dzp, D, at(save, ((long)c * NL + j - 1) * rows * D), D, 1, rows);
+        if (j == 0) {
+          lin_job(C.wg, C.firsts[c] + j, dzp, D, x0.p, x0.ld, 0, rows);
+        } else if (direct && j == NL - 1) {
+          lin_job(C.wg, C.firsts[c] + j, p->P_("dquery"), D, at(save, ((long)c * NL + j - 1) * rows * D), D, 1, rows);
+          C.wg.jobs.back().scale = at(sc.p, (long)c);
+          C.wg.jobs.back().ldscale = (int)sc.ld;
+        } else {
+          lin_job(C.wg, C.firsts[c] + j, dzp, D, at(save, ((long)c * NL + j - 1) * rows * D), D, 1, rows);
+        }
       }
     finish_group(p, C.wg);
   };
@@ -1801,7 +1828,7 @@ int launch_group(gnot_plan* p, const WgradGroup& G, float* slab, hipStream_t s) 
                              slab, s, G.d_segs, G.d_seg_start, p->bwd_accumulate));
   else
     GNOT_CK(launch_wgrad(G.d_jobs, G.d_wg_prefix, (int)G.jobs.size(), G.total_wgs, G.d_red_prefix, G.total_red, slab,
-                         s, G.x6, G.wide, p->npk(), G.tw, G.d_segs, G.d_seg_start, p->bwd_accumulate));
+                         s, G.x6, G.wide, p->npk(), G.tw, G.d_segs, G.d_seg_start, p->bwd_accumulate, G.scaled));
   return GNOT_OK;
 }
 
@@ -2038,6 +2065,9 @@ static int moe_forward(Ctx& c, const Chain& C, const float* qin, float* qout, fl
   ChainArgs a = chain_args(p, C, false, save);
   a.ldy = D;
   a.Y = p->P_("stage"); a.y_chain_stride = P * D;
+  // fp32 training at d = 256: no stage; the combine scales the saved expert outputs itself
+  const bool direct = save && p->moe_direct_out();
+  if (direct) a.Y = nullptr;
   if (p->b16s() && save) {
     // bf16 training: the experts' bf16 score-scaled terms are kept in save slot nl-1 (the backward's d score
     // operand), so the stage rows ARE that slot (chain2.hip): no separate stage write
@@ -2048,7 +2078,11 @@ static int moe_forward(Ctx& c, const Chain& C, const float* qin, float* qout, fl
     ProfScope ps(c, "moe_fwd", 2.0 * E * P * NL * (double)D * D);
     GNOT_CK(launch_chain_fwd(cw_scratch(p, a, c.s), c.s));
   }
-  GNOT_CK(launch_moe_pass(p, qin, a.Y, qout, c.s, a.y_chain_stride));
+  if (direct)
+    GNOT_CK(launch_moe_combine_scaled(qin, save + (NL - 1) * a.save_layer_stride, a.save_chain_stride, a.scores, a.ldsc,
+                                      E, qout, P, D, c.s));
+  else
+    GNOT_CK(launch_moe_pass(p, qin, a.Y, qout, c.s, a.y_chain_stride));
   return GNOT_OK;
 }
 
@@ -2201,6 +2235,7 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
     GNOT_RUN(guard_write(cc, dz));
     a.dz = dz; a.dz_layer_stride = C.rows * D; a.dz_chain_stride = NL * C.rows * D;
     if (a.b16s) { a.dz_layer_stride /= 2; a.dz_chain_stride /= 2; }   // bf16 dZ layers
+    a.skip_dz_last = (C.mode == CH_MOE && p->moe_direct_dz()) ? 1 : 0;
     {
       ProfScope ps(cc, prof, 2.0 * a.nchains * C.rows * NL * (double)D * D);
       GNOT_CK(launch_chain_bwd(cw_scratch(p, a, cc.s), cc.s));

@@ -82,6 +82,13 @@ GNOT_DEV float gelu_grad(float x) {
 }
 
 GNOT_DEV float shfl_xor(float v, int m) { return __shfl_xor(v, m, 64); }
+// a * b as its own rounded fp32 multiply: the empty asm keeps the product from being contracted into an FMA
+// with an add that consumes it (hipcc contracts across statements, __fmul_rn included)
+GNOT_DEV float mul_rn(float a, float b) {
+  float p = a * b;
+  asm volatile("" : "+v"(p));
+  return p;
+}
 
 // ---- point-form loads / stores ------------------------------------------------------------
 // load KT tiles of row p (features 16T + 4g + r); features >= ncols read as 0; invalid rows -> 0

@@ -124,6 +124,9 @@ struct ChainArgs {
   const float* dY; long lddy;        // incoming grad (CH_STORE: [P,out]; CH_MOE: dquery [P,D]);
   float* dscore;                     // CH_MOE: dscore[p*ldsc + chain] += dq . y ; CH_SOFTMAX: d(scores)
   float* dz; long dz_layer_stride; long dz_chain_stride;          // per layer dZ [P, D] for wgrad
+  // CH_MOE, d = 256, fp32: dz_{nlin-1} = s_e dq is not stored (the weight gradients of the last Linear read
+  // dq and scale it themselves, WgradJob::scale)
+  int skip_dz_last = 0;
   float* dX; long lddx; long dx_chain_stride;                     // chain input grad or null
   int np = 3;                        // d = 256: operand pieces (3 = bf16x6 fp32-exact, 1 = bf16 mode)
 #ifdef GNOT_DIAG_STAMP
@@ -164,6 +167,7 @@ struct alignas(16) WgradJob {
   const float* x;  long ldx;         // B rows [P, in]
   int x_gelu;                        // 1: B = gelu(x) (x is a saved pre-activation)
   int out, in;
+  int ldscale;                       // stride (floats) between two points' scale
   float* dW;                         // [out, in] row-major, or the state [H][dh*dh + dh] (state_dh > 0)
   float* db;                         // [out] column sums of A, or null
   const float* w; long ldw; int wdh; // optional per-(point, column/wdh) weight of the column sums
@@ -173,7 +177,13 @@ struct alignas(16) WgradJob {
   int tiles_o, tiles_i;              // 128x128 output tiles
   int splits;                        // split-K count over points
   long slab_off;                     // offset (floats) of this job's partial slabs
+  // optional per-point scale of the A rows (wide 256 x 256 kernel only): A[p, :] = scale[p * ldscale] * dz[p, :],
+  // one rounded fp32 multiply before the mask, the column sums and the split.  The soft-MoE calls' last Linear:
+  // dz = dquery (shared by the E experts), scale = the expert's score column -- the rows s_e dq the chain
+  // backward would otherwise store per expert (ChainArgs::skip_dz_last)
+  const float* scale;
 };
+static_assert(sizeof(WgradJob) == 128, "WgradJob: one 128-byte line per job");
 // one workgroup per (job, tile, split); wg_prefix / red_prefix: per-job prefix sums of workgroups and
 // of reduce elements (ntile * 128 * 129)
 // x6: plain weight-gradient jobs only (no w, state_dh, diag_only) on the bf16x6 MFMA kernel
@@ -186,10 +196,13 @@ struct alignas(16) WgradJob {
 // accumulate: the split-K finish adds its sum onto dW / db instead of overwriting them (per launch, not in
 // the job tables: one bound plan overwrites in one backward and accumulates in the next); jobs with
 // state_dh > 0 always overwrite
+// scaled: the group holds jobs with WgradJob::scale (wide, np = 3, tw = 256 only): the kernel instantiation
+// that stages them; jobs with a scale in any other launch are an error of the caller (the scale is ignored)
 hipError_t launch_wgrad(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
                         const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, bool x6 = false,
                         bool wide = false, int np = 3, int tw = 256,    // np: operand pieces (1 = bf16 mode)
-                        const int4* segs = nullptr, const int* seg_start = nullptr, bool accumulate = false);
+                        const int4* segs = nullptr, const int* seg_start = nullptr, bool accumulate = false,
+                        bool scaled = false);
 // bf16-storage jobs (ChainArgs::b16s): dz and x point at bf16 pair-interleaved rows [P, 256] (x already
 // the Linear's input, no GELU), out = in = 256, one workgroup per (job, split) as the wide kernel
 hipError_t launch_wgrad_b16(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
@@ -270,6 +283,12 @@ hipError_t launch_concat_theta(const float* x, long ldx, int in_dim, const float
 // out = (base ? base : 0) + sum_e stage[e]
 hipError_t launch_moe_combine(const float* base, const float* stage, long stage_stride, int E,
                               float* out, long n, hipStream_t s);
+// out[p, :] = base[p, :] + sum_e scores[p * ldsc + e] * y[e * y_stride + p * D + :] in expert order, each
+// product its own rounded fp32 multiply (gnot_common.h mul_rn): the bits of moe_combine over the stage rows
+// s_e y_e a CH_MOE chain forward writes, from the experts' saved outputs y_e (save slot nlin-1) instead.  D a
+// multiple of 4
+hipError_t launch_moe_combine_scaled(const float* base, const float* y, long y_stride, const float* scores, int ldsc,
+                                     int E, float* out, long P, int D, hipStream_t s);
 // the same over bf16 pair-interleaved stage rows (ChainArgs::stage_b16: 512 B per point at the start of each
 // expert's fp32-sized region, stage_stride in floats); base / out fp32 [P, 256]
 hipError_t launch_moe_combine_b16(const float* base, const float* stage, long stage_stride, int E, float* out,

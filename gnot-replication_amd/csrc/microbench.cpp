@@ -277,6 +277,21 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < ndw; ++i) { n2 += (got[i] - ref[i]) * (double)(got[i] - ref[i]); d2 += (double)ref[i] * ref[i]; }
         std::printf("wgrad MoE  bf16 wide 256x256 (%d WGs):    %8.2f us  %6.1f TFLOP/s  (rel-L2 vs fp32 %.2e)\n",
                     njobs * splits, t, fl / t / 1e6, std::sqrt(n2 / (d2 + 1e-30)));
+        {
+          // the serial soft-MoE form (WgradJob::scale): every chain's last Linear reads ONE shared dZ (dquery)
+          // scaled by the chain's score column instead of its own stored s dq rows
+          std::vector<WgradJob> sj(wj);
+          for (int k = 0; k < njobs; ++k)
+            if (k % NL == NL - 1) { sj[k].dz = dz; sj[k].scale = scores + k / NL; sj[k].ldscale = 16; }
+          CK(hipMemcpy(dwj, sj.data(), sj.size() * sizeof(WgradJob), hipMemcpyHostToDevice));
+          t = time_us([&] {
+            CK(launch_wgrad(dwj, dwpre, njobs, njobs * splits, dwpre + njobs, red, wslab, nullptr, true, true, 3, 256,
+                            nullptr, nullptr, false, true));
+          }, 20);
+          std::printf("wgrad MoE  bf16x6 wide, last Linear scaled (%d WGs): %8.2f us  %6.1f TFLOP/s\n", njobs * splits, t,
+                      fl / t / 1e6);
+          CK(hipMemcpy(dwj, wj.data(), wj.size() * sizeof(WgradJob), hipMemcpyHostToDevice));
+        }
         if (wgs == 512) {
           // diagnostics of the wide x6 kernel: without the GELU of the B operand, with every point
           // reading row 0 (L2-resident rows: no HBM latency), and both

@@ -72,6 +72,36 @@ hipError_t launch_moe_combine(const float* base, const float* stage, long stage_
   return hipGetLastError();
 }
 
+// the training forward's combine (fp32, d = 256): the stage row s_e y_e is formed here from the saved y_e, as
+// its own rounded multiply (never contracted into the add), then summed as moe_combine_kernel sums the stage
+__global__ void __launch_bounds__(256) moe_combine_scaled_kernel(const float4* __restrict__ base,
+                                                                 const float4* __restrict__ y, long y_stride4,
+                                                                 const float* __restrict__ scores, int ldsc, int E,
+                                                                 float4* __restrict__ out, long n4, int d4) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float* sc = scores + (i / d4) * ldsc;
+    float4 v = base[i];
+    for (int e = 0; e < E; ++e) {
+      const float4 t = y[e * y_stride4 + i];
+      const float s = sc[e];
+      v.x += mul_rn(t.x, s); v.y += mul_rn(t.y, s); v.z += mul_rn(t.z, s); v.w += mul_rn(t.w, s);
+    }
+    out[i] = v;
+  }
+}
+
+hipError_t launch_moe_combine_scaled(const float* base, const float* y, long y_stride, const float* scores, int ldsc,
+                                     int E, float* out, long P, int D, hipStream_t s) {
+  if (P <= 0) return hipSuccess;
+  if (!base || (D & 3) || (y_stride & 3)) return hipErrorInvalidValue;
+  const long n4 = P * (D / 4);
+  const long blocks = std::min<long>((n4 + 255) / 256, 4096);
+  hipLaunchKernelGGL(moe_combine_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(base), reinterpret_cast<const float4*>(y), y_stride / 4, scores,
+                     ldsc, E, reinterpret_cast<float4*>(out), n4, D / 4);
+  return hipGetLastError();
+}
+
 // bf16 stage rows: thread = one 16-byte chunk k of a point's 512-byte pair-interleaved row (gnot_common.h
 // b16_off): features f0 .. f0+3 (half 0) and f0+16 .. f0+19 (half 1), f0 = 32 (k >> 2) + 4 (k & 3).  Sums in
 // expert order from base, as moe_combine does over the same (bf16-exact) values: bitwise equal to it

@@ -372,6 +372,14 @@ __global__ void __launch_bounds__(256) pgemm_x6_kernel(const WgradJob* __restric
 //            iterations instead of one, and the raw rows in flight hold no registers).
 //   staging: thread t owns feature f = t & 255 and point half h = t >> 8 of a stage, for both operands:
 //            mask, column sum, GELU, then 3 bf16 pieces of 8 consecutive points = three 16-byte LDS stores.
+//   scale:   jobs with WgradJob::scale multiply each raw A value by its point's scale first (one rounded fp32
+//            multiply).  A thread's 8 points are the wave's (the point half is wave-uniform): one dword load
+//            per wave and stage leaves the scale of point l & 7 in lane l, read back lane by lane (v_readlane)
+//            where a point is staged -- one vector register per stage in flight, no LDS.  The load goes through a
+//            resource that ends with the split's last point, so the points past it read 0, never the memory
+//            behind.  It is requested one iteration ahead, in front of that iteration's row DMAs, and retired
+//            by the same counted wait.  Only the SCK = true instantiation (launch_wgrad `scaled`: groups that
+//            hold such jobs) carries any of this; inside it, jobs without a scale run the unscaled loops.
 //   LDS:     per (buffer, operand, piece) a fragment-order image of 8 row blocks x 64 lanes x 16 B:
 //            lane (r, h) of block rb holds rows 32 rb + r, points 8h .. 8h+7 -- the A/B operand layout of
 //            v_mfma_f32_32x32x16_bf16, so fragment reads are contiguous 1 KiB ds_read_b128.
@@ -409,7 +417,9 @@ GNOT_DEV float lds_read_b32_off(unsigned addr) {
 // segs[seg_start[w] .. seg_start[w + 1]) = {job, slab slot, first point, end point} one after the other (a
 // range of the groups' concatenated points, cut at job boundaries), so every workgroup gets the same share
 // of the group's points whatever the job count; without them, one split of one job (prefix)
-template <int NP = 3, int TW = 256>
+// SCK: the instantiation for groups that hold scaled jobs (NP = 3, TW = 256); every other group runs the
+// SCK = false kernel, which carries none of the scaled form's code or registers
+template <int NP = 3, int TW = 256, bool SCK = false>
 __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob* __restrict__ jobs,
                                                                  const int* __restrict__ prefix, int njobs,
                                                                  float* __restrict__ slab,
@@ -451,6 +461,7 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
   const int ncb = max(0, min(2, (J.in - 64 * wc + 31) / 32));
   const bool full = nrb == RB && ncb == 2;
   const bool gel = J.x_gelu != 0;
+  const bool scaled = SCK && J.scale != nullptr;
 
   f32x16 acc[RB][2];
 #pragma unroll
@@ -466,6 +477,28 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
   const long nsp = pe > pb ? pe - pb : 0;
   const rsrc_t rA = make_rsrc(J.dz + pb * J.lddz, (unsigned)(nsp * J.lddz * 4));
   const rsrc_t rB = make_rsrc(J.x + pb * J.ldx, (unsigned)(nsp * J.ldx * 4));
+  // scaled jobs: the split's scales, ending with its last point's (the whole offset goes in the VGPR: every
+  // byte of it is bounds-checked).  Lane l asks for point l & 7 of the wave's 8 points of stage st
+  const rsrc_t rS = make_rsrc(scaled ? J.scale + pb * J.ldscale : nullptr,
+                              scaled && nsp > 0 ? (unsigned)(((nsp - 1) * J.ldscale + 1) * 4) : 0u);
+  auto scale_voff = [&](int st) __attribute__((always_inline)) {
+    int l = lane & 7;
+    asm volatile("" : "+v"(l));                    // recomputed per stage: no register held across the loop
+    return (st * kWStage + 8 * (wave / FG) + l) * (int)J.ldscale * 4;
+  };
+  // the load as the compiler sees it (it waits for every vector-memory op in flight: outside the loop only)
+  auto scale_load = [&](int st) __attribute__((always_inline)) { return buf_load_f32(rS, scale_voff(st), 0); };
+  // ... and behind its back, in the counted-vmcnt stream of the row DMAs: valid only after a counted wait
+  // that names the register (scale_wait)
+  auto scale_issue = [&](int st) __attribute__((always_inline)) {
+    float v;
+    asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(v) : "v"(scale_voff(st)), "s"(rS) : "memory");
+    return v;
+  };
+  // point k's scale out of the loaded register
+  auto scale_of = [](float v, int k) __attribute__((always_inline)) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
+  };
   // DMA lane role: instruction i of operand o brings points 4 i + (lane >> 4) of the wave's half, features
   // 64 (wave % FG) + 4 (lane & 15) .. +3; in the slot, point k of the half is the 256-byte row k (64 floats)
   const int fcol = 64 * (wave % FG) + 4 * (lane & 15);
@@ -500,11 +533,12 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
   };
   // split + LDS store of the staged rows; gel is uniform per workgroup: one branch around the whole
   // stage (not per element), so each variant is one straight-line block the scheduler can interleave
-  auto stage_v = [&](int buf, auto GEL) {
+  auto stage_v = [&](int buf, auto GEL, auto SC, float sc) {
     float ra[8], vb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      ra[k] = fa ? ra_raw[k] : 0.f;               // columns past out / in
+      const float av = decltype(SC)::value ? mul_rn(ra_raw[k], scale_of(sc, k)) : ra_raw[k];
+      ra[k] = fa ? av : 0.f;                      // columns past out / in
       const float b = fb ? rb_raw[k] : 0.f;
       dbacc += ra[k];
       vb[k] = decltype(GEL)::value ? gelu(b) : b;
@@ -519,9 +553,18 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
       base[(NP + q) * kWPiece + sdst] = pq[q];
     }
   };
-  auto stage = [&](int buf) {
-    if (gel) stage_v(buf, std::true_type{});
-    else stage_v(buf, std::false_type{});
+  // st: the stage whose rows ra_raw / rb_raw hold (scaled jobs load its scales here, unhidden: the prologue
+  // and the edge-tile loop)
+  auto stage = [&](int buf, int st) {
+    float sc = 0.f;
+    if (scaled) {
+      sc = scale_load(st);
+      if (gel) stage_v(buf, std::true_type{}, std::true_type{}, sc);
+      else stage_v(buf, std::false_type{}, std::true_type{}, sc);
+    } else {
+      if (gel) stage_v(buf, std::true_type{}, std::false_type{}, sc);
+      else stage_v(buf, std::false_type{}, std::false_type{}, sc);
+    }
   };
   auto compute = [&](int buf) {
     const u32x4* A = wl + buf * w_buf(NP, TW);
@@ -556,11 +599,12 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
     c2_wait_vm<4>();
     raw_read(0);
     raw_dma(2);
-    stage(0);
+    stage(0, 0);
     lds_barrier();
     int buf = 0;
     // MASK: columns past out / in exist (the fa / fb selects); jobs with out = in = 256 skip them
-    auto fused = [&](int b, auto GEL, auto MASK) {
+    // SC: scaled job, sc = the scales of the 8 points being staged (scale_load's register)
+    auto fused = [&](int b, auto GEL, auto MASK, auto SC, float sc) {
       const u32x4* A = wl + b * w_buf(NP, TW);
       const u32x4* Bm = A + NP * kWPiece;
       u32x4 bf[2][NP], af[2][NP], pa[NP], pq[NP];
@@ -575,7 +619,8 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
       // second point the split of the pair just finished); sched_barrier pins the order, so each wave
       // alternates MFMA groups and VALU chunks and the two waves of a SIMD fill each other's gaps
       auto chunk = [&](int k) {
-        ra[k] = (!decltype(MASK)::value || fa) ? ra_raw[k] : 0.f;
+        const float av = decltype(SC)::value ? mul_rn(ra_raw[k], scale_of(sc, k)) : ra_raw[k];
+        ra[k] = (!decltype(MASK)::value || fa) ? av : 0.f;
         dbacc += ra[k];
         const float bv = (!decltype(MASK)::value || fb) ? rb_raw[k] : 0.f;
         vb[k] = decltype(GEL)::value ? gelu(bv) : bv;
@@ -617,23 +662,39 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
     };
     // iteration s: stage s + 1's rows (the wait leaves stage s + 2's four DMAs in flight) are read, their
     // slot refilled with stage s + 3, and staged while stage s is multiplied
-    auto run = [&](auto GEL, auto MASK) {
-      for (int s = 0; s + 1 < nst; ++s) {
+    // scaled jobs: stage s + 2's scales are requested in front of stage s + 3's rows, so the counted wait
+    // that leaves those four DMAs in flight retires them with stage s + 2's rows.  That wait stands at the END
+    // of the iteration (the same place in time as the top of the next): it names the loaded register, so
+    // whatever the compiler does with the value for the next iteration comes after it
+    auto run = [&](auto GEL, auto MASK, auto SC) {
+      float scn = 0.f;
+      if (decltype(SC)::value) {
+        scn = scale_load(1);
         c2_wait_vm<4>();
+      }
+      for (int s = 0; s + 1 < nst; ++s) {
+        const float sc = scn;
+        if (!decltype(SC)::value) c2_wait_vm<4>();
         raw_read(s + 1);
+        if (decltype(SC)::value) scn = scale_issue(s + 2);
         raw_dma(s + 3);
-        fused(buf, GEL, MASK);
+        fused(buf, GEL, MASK, SC, sc);
         lds_barrier();
         buf ^= 1;
+        if (decltype(SC)::value) asm volatile("s_waitcnt vmcnt(4)" : "+v"(scn) :: "memory");
       }
     };
-    if (full) {
+    // the interleaved form of scaled jobs: whole 256 x 256 gradients of a GELU'd input (a chain's last hidden
+    // Linear, all the engine scales); any other scaled job takes the plain loop below
+    if (full && scaled && gel && J.out >= TW && J.in >= TW) {
+      run(std::true_type{}, std::false_type{}, std::true_type{});
+    } else if (full && !scaled) {
       if (J.out >= TW && J.in >= TW) {
-        if (gel) run(std::true_type{}, std::false_type{});
-        else run(std::false_type{}, std::false_type{});
+        if (gel) run(std::true_type{}, std::false_type{}, std::false_type{});
+        else run(std::false_type{}, std::false_type{}, std::false_type{});
       } else {
-        if (gel) run(std::true_type{}, std::true_type{});
-        else run(std::false_type{}, std::true_type{});
+        if (gel) run(std::true_type{}, std::true_type{}, std::false_type{});
+        else run(std::false_type{}, std::true_type{}, std::false_type{});
       }
     } else {
       for (int s = 0; s + 1 < nst; ++s) {
@@ -641,7 +702,7 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
         raw_read(s + 1);
         raw_dma(s + 3);
         compute(buf);
-        stage(buf ^ 1);
+        stage(buf ^ 1, s + 1);
         lds_barrier();
         buf ^= 1;
       }
@@ -652,8 +713,16 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
   }
 
   // partials -> slab [split][128-tile][128 x (128 + 1)] (the pgemm_kernel layout)
-  const int ntile = J.tiles_o * J.tiles_i;
-  float* S0 = slab + J.slab_off + (long)split * ntile * (kTile * (kTile + 1));
+  // (SCK: the job's fields are read again here -- holding them in SGPRs through the stage loops above, next
+  // to the scaled form's resource, costs the loops registers they do not have)
+  const WgradJob* jp = &J;
+  if constexpr (SCK) {
+    jp = jobs + j;
+    asm volatile("" : "+s"(jp));
+  }
+  const WgradJob& JE = *jp;
+  const int ntile = JE.tiles_o * JE.tiles_i;
+  float* S0 = slab + JE.slab_off + (long)split * ntile * (kTile * (kTile + 1));
 #pragma unroll
   for (int ib = 0; ib < RB; ++ib)
 #pragma unroll
@@ -662,11 +731,11 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
       for (int r = 0; r < 16; ++r) {
         const int row = wr * 32 * RB + ib * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         const int col = wc * 64 + jb * 32 + (lane & 31);
-        if (row < J.out && col < J.in)
-          S0[((row >> 7) * J.tiles_i + (col >> 7)) * (kTile * (kTile + 1)) + (row & 127) * (kTile + 1) + (col & 127)] =
+        if (row < JE.out && col < JE.in)
+          S0[((row >> 7) * JE.tiles_i + (col >> 7)) * (kTile * (kTile + 1)) + (row & 127) * (kTile + 1) + (col & 127)] =
               acc[ib][jb][r];
       }
-  if (J.db != nullptr) {
+  if (JE.db != nullptr) {
     // column sums of A: the two point halves of every feature through LDS, in a fixed order
     // (red overlays stage buffer 0, which other waves may still be reading in the last compute(): the
     // interleaved loop ends without a barrier)
@@ -674,8 +743,8 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
     __syncthreads();
     red[hh * TW + f] = dbacc;
     __syncthreads();
-    if (tid < TW && f < J.out)
-      S0[((f >> 7) * J.tiles_i) * (kTile * (kTile + 1)) + (f & 127) * (kTile + 1) + kTile] = red[f] + red[TW + f];
+    if (tid < TW && f < JE.out)
+      S0[((f >> 7) * JE.tiles_i) * (kTile * (kTile + 1)) + (f & 127) * (kTile + 1) + kTile] = red[f] + red[TW + f];
   }
   }
 }
@@ -905,22 +974,24 @@ hipError_t launch_wgrad_b16(const WgradJob* jobs_dev, const int* wg_prefix_dev, 
 
 hipError_t launch_wgrad(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
                         const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, bool x6, bool wide,
-                        int np, int tw, const int4* segs, const int* seg_start, bool accumulate) {
+                        int np, int tw, const int4* segs, const int* seg_start, bool accumulate, bool scaled) {
   if (njobs <= 0) return hipSuccess;
+  if (scaled && !(wide && np == 3 && tw == 256)) return hipErrorInvalidValue;
   if (wide) {
     const size_t lds = w_lds_bytes(np, tw);
-#define GNOT_X6W(NP_, TW_)                                                                                     \
-  if (np == NP_ && tw == TW_) {                                                                                \
+#define GNOT_X6W(NP_, TW_, SC_)                                                                                \
+  if (np == NP_ && tw == TW_ && scaled == SC_) {                                                               \
     static bool attr = false;                                                                                  \
     if (!attr) {                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pgemm_x6w_kernel<NP_, TW_>),                     \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pgemm_x6w_kernel<NP_, TW_, SC_>),                \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
       attr = true;                                                                                             \
     }                                                                                                          \
-    hipLaunchKernelGGL((pgemm_x6w_kernel<NP_, TW_>), dim3(total_wgs), dim3(w_threads(TW_)), lds, s, jobs_dev,  \
-                       wg_prefix_dev, njobs, slab, segs, seg_start);                                           \
+    hipLaunchKernelGGL((pgemm_x6w_kernel<NP_, TW_, SC_>), dim3(total_wgs), dim3(w_threads(TW_)), lds, s,       \
+                       jobs_dev, wg_prefix_dev, njobs, slab, segs, seg_start);                                 \
   }
-    GNOT_X6W(3, 256) GNOT_X6W(1, 256) GNOT_X6W(3, 128) GNOT_X6W(1, 128)
+    GNOT_X6W(3, 256, false) GNOT_X6W(3, 256, true) GNOT_X6W(1, 256, false) GNOT_X6W(3, 128, false)
+    GNOT_X6W(1, 128, false)
 #undef GNOT_X6W
   } else if (x6) {
     if (np == 1) hipLaunchKernelGGL(pgemm_x6_kernel<1>, dim3(total_wgs), dim3(256), 0, s, jobs_dev, wg_prefix_dev, njobs, slab);
