@@ -2453,15 +2453,28 @@ extern "C" size_t gnot_rel_l2_work_floats(const int64_t* off_host, int B, int C)
   return (size_t)B * rel_l2_splits(off.data(), B) * 2 * C + (size_t)B * C;
 }
 
-extern "C" int gnot_rel_l2_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
-                                int B, int C, float* work, float* loss, float* dpred, void* stream) {
+// gnot_rel_l2_loss (stats == nullptr) and gnot_rel_l2_loss_affine
+static int rel_l2_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B,
+                       int C, const float* stats, float* work, float* loss, float* dpred, void* stream) {
   if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
     return fail(GNOT_E_INVALID, "bad rel_l2 arguments");
   std::vector<long> off(off_host, off_host + B + 1);
   if (int rc = check_loss_offsets(off, true)) return rc;
   GNOT_CK(launch_rel_l2(pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B),
-                        off[B], work, loss, dpred, static_cast<hipStream_t>(stream)));
+                        off[B], stats, work, loss, dpred, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
+}
+
+extern "C" int gnot_rel_l2_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
+                                int B, int C, float* work, float* loss, float* dpred, void* stream) {
+  return rel_l2_loss(pred, tgt, off_dev, off_host, B, C, nullptr, work, loss, dpred, stream);
+}
+
+extern "C" int gnot_rel_l2_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev,
+                                       const int64_t* off_host, int B, int C, const float* out_stats, float* work,
+                                       float* loss, float* dpred, void* stream) {
+  if (!out_stats) return fail(GNOT_E_INVALID, "rel_l2_loss_affine: null out_stats");
+  return rel_l2_loss(pred, tgt, off_dev, off_host, B, C, out_stats, work, loss, dpred, stream);
 }
 
 extern "C" int gnot_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
@@ -2479,15 +2492,28 @@ extern "C" size_t gnot_mse_work_floats(const int64_t* off_host, int B, int C) {
   return (size_t)B * rel_l2_splits(off.data(), B) * C;
 }
 
-extern "C" int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
-                             int B, int C, float* work, float* loss, float* dpred, void* stream) {
+// gnot_mse_loss (stats == nullptr) and gnot_mse_loss_affine
+static int mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B, int C,
+                    const float* stats, float* work, float* loss, float* dpred, void* stream) {
   if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
     return fail(GNOT_E_INVALID, "bad mse arguments");
   std::vector<long> off(off_host, off_host + B + 1);
   if (int rc = check_loss_offsets(off, false)) return rc;
   GNOT_CK(launch_mse(pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
-                     work, loss, dpred, static_cast<hipStream_t>(stream)));
+                     stats, work, loss, dpred, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
+}
+
+extern "C" int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
+                             int B, int C, float* work, float* loss, float* dpred, void* stream) {
+  return mse_loss(pred, tgt, off_dev, off_host, B, C, nullptr, work, loss, dpred, stream);
+}
+
+extern "C" int gnot_mse_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev,
+                                    const int64_t* off_host, int B, int C, const float* out_stats, float* work,
+                                    float* loss, float* dpred, void* stream) {
+  if (!out_stats) return fail(GNOT_E_INVALID, "mse_loss_affine: null out_stats");
+  return mse_loss(pred, tgt, off_dev, off_host, B, C, out_stats, work, loss, dpred, stream);
 }
 
 extern "C" size_t gnot_grad_clip_work_floats(int64_t n) { return (size_t)grad_clip_partials(n); }
@@ -2546,8 +2572,9 @@ extern "C" int gnot_adamw_step_ema(float* param, const float* grad, float* exp_a
   return GNOT_OK;
 }
 
-extern "C" int gnot_gather_rows(const float* src, int C, const int64_t* table_dev, const int64_t* table_host, int B,
-                                float* dst, void* stream) {
+// gnot_gather_rows (stats == nullptr) and gnot_gather_rows_affine
+static int gather_rows(const float* src, int C, const int64_t* table_dev, const int64_t* table_host, int B,
+                       const float* stats, float* dst, void* stream) {
   if (!src || !table_dev || !table_host || !dst) return fail(GNOT_E_INVALID, "gather_rows: null argument");
   if (B < 1 || C < 1) return fail(GNOT_E_INVALID, "gather_rows: B and C must be at least 1");
   long rows = 0;
@@ -2563,8 +2590,35 @@ extern "C" int gnot_gather_rows(const float* src, int C, const int64_t* table_de
     rows += T[3];
   }
   if (rows == 0) return GNOT_OK;
-  GNOT_CK(launch_gather_rows(src, C, reinterpret_cast<const long*>(table_dev), B, dst, rows,
+  GNOT_CK(launch_gather_rows(src, C, reinterpret_cast<const long*>(table_dev), B, stats, dst, rows,
                              static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_gather_rows(const float* src, int C, const int64_t* table_dev, const int64_t* table_host, int B,
+                                float* dst, void* stream) {
+  return gather_rows(src, C, table_dev, table_host, B, nullptr, dst, stream);
+}
+
+extern "C" int gnot_gather_rows_affine(const float* src, int C, const int64_t* table_dev, const int64_t* table_host,
+                                       int B, const float* stats, float* dst, void* stream) {
+  if (!stats) return fail(GNOT_E_INVALID, "gather_rows_affine: null stats");
+  return gather_rows(src, C, table_dev, table_host, B, stats, dst, stream);
+}
+
+extern "C" size_t gnot_channel_stats_work_floats(int64_t rows, int C) {
+  if (rows < 1 || C < 1) return 0;
+  return (size_t)channel_stats_slices(rows) * 3 * (size_t)C;
+}
+
+extern "C" int gnot_channel_stats(const float* src, int64_t rows, int C, float eps, float* work, float* stats,
+                                  void* stream) {
+  if (!src || !work || !stats) return fail(GNOT_E_INVALID, "channel_stats: null argument");
+  if (rows < 1 || rows >= (1L << 31)) return fail(GNOT_E_INVALID, "channel_stats: rows must be in [1, 2^31)");
+  if (C < 1) return fail(GNOT_E_INVALID, "channel_stats: C must be at least 1");
+  if (!(eps >= 0.f) || !std::isfinite(eps))
+    return fail(GNOT_E_INVALID, "channel_stats: eps must be finite and not negative");
+  GNOT_CK(launch_channel_stats(src, rows, C, eps, work, stats, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

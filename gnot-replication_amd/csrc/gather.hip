@@ -6,6 +6,7 @@
 //
 //   table  one row of kGatherCols int64 per segment b: {src_row0, n, dst_row0, k, key_lo, key_hi}
 //   dst[dst_row0 + j] = src[src_row0 + sigma_b(j)], 0 <= j < k;  sigma_b = identity if k == n, else pi
+//   (gnot_gather_rows_affine: the same rows, every value normalised with its channel's statistics, stats.hip)
 //
 // pi(j; n, key) is a cycle-walking Feistel permutation of [0, n), all arithmetic uint32:
 //   bits = bit_length(n - 1), h = (bits + 1) / 2, mask = 2^h - 1   (the domain 2^(2h) is below 4 n)
@@ -40,10 +41,16 @@ __device__ __forceinline__ int segment_of_row(const long* __restrict__ table, in
   return lo;
 }
 
-// one thread per destination row; `rows` = sum of k
+// one thread per destination row; `rows` = sum of k.  Stats is empty -- gather_rows_kernel<>, the plain copy, with
+// the argument list and so the code it had before there was anything else -- or one const float*, the stats
+// block {mean[C], std[C], rstd[C]}: every value is then written normalised, (s - mean[c]) * rstd[c], the
+// difference and the product each rounded to fp32 -- the bits of the plain gather followed by torch's
+// (g - mean) * rstd
+template <typename... Stats>
 __global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restrict__ src, int C,
                                                           const long* __restrict__ table, int B,
-                                                          float* __restrict__ dst, long rows) {
+                                                          float* __restrict__ dst, long rows, Stats... stats_arg) {
+  static_assert(sizeof...(Stats) <= 1, "at most one stats block");
   for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < rows; r += (long)gridDim.x * 256) {
     const long* T = table + (long)segment_of_row(table, B, r) * kGatherCols;
     const long n = T[1], k = T[3];
@@ -68,15 +75,24 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restric
     }
     const float* s = src + (T[0] + (long)x) * C;
     float* d = dst + r * C;
-    for (int c = 0; c < C; ++c) d[c] = s[c];
+    if constexpr (sizeof...(Stats) == 1) {
+      const float* __restrict__ stats = (stats_arg, ...);
+      for (int c = 0; c < C; ++c) d[c] = __fmul_rn(__fsub_rn(s[c], stats[c]), stats[2 * C + c]);
+    } else {
+      for (int c = 0; c < C; ++c) d[c] = s[c];
+    }
   }
 }
 
-// rows >= 1
-hipError_t launch_gather_rows(const float* src, int C, const long* table, int B, float* dst, long rows,
-                              hipStream_t s) {
+// rows >= 1; stats == nullptr: the plain copy
+hipError_t launch_gather_rows(const float* src, int C, const long* table, int B, const float* stats, float* dst,
+                              long rows, hipStream_t s) {
   const unsigned grid = (unsigned)std::min<long>((rows + 255) / 256, 8192);
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(256), 0, s, src, C, table, B, dst, rows);
+  if (stats)
+    hipLaunchKernelGGL(gather_rows_kernel<const float*>, dim3(grid), dim3(256), 0, s, src, C, table, B, dst, rows,
+                       stats);
+  else
+    hipLaunchKernelGGL(gather_rows_kernel<>, dim3(grid), dim3(256), 0, s, src, C, table, B, dst, rows);
   return hipGetLastError();
 }
 

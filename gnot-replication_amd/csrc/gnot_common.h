@@ -90,6 +90,20 @@ GNOT_DEV float mul_rn(float a, float b) {
   return p;
 }
 
+// (train.hip, stats.hip) The sum of x over the workgroup's 256 threads, to every thread: a binary tree through red (256 floats of
+// shared memory), always in the same order.  red is free again on return.
+GNOT_DEV float block_sum(float x, float* red) {
+  red[threadIdx.x] = x;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float sum = red[0];
+  __syncthreads();
+  return sum;
+}
+
 // ---- point-form loads / stores ------------------------------------------------------------
 // load KT tiles of row p (features 16T + 4g + r); features >= ncols read as 0; invalid rows -> 0
 // (16-byte loads when the row pitch allows it; X must then be 16-byte aligned)

@@ -312,12 +312,13 @@ hipError_t launch_segcopy(const CopySeg* segs, const int* prefix, int nseg, int 
 
 // ------------------------------------------------------------------ training step (train.hip)
 int rel_l2_splits(const long* off_host, int B);
-// work: B*nsplit*2C + B*C floats
+// work: B*nsplit*2C + B*C floats.  stats != nullptr (a stats block {mean[C], std[C], rstd[C]}, stats.hip): the
+// loss of pred * std[c] + mean[c] and its gradient times std[c]; nullptr: the plain loss
 hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                         long rows, float* work, float* loss, float* dpred, hipStream_t s);
-// work: B*nsplit*C floats (nsplit = rel_l2_splits); every sample must have at least one row
+                         long rows, const float* stats, float* work, float* loss, float* dpred, hipStream_t s);
+// work: B*nsplit*C floats (nsplit = rel_l2_splits); every sample must have at least one row; stats as above
 hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
-                      float* work, float* loss, float* dpred, hipStream_t s);
+                      const float* stats, float* work, float* loss, float* dpred, hipStream_t s);
 // stage-1 partial sums of sum g^2 over n elements (a function of n alone); 0 for n < 1
 long grad_clip_partials(long n);
 // work: grad_clip_partials(n) floats; clip: 2 floats {norm, coefficient}
@@ -338,9 +339,18 @@ hipError_t launch_adamw_update(float* param, const float* grad, float* m, float*
 // ------------------------------------------------------------------ batch assembly (gather.hip)
 // table: one row of kGatherCols longs per segment {src_row0, n, dst_row0, k, key_lo, key_hi}; dst row
 // dst_row0 + j = src row src_row0 + j (k == n) or src_row0 + pi(j; n, key) (k < n), 0 <= j < k.
-// rows = sum of k >= 1; the table is validated by the caller (gnot_gather_rows)
+// rows = sum of k >= 1; the table is validated by the caller (gnot_gather_rows).  stats != nullptr: every value
+// is written as (s - mean[c]) * rstd[c] from the stats block {mean[C], std[C], rstd[C]}; nullptr: the plain copy
 constexpr int kGatherCols = 6;
-hipError_t launch_gather_rows(const float* src, int C, const long* table, int B, float* dst, long rows,
-                              hipStream_t s);
+hipError_t launch_gather_rows(const float* src, int C, const long* table, int B, const float* stats, float* dst,
+                              long rows, hipStream_t s);
+
+// ------------------------------------------------------------------ channel statistics (stats.hip)
+// stage-1 slices over `rows` rows (a function of rows alone); 0 for rows < 1
+long channel_stats_slices(long rows);
+// stats = {mean[C], std[C], rstd[C]} of src [rows, C] (unbiased std, rstd = 1 / (std + eps); a constant channel:
+// std 0, rstd 1).  work: channel_stats_slices(rows) * 3 * C floats; rows >= 1, C >= 1
+hipError_t launch_channel_stats(const float* src, long rows, int C, float eps, float* work, float* stats,
+                                hipStream_t s);
 
 }  // namespace gnot

@@ -17,6 +17,8 @@
 //   ema       an exponential moving average of the parameters, ema += w (param - ema), as one more stream of
 //             the update (adamw_update_kernel<true>: plain, clipped or guarded) or as a pass of its own
 //             (ema_update_kernel); w comes from device memory like the other hyper-parameters.
+//   affine    both losses on a normalised prediction: p' = pred * std[c] + mean[c] against the raw target, and
+//             the gradient scaled by std[c], inside the same passes (Stats of the partial and grad kernels).
 // adamw, its clipped and guarded forms and the fused average are one kernel, adamw_update_kernel<kEma>.
 #include "gnot_common.h"
 #include "gnot_kernels.h"
@@ -24,20 +26,6 @@
 namespace gnot {
 
 constexpr int kLossRows = 2048;   // rows per partial-sum workgroup
-
-// The sum of x over the workgroup's 256 threads, to every thread: a binary tree through red (256 floats of
-// shared memory), always in the same order.  red is free again on return.
-__device__ __forceinline__ float block_sum(float x, float* red) {
-  red[threadIdx.x] = x;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float sum = red[0];
-  __syncthreads();
-  return sum;
-}
 
 // the sample b of packed row r: off[b] <= r < off[b + 1], for 0 <= r < off[B]
 __device__ __forceinline__ int sample_of_row(const long* __restrict__ off, int B, long r) {
@@ -52,11 +40,22 @@ __device__ __forceinline__ int sample_of_row(const long* __restrict__ off, int B
 // the grid of an elementwise grid-stride kernel over n >= 1 elements, 256 threads a workgroup
 static unsigned flat_grid(long n) { return (unsigned)std::min<long>((n + 255) / 256, 2048); }
 
+// The _affine losses (gnot_rel_l2_loss_affine, gnot_mse_loss_affine): pred is a normalised prediction and the
+// loss that of p' = pred * std[c] + mean[c] against the raw target, stats = {mean[C], std[C], rstd[C]}
+// (stats.hip).  The product and the sum are each rounded -- torch's pred * std + mean, bit for bit -- and
+// d loss / d pred = (d loss / d p') * std[c] is one more rounded product.  The partial and the gradient kernels
+// take the block as a template parameter pack, Stats: empty -- kernel<>, the plain loss, with the argument list
+// and so the code it had before there was anything else -- or one const float*.
+__device__ __forceinline__ float denormalised(float p, const float* __restrict__ stats, int C, int c) {
+  return __fadd_rn(mul_rn(p, stats[C + c]), stats[c]);
+}
+
 // partial[b][split][0..2C) = (sum (p-t)^2 [C], sum t^2 [C]) over the split's rows of sample b
+template <typename... Stats>
 __global__ void __launch_bounds__(256) rel_l2_partial_kernel(const float* __restrict__ pred,
                                                              const float* __restrict__ tgt,
                                                              const long* __restrict__ off, int C, int nsplit,
-                                                             float* __restrict__ partial) {
+                                                             float* __restrict__ partial, Stats... stats_arg) {
   __shared__ float red[256];
   const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
   const long r0 = off[b] + (long)split * kLossRows;
@@ -65,7 +64,9 @@ __global__ void __launch_bounds__(256) rel_l2_partial_kernel(const float* __rest
     float num = 0.f, den = 0.f;
     for (long r = r0 + threadIdx.x; r < r1; r += 256) {
       const float t = tgt[r * C + c];
-      const float d = pred[r * C + c] - t;
+      float d;
+      if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[r * C + c], (stats_arg, ...), C, c) - t;
+      else d = pred[r * C + c] - t;
       num = fmaf(d, d, num);
       den = fmaf(t, t, den);
     }
@@ -102,15 +103,22 @@ __global__ void __launch_bounds__(256) rel_l2_finish_kernel(const float* __restr
   if (threadIdx.x == 0) *loss = acc / (float)(B * C);
 }
 
+template <typename... Stats>
 __global__ void __launch_bounds__(256) rel_l2_grad_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                           const long* __restrict__ off, int B, int C,
                                                           const float* __restrict__ scale, float* __restrict__ dpred,
-                                                          long rows) {
+                                                          long rows, Stats... stats_arg) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= rows * C) return;
   const long r = i / C;
   const int c = (int)(i % C);
-  dpred[i] = (pred[i] - tgt[i]) * scale[sample_of_row(off, B, r) * C + c];
+  if constexpr (sizeof...(Stats) == 1) {
+    const float* __restrict__ stats = (stats_arg, ...);
+    const float g = (denormalised(pred[i], stats, C, c) - tgt[i]) * scale[sample_of_row(off, B, r) * C + c];
+    dpred[i] = mul_rn(g, stats[C + c]);
+  } else {
+    dpred[i] = (pred[i] - tgt[i]) * scale[sample_of_row(off, B, r) * C + c];
+  }
 }
 
 int rel_l2_splits(const long* off_host, int B) {
@@ -119,25 +127,35 @@ int rel_l2_splits(const long* off_host, int B) {
   return (int)((mx + kLossRows - 1) / kLossRows);
 }
 
-hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                         long rows, float* work, float* loss, float* dpred, hipStream_t s) {
+template <typename... Stats>
+static hipError_t launch_rel_l2_t(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
+                                  long rows, float* work, float* loss, float* dpred, hipStream_t s, Stats... stats) {
   float* partial = work;                                  // [B][nsplit][2C]
   float* scale = work + (size_t)B * nsplit * 2 * C;       // [B][C]
-  hipLaunchKernelGGL(rel_l2_partial_kernel, dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev, C, nsplit, partial);
+  hipLaunchKernelGGL(rel_l2_partial_kernel<Stats...>, dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev, C, nsplit,
+                     partial, stats...);
   hipLaunchKernelGGL(rel_l2_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)partial, B, C, nsplit, scale, loss);
   if (dpred && rows > 0)
-    hipLaunchKernelGGL(rel_l2_grad_kernel, dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s, pred, tgt,
-                       off_dev, B, C, (const float*)scale, dpred, rows);
+    hipLaunchKernelGGL(rel_l2_grad_kernel<Stats...>, dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s, pred,
+                       tgt, off_dev, B, C, (const float*)scale, dpred, rows, stats...);
   return hipGetLastError();
+}
+
+// stats == nullptr: the plain loss
+hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
+                         long rows, const float* stats, float* work, float* loss, float* dpred, hipStream_t s) {
+  return stats ? launch_rel_l2_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s, stats)
+               : launch_rel_l2_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s);
 }
 
 // ---------------------------------------------------------------- MSELoss (reference loss.py:4-12)
 // dgl AvgPooling of (p - t)^2 = per-sample mean over points, then the mean over (sample, channel); the
 // passes have the shape of the RelL2 ones above (which stay as they are, bit for bit).
 // partial[b][split][0..C) = sum (p-t)^2 over the split's rows of sample b
+template <typename... Stats>
 __global__ void __launch_bounds__(256) mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                           const long* __restrict__ off, int C, int nsplit,
-                                                          float* __restrict__ partial) {
+                                                          float* __restrict__ partial, Stats... stats_arg) {
   __shared__ float red[256];
   const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
   const long r0 = off[b] + (long)split * kLossRows;
@@ -145,7 +163,9 @@ __global__ void __launch_bounds__(256) mse_partial_kernel(const float* __restric
   for (int c = 0; c < C; ++c) {
     float num = 0.f;
     for (long r = r0 + threadIdx.x; r < r1; r += 256) {
-      const float d = pred[r * C + c] - tgt[r * C + c];
+      float d;
+      if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[r * C + c], (stats_arg, ...), C, c) - tgt[r * C + c];
+      else d = pred[r * C + c] - tgt[r * C + c];
       num = fmaf(d, d, num);
     }
     num = block_sum(num, red);
@@ -170,24 +190,42 @@ __global__ void __launch_bounds__(256) mse_finish_kernel(const float* __restrict
 }
 
 // d loss / d pred = 2 (p - t) / (B C N_b)
+template <typename... Stats>
 __global__ void __launch_bounds__(256) mse_grad_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                        const long* __restrict__ off, int B, int C,
-                                                       float* __restrict__ dpred, long rows) {
+                                                       float* __restrict__ dpred, long rows, Stats... stats_arg) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= rows * C) return;
   const int b = sample_of_row(off, B, i / C);
-  dpred[i] = (pred[i] - tgt[i]) * (2.0f / ((float)(B * C) * (float)(off[b + 1] - off[b])));
+  if constexpr (sizeof...(Stats) == 1) {
+    const float* __restrict__ stats = (stats_arg, ...);
+    const int c = (int)(i % C);
+    const float g = (denormalised(pred[i], stats, C, c) - tgt[i]) *
+                    (2.0f / ((float)(B * C) * (float)(off[b + 1] - off[b])));
+    dpred[i] = mul_rn(g, stats[C + c]);
+  } else {
+    dpred[i] = (pred[i] - tgt[i]) * (2.0f / ((float)(B * C) * (float)(off[b + 1] - off[b])));
+  }
 }
 
 // work: B*nsplit*C floats
-hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
-                      float* work, float* loss, float* dpred, hipStream_t s) {
-  hipLaunchKernelGGL(mse_partial_kernel, dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev, C, nsplit, work);
+template <typename... Stats>
+static hipError_t launch_mse_t(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
+                               long rows, float* work, float* loss, float* dpred, hipStream_t s, Stats... stats) {
+  hipLaunchKernelGGL(mse_partial_kernel<Stats...>, dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev, C, nsplit,
+                     work, stats...);
   hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)work, off_dev, B, C, nsplit, loss);
   if (dpred && rows > 0)
-    hipLaunchKernelGGL(mse_grad_kernel, dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s, pred, tgt, off_dev,
-                       B, C, dpred, rows);
+    hipLaunchKernelGGL(mse_grad_kernel<Stats...>, dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s, pred, tgt,
+                       off_dev, B, C, dpred, rows, stats...);
   return hipGetLastError();
+}
+
+// stats == nullptr: the plain loss
+hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
+                      const float* stats, float* work, float* loss, float* dpred, hipStream_t s) {
+  return stats ? launch_mse_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s, stats)
+               : launch_mse_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s);
 }
 
 // ---------------------------------------------------------------- global gradient norm and clip coefficient

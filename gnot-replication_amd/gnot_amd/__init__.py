@@ -6,9 +6,12 @@
                  n_input_functions).cuda()
 
 The training step around it lives in `gnot_amd.train` (`RelL2Loss`, `MSELoss`, `FlatAdamW` with optional
-global-norm gradient clipping, `OneCycle`, `fit`) and the multi-GPU glue in `gnot_amd.parallel`.
+global-norm gradient clipping, `OneCycle`, `fit`), datasets, loaders and unit-Gaussian normalisation
+(`Normalizer`, `DeviceDataset`, `DeviceLoader`) in `gnot_amd.data`, and the multi-GPU glue in
+`gnot_amd.parallel`.
 """
 from .model import GNOT, MLP, LinearAttention, HeterogeneousNormalizedAttentionBlock  # noqa: F401
 from . import _lib  # noqa: F401
+from .data import Normalizer  # noqa: F401
 
-__all__ = ["GNOT", "MLP", "LinearAttention", "HeterogeneousNormalizedAttentionBlock"]
+__all__ = ["GNOT", "MLP", "LinearAttention", "HeterogeneousNormalizedAttentionBlock", "Normalizer"]

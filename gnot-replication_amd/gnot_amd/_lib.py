@@ -34,6 +34,8 @@ EXPORTS = [
     "gnot_mse_work_floats", "gnot_mse_loss", "gnot_grad_clip_work_floats", "gnot_grad_clip", "gnot_adamw_step_clipped",
     "gnot_plan_set_grad_arena", "gnot_backward_ex", "gnot_grad_norm", "gnot_adamw_step_guarded",
     "gnot_ema_update", "gnot_adamw_step_ema", "gnot_gather_rows", "gnot_debug_gelu",
+    "gnot_channel_stats_work_floats", "gnot_channel_stats", "gnot_gather_rows_affine", "gnot_rel_l2_loss_affine",
+    "gnot_mse_loss_affine",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -64,7 +66,7 @@ def build(jobs=8, quiet=True):
 # every file the library's code depends on (csrc/Makefile's SRCS, its headers and its flags)
 SOURCES = ["Makefile", "gnot_common.h", "gnot_kernels.h", "x6_core.h", "pack.hip", "linear.hip", "linear2.hip",
            "chain.hip", "chain2.hip", "chainw.hip", "wgrad.hip", "state.hip", "attn.hip", "attn_mfma.hip", "misc.hip",
-           "train.hip", "gather.hip", "engine.cpp"]
+           "train.hip", "gather.hip", "stats.hip", "engine.cpp"]
 
 
 def source_hash():
@@ -134,6 +136,12 @@ def _declare(lib):
     lib.gnot_adamw_step_ema.argtypes = [P, P, P, P, P, i64, P, P, P, P]
     lib.gnot_gather_rows.argtypes = [P, i32, P, ctypes.POINTER(i64), i32, P, P]
     lib.gnot_debug_gelu.argtypes = [P, P, P, P, P, i64, P]
+    lib.gnot_channel_stats_work_floats.argtypes = [i64, i32]
+    lib.gnot_channel_stats_work_floats.restype = sz
+    lib.gnot_channel_stats.argtypes = [P, i64, i32, ctypes.c_float, P, P, P]
+    lib.gnot_gather_rows_affine.argtypes = [P, i32, P, ctypes.POINTER(i64), i32, P, P, P]
+    lib.gnot_rel_l2_loss_affine.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, P, P, P, P, P]
+    lib.gnot_mse_loss_affine.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, P, P, P, P, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p

@@ -9,6 +9,9 @@ cannot run code through it).  `collate_packed` is the packed-offsets batch the e
 reference's padded tensors exactly, for parity runs.  `synthetic_sample` / `write_ns2d` generate
 meshes in the same on-disk format.
 
+`Normalizer` holds per-channel statistics of a dataset's arrays (computed on the device, gnot_channel_stats)
+and applies unit-Gaussian normalisation in the loader, the losses and the checkpoint.
+
 `DeviceDataset` / `DeviceLoader` keep the whole dataset in device memory and assemble every packed batch
 there with one small kernel per array (libgnot_hip.so gnot_gather_rows), which also draws a per-mesh
 subsample of the query points (`points_per_mesh`) as a keyed permutation -- no reference counterpart
@@ -193,6 +196,184 @@ class DeviceDataset:
         return len(self.x_off) - 1
 
 
+# ------------------------------------------------------------------ unit-Gaussian normalisation
+def _block(mean, std, eps):
+    """a stats block [3, C] fp32 {mean, std, rstd} from host values, under gnot_channel_stats' rules: a constant
+    channel (std <= 1e-6 |mean|) gets std 0 and rstd 1, every other one rstd = 1 / (std + eps) in fp32"""
+    mean = torch.as_tensor(np.atleast_1d(np.asarray(mean, dtype=np.float64))).float()
+    std = torch.as_tensor(np.atleast_1d(np.asarray(std, dtype=np.float64))).float()
+    if mean.shape != std.shape or mean.dim() != 1:
+        raise ValueError("Normalizer: mean and std must be vectors of one length")
+    const = std <= 1e-6 * mean.abs()
+    std = torch.where(const, torch.zeros_like(std), std)
+    rstd = torch.where(const, torch.ones_like(std), 1.0 / (std + torch.tensor(eps, dtype=torch.float32)))
+    return torch.stack([mean, std, rstd]).contiguous()
+
+
+class Normalizer:
+    """Per-channel unit-Gaussian normalisation of a dataset's inputs and targets, as the original GNOT code
+    base's UnitTransformer does it ((v - mean) / (std + 1e-8), metric reported in physical units); the
+    replicated main.py trains on raw values.  One stats block per array -- `x`, `theta`, `y` and `fns[i]`, each a
+    [3, C] fp32 tensor {mean, std, rstd} on one device, the layout libgnot_hip.so's entries read:
+      fit(device_dataset)    the statistics of x_all, theta, every fn_all[i] and y_all, computed where the data
+                             lives (gnot_channel_stats: unbiased std, rstd = 1 / (std + eps), a constant channel
+                             std 0 / rstd 1); an array whose flag is off gets the identity block (mean 0, std 1,
+                             rstd 1), for which both transforms below return their argument's bits (but for the
+                             sign of a zero in decode)
+      from_stats(...)        the same from host (mean, std) pairs; needs no GPU
+      DeviceLoader(normalizer=)   x, theta and the input functions normalised as they are gathered
+                             (gnot_gather_rows_affine); y stays raw
+      encode_batch(batch)    the same arithmetic, (v - mean) * rstd, in torch ops on a collate_packed batch
+                             wherever it lives -- bit for bit the kernel's values
+      train.RelL2Loss(normalizer=) / MSELoss(normalizer=)   read the model's output as a normalised prediction
+                             and compute loss and metric in physical units (the _affine entries, `y` block)
+      decode(out)            out * std_y + mean_y, for inference on normalised weights
+      fold(state_dict, n_mlp_num_layers)   the statistics moved into the first and last Linears, so that the
+                             checkpoint maps raw inputs to physical outputs with the reference's keys alone
+    Out of scope: the point-sharded losses of parallel.py, padded batches (collate_padded), and per-rank
+    statistics (every rank fits the same whole dataset and so holds the same blocks)."""
+
+    def __init__(self, x, theta, y, fns=()):
+        self.x, self.theta, self.y, self.fns = x, theta, y, list(fns)
+        for b in self.blocks().values():
+            if b.dim() != 2 or b.shape[0] != 3 or b.dtype != torch.float32:
+                raise ValueError("Normalizer: a stats block is a [3, C] fp32 tensor {mean, std, rstd}")
+
+    def blocks(self):
+        """{entry name: block} in a fixed order: x, theta, y, fns.0, fns.1, ..."""
+        out = {"x": self.x, "theta": self.theta, "y": self.y}
+        out.update({f"fns.{i}": b for i, b in enumerate(self.fns)})
+        return out
+
+    @staticmethod
+    def identity(C, device="cpu"):
+        """the block that changes nothing: mean 0, std 1, rstd 1"""
+        return torch.tensor([[0.0] * C, [1.0] * C, [1.0] * C], dtype=torch.float32, device=device)
+
+    @classmethod
+    def fit(cls, dataset, x=True, theta=True, fns=True, y=True, eps=1e-8):
+        """Statistics over a DeviceDataset's arrays on its device (two small kernels per array on the current
+        stream, nothing read back)."""
+        if not dataset.x_all.is_cuda:
+            raise RuntimeError("gnot_amd.Normalizer.fit computes on a ROCm GPU only (libgnot_hip.so); "
+                               "from_stats builds one from host statistics")
+        lib = _lib.load()
+
+        def block(src, on):
+            rows, C = src.shape
+            if not on:
+                return cls.identity(C, src.device)
+            stats = torch.empty((3, C), dtype=torch.float32, device=src.device)
+            work = torch.empty(lib.gnot_channel_stats_work_floats(rows, C), dtype=torch.float32, device=src.device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+            _lib.check(lib.gnot_channel_stats(src.data_ptr(), rows, C, eps, work.data_ptr(), stats.data_ptr(), stream))
+            return stats
+
+        return cls(block(dataset.x_all, x), block(dataset.theta, theta), block(dataset.y_all, y),
+                   [block(f, fns) for f in dataset.fn_all])
+
+    @classmethod
+    def from_stats(cls, x, theta, y, fns=(), eps=1e-8, device="cpu"):
+        """From host statistics: every argument a (mean, std) pair of vectors (numpy, lists or numbers; float64
+        is rounded to fp32 once), fns a list of such pairs.  Needs no GPU."""
+        mk = lambda ms: _block(ms[0], ms[1], eps).to(device)
+        return cls(mk(x), mk(theta), mk(y), [mk(f) for f in fns])
+
+    def to(self, device):
+        """the same statistics on `device` (self if they are there already)"""
+        device = torch.device(device)
+        if all(b.device == device for b in self.blocks().values()):
+            return self
+        return Normalizer(self.x.to(device), self.theta.to(device), self.y.to(device), [f.to(device) for f in self.fns])
+
+    def state_dict(self):
+        """plain CPU fp32 tensors (copies): {"x", "theta", "y": [3, C], "fns": [[3, F], ...]}; loadable with
+        weights_only=True"""
+        cp = lambda b: b.detach().cpu().clone()
+        return {"x": cp(self.x), "theta": cp(self.theta), "y": cp(self.y), "fns": [cp(f) for f in self.fns]}
+
+    @classmethod
+    def from_state_dict(cls, sd, device="cpu"):
+        mv = lambda b: b.detach().clone().float().to(device)
+        return cls(mv(sd["x"]), mv(sd["theta"]), mv(sd["y"]), [mv(f) for f in sd["fns"]])
+
+    def mismatch(self, other):
+        """the first entry (blocks' names) whose statistics differ bitwise from `other`'s -- a Normalizer or a
+        state_dict() -- or "fns" for another number of input functions; None: equal.  Compared on the host."""
+        a = self.state_dict()
+        b = other.state_dict() if isinstance(other, Normalizer) else other
+        if len(a["fns"]) != len(b["fns"]):
+            return "fns"
+        pairs = [(k, a[k], b[k]) for k in ("x", "theta", "y")] + \
+                [(f"fns.{i}", p, q) for i, (p, q) in enumerate(zip(a["fns"], b["fns"]))]
+        for name, p, q in pairs:
+            if p.shape != q.shape or not torch.equal(p.view(torch.int32), q.float().view(torch.int32)):
+                return name
+        return None
+
+    @staticmethod
+    def _encode(v, block):
+        b = block.to(device=v.device, dtype=v.dtype)
+        return (v - b[0]) * b[2]
+
+    def encode_batch(self, batch):
+        """A collate_packed batch with x, theta and every input function normalised, (v - mean) * rstd in torch
+        ops on the tensors' own device and dtype (fp32: gnot_gather_rows_affine's bits); y and the offsets are
+        passed through.  A padded batch (collate_padded) is refused: its pad rows would stop being zeros."""
+        if "counts" in batch:
+            raise ValueError("Normalizer.encode_batch takes packed batches (collate_packed) only")
+        if len(batch["fns"]) != len(self.fns):
+            raise ValueError(f"Normalizer.encode_batch: {len(batch['fns'])} input functions in the batch, "
+                             f"{len(self.fns)} in the statistics")
+        return dict(batch, x=self._encode(batch["x"], self.x), theta=self._encode(batch["theta"], self.theta),
+                    fns=[self._encode(f, b) for f, b in zip(batch["fns"], self.fns)])
+
+    def decode(self, out):
+        """a normalised prediction [..., out_dim] in physical units: out * std_y + mean_y"""
+        b = self.y.to(device=out.device, dtype=out.dtype)
+        return out * b[1] + b[0]
+
+    def fold(self, state_dict, n_mlp_num_layers, dtype=torch.float32):
+        """A new state dict (the model and `state_dict` are left alone) whose network takes raw inputs and
+        returns physical outputs, with the reference's keys and nothing else:
+          first Linear of each encoder, W' = W diag(r), b' = b - W' m, with (m, r) = (mean, rstd) of
+            x.layers.0                     the x and theta blocks concatenated (the encoder's input is [x, theta])
+            gating.layers.0                the x block
+            input_func_mlps.i.layers.0     input function i's block
+          last Linear of out (out.layers.{2 n_mlp_num_layers}): W' = diag(std_y) W, b' = std_y b + mean_y.
+        Computed in float64 on the host and rounded to `dtype` once.  In exact arithmetic the folded network on
+        raw inputs IS decode(network(encode(inputs))); in fp32 the first pre-activation now takes W' v - W' m
+        as a difference of two numbers |mean| / std times larger than itself, so folding costs about
+        (|mean| / std) 2^-24 relative there (x in [100, 108]: 3e-6).  Evaluate with the unfolded weights and
+        the normalizer where that matters."""
+        sd = {k: v.detach().cpu().clone() for k, v in state_dict.items()}
+        f64 = lambda t: t.detach().cpu().double()
+
+        def first(prefix, blocks):
+            m = torch.cat([f64(b[0]) for b in blocks])
+            r = torch.cat([f64(b[2]) for b in blocks])
+            W = f64(sd[prefix + ".layers.0.weight"])
+            if W.shape[1] != m.numel():
+                raise ValueError(f"Normalizer.fold: {prefix}.layers.0 takes {W.shape[1]} channels, the statistics "
+                                 f"hold {m.numel()}")
+            W2 = W * r[None, :]
+            sd[prefix + ".layers.0.weight"] = W2.to(dtype)
+            sd[prefix + ".layers.0.bias"] = (f64(sd[prefix + ".layers.0.bias"]) - W2 @ m).to(dtype)
+
+        first("x", [self.x, self.theta])
+        first("gating", [self.x])
+        for i, b in enumerate(self.fns):
+            first(f"input_func_mlps.{i}", [b])
+        last = f"out.layers.{2 * max(int(n_mlp_num_layers), 1)}"
+        mean, std = f64(self.y[0]), f64(self.y[1])
+        W = f64(sd[last + ".weight"])
+        if W.shape[0] != std.numel():
+            raise ValueError(f"Normalizer.fold: {last} has {W.shape[0]} outputs, the statistics hold {std.numel()}")
+        sd[last + ".weight"] = (std[:, None] * W).to(dtype)
+        sd[last + ".bias"] = (std * f64(sd[last + ".bias"]) + mean).to(dtype)
+        return sd
+
+
 class DeviceLoader:
     """A loader of packed batches over a DeviceDataset: iterable, with __len__, yielding collate_packed's dict
     (x, x_off, y, theta, fns, fn_offs; tensors on the device, offsets host lists), every array assembled on the
@@ -208,10 +389,15 @@ class DeviceLoader:
     The epoch's tables reach the device as one copy from pinned memory (non_blocking); iterating performs no
     pageable copy and no device-to-host read, and every batch is a fresh allocation of the stream-ordered
     caching allocator, so a step still in flight keeps its batch.
+    normalizer: a Normalizer over this dataset's arrays; x, theta and every input function are then gathered
+    through gnot_gather_rows_affine -- normalised in the copy, bit for bit Normalizer.encode_batch of the plain
+    batch -- and y stays raw (plain gather), for a loss that holds the same normalizer.  None (default): the
+    calls above, unchanged.
     Padded batches (collate_padded) and slicing a loader over ranks are out of scope: packed batches, one
     process's whole dataset."""
 
-    def __init__(self, dataset, batch_size, shuffle=False, drop_last=False, points_per_mesh=None, generator=None):
+    def __init__(self, dataset, batch_size, shuffle=False, drop_last=False, points_per_mesh=None, generator=None,
+                 normalizer=None):
         if int(batch_size) < 1:
             raise ValueError("batch_size must be at least 1")
         if points_per_mesh is not None and int(points_per_mesh) < 1:
@@ -219,6 +405,13 @@ class DeviceLoader:
         self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), bool(shuffle), bool(drop_last)
         self.points_per_mesh = None if points_per_mesh is None else int(points_per_mesh)
         self.generator = generator
+        self.normalizer = normalizer
+        if normalizer is not None:
+            have = [b.shape[1] for b in (normalizer.x, normalizer.theta, normalizer.y, *normalizer.fns)]
+            need = [t.shape[1] for t in (dataset.x_all, dataset.theta, dataset.y_all, *dataset.fn_all)]
+            if have != need:
+                raise ValueError(f"DeviceLoader: the normalizer's channels (x, theta, y, fns...) are {have}, "
+                                 f"the dataset's {need}")
 
     def __len__(self):
         S = len(self.dataset)
@@ -230,14 +423,20 @@ class DeviceLoader:
         return gather_tables(ds.x_off, ds.fn_offs, self.batch_size, self.shuffle, self.drop_last, self.points_per_mesh,
                              self.generator)
 
-    def _gather(self, src, rows, table_dev, rows_out):
-        """the [rows_out, C] rows of src that the table selects (host rows `rows`, the same on the device)"""
+    def _gather(self, src, rows, table_dev, rows_out, stats=None):
+        """the [rows_out, C] rows of src that the table selects (host rows `rows`, the same on the device);
+        stats: a stats block on src's device, the rows are normalised with it as they are copied"""
         dst = torch.empty((rows_out, src.shape[1]), dtype=torch.float32, device=src.device)
         if rows_out:
             host = (ctypes.c_int64 * (len(rows) * GATHER_COLS))(*[v for r in rows for v in r])
             stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
-            _lib.check(_lib.load().gnot_gather_rows(src.data_ptr(), src.shape[1], table_dev.data_ptr(), host, len(rows),
-                                                    dst.data_ptr(), stream))
+            if stats is None:
+                rc = _lib.load().gnot_gather_rows(src.data_ptr(), src.shape[1], table_dev.data_ptr(), host, len(rows),
+                                                  dst.data_ptr(), stream)
+            else:
+                rc = _lib.load().gnot_gather_rows_affine(src.data_ptr(), src.shape[1], table_dev.data_ptr(), host,
+                                                         len(rows), stats.data_ptr(), dst.data_ptr(), stream)
+            _lib.check(rc)
         return dst
 
     def __iter__(self):
@@ -247,6 +446,8 @@ class DeviceLoader:
         batches = self.epoch_tables()
         if not batches:
             return
+        nz = None if self.normalizer is None else self.normalizer.to(ds.device)
+        sx, sth, sfn = (None, None, [None] * len(ds.fn_all)) if nz is None else (nz.x, nz.theta, nz.fns)
         # every table of the epoch in one pinned tensor and one asynchronous copy; torch's host allocator keeps
         # the pinned block from reuse until the copy has executed
         rows = [r for b in batches for t in [b["x"], b["theta"]] + b["fns"] for r in t]
@@ -257,11 +458,11 @@ class DeviceLoader:
         for b in batches:
             B = len(b["samples"])
             dev_table = lambda k: tables[r0 + k * B:r0 + (k + 1) * B]      # the batch's tables: x, theta, fns...
-            out = dict(x=self._gather(ds.x_all, b["x"], dev_table(0), b["x_off"][-1]), x_off=b["x_off"],
+            out = dict(x=self._gather(ds.x_all, b["x"], dev_table(0), b["x_off"][-1], sx), x_off=b["x_off"],
                        y=self._gather(ds.y_all, b["x"], dev_table(0), b["x_off"][-1]),
-                       theta=self._gather(ds.theta, b["theta"], dev_table(1), B),
-                       fns=[self._gather(f, t, dev_table(2 + i), o[-1])
-                            for i, (f, t, o) in enumerate(zip(ds.fn_all, b["fns"], b["fn_offs"]))],
+                       theta=self._gather(ds.theta, b["theta"], dev_table(1), B, sth),
+                       fns=[self._gather(f, t, dev_table(2 + i), o[-1], st)
+                            for i, (f, t, o, st) in enumerate(zip(ds.fn_all, b["fns"], b["fn_offs"], sfn))],
                        fn_offs=b["fn_offs"])
             r0 += (2 + len(ds.fn_all)) * B
             yield out

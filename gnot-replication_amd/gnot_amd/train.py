@@ -24,6 +24,10 @@
 * `WeightEMA` and `FlatAdamW(ema_decay=...)` / `fit(ema_decay=...)` -- an exponential moving average of the
   parameters, updated inside the AdamW kernel (gnot_adamw_step_ema) and evaluated and checkpointed in place
   of the raw weights (`WeightEMA.swapped()`).
+* `RelL2Loss(normalizer=)` / `MSELoss(normalizer=)` / `fit(normalizer=)` -- training on unit-Gaussian inputs and
+  targets (data.Normalizer): the losses de-normalise the prediction inside their kernels
+  (gnot_rel_l2_loss_affine / gnot_mse_loss_affine), the statistics travel in the state file, and the best
+  checkpoint is written with them folded into its first and last Linears.
 """
 import contextlib
 import ctypes
@@ -37,37 +41,45 @@ from . import _lib
 
 # ------------------------------------------------------------------ loss (loss.py:14-23)
 class _NativeLoss(torch.autograd.Function):
-    """loss and d loss / d pred in one pass of the native entry `entry` (gnot_rel_l2_loss or gnot_mse_loss)"""
+    """loss and d loss / d pred in one pass of the native entry `entry` (gnot_rel_l2_loss or gnot_mse_loss);
+    stats: the targets' stats block on pred's device, and `entry` is then the _affine entry that takes it"""
 
     @staticmethod
-    def forward(ctx, pred, tgt, off_dev, off_host, work, entry):
+    def forward(ctx, pred, tgt, off_dev, off_host, work, entry, stats=None):
         B = len(off_host) - 1
         C = pred.shape[1]
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
         dpred = torch.empty_like(pred) if pred.requires_grad else None
         oh = (ctypes.c_int64 * (B + 1))(*off_host)
         s = ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-        _lib.check(getattr(_lib.load(), entry)(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, C,
-                                               work.data_ptr(), loss.data_ptr(),
-                                               dpred.data_ptr() if dpred is not None else None, s))
+        tail = (work.data_ptr(), loss.data_ptr(), dpred.data_ptr() if dpred is not None else None, s)
+        if stats is not None:
+            tail = (stats.data_ptr(),) + tail
+        _lib.check(getattr(_lib.load(), entry)(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, C, *tail))
         ctx.save_for_backward(dpred) if dpred is not None else None
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
-        return dpred * g, None, None, None, None, None
+        return dpred * g, None, None, None, None, None, None
 
 
 class RelL2Loss(torch.nn.Module):
     """mean over (sample, channel) of sqrt(sum_n (p - t)^2 / sum_n t^2) (reference loss.py:14-23).
-    The dgl graph argument of the reference becomes the packed offsets x_off [B+1] (host list)."""
+    The dgl graph argument of the reference becomes the packed offsets x_off [B+1] (host list).
+    normalizer (a data.Normalizer): `predictions` is read as a NORMALISED prediction and compared with the raw
+    targets in physical units -- the loss of predictions * std_y + mean_y, in one pass of the _affine entry
+    (no de-normalised copy of the prediction, the gradient scaled by std_y in the same kernel).  None
+    (default): the plain entry.  The point-sharded losses of parallel.py take no normalizer."""
 
     _entry, _work_floats = "gnot_rel_l2_loss", "gnot_rel_l2_work_floats"
 
-    def __init__(self):
+    def __init__(self, normalizer=None):
         super().__init__()
         self._cache = {}
+        self.normalizer = normalizer
+        self._stats = None         # the normalizer's y block on the predictions' device
 
     def forward(self, x_off, predictions, targets):
         if not predictions.is_cuda:
@@ -83,8 +95,16 @@ class RelL2Loss(torch.nn.Module):
             self._cache = {key: (pinned.to(predictions.device, non_blocking=True),
                                  torch.empty(n, dtype=torch.float32, device=predictions.device), pinned)}
         off_dev, work, _ = self._cache[key]
+        if self.normalizer is None:
+            return _NativeLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0],
+                                     work, self._entry)
+        if self._stats is None or self._stats.device != predictions.device:
+            self._stats = self.normalizer.y.to(predictions.device).contiguous()
+        if self._stats.shape[1] != predictions.shape[1]:
+            raise ValueError(f"{type(self).__name__}: the normalizer's y statistics hold {self._stats.shape[1]} "
+                             f"channels, the prediction {predictions.shape[1]}")
         return _NativeLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0], work,
-                                 self._entry)
+                                 self._entry + "_affine", self._stats)
 
 
 class MSELoss(RelL2Loss):
@@ -381,9 +401,13 @@ class FlatAdamW:
 
 
 # ------------------------------------------------------------------ driver (main.py:55-153)
-def save_checkpoint(model, path):
-    """torch.save(model.state_dict()) exactly as main.py:151 (reference-compatible keys/shapes)."""
-    torch.save(model.state_dict(), path)
+def save_checkpoint(model, path, normalizer=None):
+    """torch.save(model.state_dict()) exactly as main.py:151 (reference-compatible keys/shapes).
+    normalizer: the model was trained on normalised data; the statistics are folded into its first and last
+    Linears (Normalizer.fold), so the file predicts physical outputs from raw inputs -- in gnot_amd.GNOT and in
+    the reference module alike -- and holds the reference's keys and nothing else."""
+    sd = model.state_dict()
+    torch.save(sd if normalizer is None else normalizer.fold(sd, model._cfg["n_mlp_num_layers"]), path)
 
 
 def load_checkpoint(model, path):
@@ -426,19 +450,22 @@ def restore_rng_state(state, train_loader=None):
 
 
 def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, hist_test, args, train_loader=None,
-                        ema_args=None):
+                        ema_args=None, normalizer=None):
     """Everything fit needs to continue a run bit for bit, in one torch.save of tensors (on the host) and plain
     Python values, readable with weights_only=True: the model state_dict (reference keys), the optimizer's
     and the schedule's state_dict(), the next epoch, the best metric, both histories, the host random state
     (rng_state) and the trajectory arguments `args` (TRAJECTORY_ARGS); with a weight average also `ema_args`
     (fit's ema_decay / ema_warmup; the average itself travels in the optimizer's state, the model entry holds
-    the raw weights).  Written under a temporary name in
+    the raw weights); with a normalizer its statistics ("normalizer": Normalizer.state_dict(); the model
+    entry holds the unfolded weights, which take normalised inputs).  Written under a temporary name in
     the same directory and moved into place with os.replace: a kill in mid-write leaves the previous file."""
     state = {"model": _cpu(model.state_dict()), "optimizer": _cpu(opt.state_dict()), "schedule": sched.state_dict(),
              "next_epoch": int(next_epoch), "best": float(best), "hist_train": [float(v) for v in hist_train],
              "hist_test": [float(v) for v in hist_test], "rng": rng_state(train_loader), "args": dict(args)}
     if ema_args is not None:
         state["ema_args"] = dict(ema_args)
+    if normalizer is not None:
+        state["normalizer"] = normalizer.state_dict()
     tmp = f"{path}.tmp{os.getpid()}"
     try:
         torch.save(state, tmp)
@@ -458,11 +485,18 @@ def _to(batch, dev):
             batch["fn_offs"], batch["y"].to(dev))
 
 
-def _forward_batch(model, batch, dev):
+def _forward_batch(model, batch, dev, encoder=None):
     """(prediction [sum N, out], packed offsets, target) of one batch.  Packed batches (collate_packed)
     go through forward_packed; padded batches (collate_padded) through the reference calling
     convention `model(x, theta, input_functions)` (main.py:84) and are un-padded with the real point
-    counts (main.py:87-89) -- the pad rows still enter the attention sums, exactly as in main.py."""
+    counts (main.py:87-89) -- the pad rows still enter the attention sums, exactly as in main.py.
+    encoder: a data.Normalizer whose encode_batch the (packed) batch still needs, applied on the device."""
+    if encoder is not None:
+        if "counts" in batch:
+            raise ValueError("normalisation takes packed batches (collate_packed) only")
+        x, x_off, theta, fns, fn_offs, y = _to(batch, dev)
+        enc = encoder.encode_batch(dict(x=x, theta=theta, fns=fns))
+        return model.forward_packed(enc["x"], x_off, enc["theta"], enc["fns"], fn_offs), x_off, y
     if "counts" in batch:
         x = batch["x"].to(dev)
         fns = batch["fns"].to(dev) if batch["fns"] is not None else None
@@ -482,16 +516,52 @@ def _read_back(losses):
     return torch.stack(losses).tolist() if losses else []
 
 
-def evaluate(model, loader, loss_fn=None):
+def _check_normalizer(held, normalizer, who):
+    """ValueError unless `held` (what a loss or a loader holds) and `normalizer` (what the call was given) are
+    both None or carry the same statistics bit for bit.  Host comparisons only."""
+    if held is None and normalizer is None:
+        return
+    if held is None or normalizer is None:
+        raise ValueError(f"{who} holds {'no' if held is None else 'a'} normalizer, this call has "
+                         f"{'none' if normalizer is None else 'one'}")
+    bad = normalizer.mismatch(held)
+    if bad is not None:
+        raise ValueError(f"{who} holds a normalizer with other statistics than this call's (entry {bad!r})")
+
+
+_NO_ATTR = object()
+
+
+def _batch_encoder(loader, normalizer, who):
+    """The normalizer whose encode_batch `loader`'s batches still need: None for a loader that has a
+    `.normalizer` attribute (data.DeviceLoader normalises as it gathers) -- it must then hold the call's
+    statistics, else ValueError -- and `normalizer` itself for every other loader."""
+    held = getattr(loader, "normalizer", _NO_ATTR)
+    if held is _NO_ATTR:
+        return normalizer
+    _check_normalizer(held, normalizer, who)
+    return None
+
+
+def evaluate(model, loader, loss_fn=None, normalizer=None):
     """main.py:108-147: mean RelL2 over the test batches, no_grad (no activations kept).  Batches from
     collate_padded reproduce main.py's padded evaluation; collate_packed batches the unpadded one.
-    The batch losses stay on the device and are read once, behind the last batch."""
-    loss_fn = loss_fn or RelL2Loss()
+    The batch losses stay on the device and are read once, behind the last batch.
+    normalizer: the model takes normalised inputs and returns normalised predictions (fit's normalizer); the
+    metric is in physical units.  loss_fn, if given, must hold the same normalizer, and so must a
+    data.DeviceLoader; batches of any other loader are encoded on the device (Normalizer.encode_batch)."""
+    loss_fn = loss_fn or RelL2Loss(normalizer)
+    _check_normalizer(getattr(loss_fn, "normalizer", None), normalizer, "evaluate: loss_fn")
+    return _evaluate(model, loader, loss_fn, _batch_encoder(loader, normalizer, "evaluate: the loader"))
+
+
+def _evaluate(model, loader, loss_fn, encoder):
+    """evaluate behind its checks; encoder: _batch_encoder's answer for this loader"""
     dev = next(model.parameters()).device
     vals = []
     with torch.no_grad():
         for batch in loader:
-            pred, off, y = _forward_batch(model, batch, dev)
+            pred, off, y = _forward_batch(model, batch, dev, encoder)
             vals.append(loss_fn(off, pred, y))
     vals = _read_back(vals)
     return sum(vals) / max(len(vals), 1)
@@ -527,14 +597,14 @@ def _grouped(loader, k):
         yield group
 
 
-def _accum_step(model, eng, opt, loss_fn, group, dev):
+def _accum_step(model, eng, opt, loss_fn, group, dev, encoder=None):
     """One optimizer step on a group of micro-batches (fit's accum_steps): returns the micro-batches' losses
     (0-d device tensors, nothing read back) and their weights B_i / sum B; the step's loss is
     sum_i (B_i / sum B) loss_i."""
     _, (weights,) = accum_groups([_batch_samples(b) for b in group], len(group))
     vals = []
     for i, (batch, w) in enumerate(zip(group, weights)):
-        pred, off, y = _forward_batch(model, batch, dev)
+        pred, off, y = _forward_batch(model, batch, dev, encoder)
         loss = loss_fn(off, pred, y)
         # the first micro-batch overwrites the arena (no clear), the others add; only the last one reduces
         with model.backward_options(accumulate=i > 0, reduce=i == len(group) - 1):
@@ -546,7 +616,7 @@ def _accum_step(model, eng, opt, loss_fn, group, dev):
 
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
         log=print, loss_fn=None, max_grad_norm=None, accum_steps=1, skip_nonfinite=False, state_path=None,
-        resume=False, ema_decay=None, ema_warmup=True):
+        resume=False, ema_decay=None, ema_warmup=True, normalizer=None):
     """The reference training loop (main.py:50-153): AdamW(lr) + OneCycleLR(max_lr=lr, steps_per_epoch,
     epochs), RelL2 loss, per-epoch test metric and best checkpoint.  With per_epoch_schedule=True the
     schedule is stepped once per epoch, as main.py:106 does.  The loaders decide the batch form:
@@ -579,6 +649,18 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     parameters: no collective).  The state file keeps the raw weights, carries the average inside the
     optimizer state and names the two arguments in its own entry, "ema_args"; resume refuses a file whose
     entry differs from this call's, an absent one included.  None (default): raw weights throughout.
+    normalizer (a data.Normalizer): train on unit-Gaussian inputs and targets.  The model sees normalised x,
+    theta and input functions and its output is read as a normalised prediction; both losses -- the training
+    loss and the RelL2 test metric -- compare it with the raw targets in physical units (RelL2Loss /
+    MSELoss(normalizer=)).  A loss_fn passed in must hold the same normalizer.  A data.DeviceLoader (train or
+    test) must hold one with equal statistics and normalises as it gathers; the batches of every other loader
+    are encoded on the device (Normalizer.encode_batch, the same bits).  Anything else is a ValueError, raised
+    before any GPU work.  The best checkpoint is written folded (Normalizer.fold; with ema_decay the averaged
+    weights are the ones folded), so it predicts physical outputs from raw inputs with the reference's keys.
+    The state file keeps the unfolded weights and the statistics in an entry of its own, "normalizer"; resume
+    refuses a file whose statistics differ, one that has the entry when this call has no normalizer, and one
+    that lacks it when this call has one.  Padded batches and the point-sharded losses are out of scope.
+    None (default): raw data, every call what it was.
     No step reads its loss back: every step's 0-d loss (with accum_steps, every micro-batch's) stays on the
     device and the epoch reads them all at its end, then does the host arithmetic above on those fp32 values;
     with a loader whose batches are on the device already (data.DeviceLoader) the host runs ahead of the GPU
@@ -589,7 +671,10 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
         raise ValueError("accum_steps must be >= 1")
     if resume and not state_path:
         raise ValueError("resume needs a state_path")
-    loss_fn = loss_fn or RelL2Loss()
+    loss_fn = loss_fn or RelL2Loss(normalizer)
+    _check_normalizer(getattr(loss_fn, "normalizer", None), normalizer, "fit: loss_fn")
+    enc_train = _batch_encoder(train_loader, normalizer, "fit: train_loader")
+    enc_test = None if test_loader is None else _batch_encoder(test_loader, normalizer, "fit: test_loader")
     steps_per_epoch = -(-len(train_loader) // accum_steps)
     args = dict(epochs=int(epochs), lr=float(lr), steps_per_epoch=steps_per_epoch, accum_steps=accum_steps,
                 per_epoch_schedule=bool(per_epoch_schedule),
@@ -609,6 +694,14 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             if stored.get(k) != (ema_args or {}).get(k):
                 raise ValueError(f"fit(resume=True): {state_path} was written with {k}={stored.get(k)!r}, "
                                  f"this call has {k}={(ema_args or {}).get(k)!r}")
+        stored = state.get("normalizer")
+        if (stored is None) != (normalizer is None):
+            raise ValueError(f"fit(resume=True): {state_path} "
+                             + ("has no normalizer entry, this call has a normalizer" if stored is None
+                                else "has a normalizer entry, this call has no normalizer"))
+        if normalizer is not None and normalizer.mismatch(stored) is not None:
+            raise ValueError(f"fit(resume=True): {state_path} was written with other statistics in its normalizer "
+                             f"entry ({normalizer.mismatch(stored)!r} differs from this call's)")
         model.load_state_dict(state["model"])       # before the parameters move into the flat arena
     flat = flatten_parameters(model)
     sched = OneCycle(lr, epochs, steps_per_epoch)
@@ -621,7 +714,7 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     eng = model.engine()
     prev = eng.param_grads
     eng.param_grads = False          # FlatAdamW reads the gradient arena; no .grad copies
-    metric = loss_fn if type(loss_fn) is RelL2Loss else RelL2Loss()
+    metric = loss_fn if type(loss_fn) is RelL2Loss else RelL2Loss(normalizer)
     best, hist_train, hist_test, first, skipped = float("inf"), [], [], 0, 0
     if state is not None:
         opt.load_state_dict(state["optimizer"])
@@ -634,7 +727,7 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             losses = []
             if accum_steps == 1:
                 for batch in train_loader:
-                    pred, off, y = _forward_batch(model, batch, dev)
+                    pred, off, y = _forward_batch(model, batch, dev, enc_train)
                     loss = loss_fn(off, pred, y)
                     loss.backward()
                     opt.step(eng.grad_flat)
@@ -645,7 +738,7 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             else:
                 steps = []
                 for group in _grouped(train_loader, accum_steps):
-                    steps.append(_accum_step(model, eng, opt, loss_fn, group, dev))
+                    steps.append(_accum_step(model, eng, opt, loss_fn, group, dev, enc_train))
                     if not per_epoch_schedule:
                         sched.step()
                 vals = iter(_read_back([l for ls, _ in steps for l in ls]))
@@ -664,15 +757,15 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             if test_loader is not None:
                 # with ema_decay the metric and the checkpoint see the averaged weights
                 with opt.ema.swapped() if opt.ema is not None else contextlib.nullcontext():
-                    res = evaluate(model, test_loader, metric)
+                    res = _evaluate(model, test_loader, metric, enc_test)
                     hist_test.append(res)
                     log(f"Epoch {epoch}, Test Metric: {res}")
                     if res < best and checkpoint:
                         best = res
-                        save_checkpoint(model, checkpoint)
+                        save_checkpoint(model, checkpoint, normalizer)
             if state_path:       # outside the swap: the raw weights, the average inside the optimizer state
                 save_training_state(state_path, model, opt, sched, epoch + 1, best, hist_train, hist_test, args,
-                                    train_loader, ema_args)
+                                    train_loader, ema_args, normalizer)
     finally:
         eng.param_grads = prev       # ordinary autograd use after fit() gets .grad again
         if accum_steps > 1:

@@ -342,6 +342,47 @@ int gnot_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* 
 int gnot_gather_rows(const float* src, int C, const int64_t* table_dev, const int64_t* table_host, int B, float* dst,
                      void* stream);
 
+/* Unit-Gaussian normalisation of inputs and targets (the original GNOT code's UnitTransformer,
+ * (x - mean) / (std + 1e-8) per channel; the replicated main.py trains on raw values).  A "stats block" for C
+ * channels is a DEVICE array of 3 C floats, {mean[C], std[C], rstd[C]}.
+ *
+ * gnot_channel_stats fills one from src [rows, C] (fp32, device): mean[c], the unbiased standard deviation
+ * std[c] (divisor rows - 1, as torch.std) and rstd[c] = 1 / (std[c] + eps).  A channel counts as constant and
+ * gets std[c] = 0, rstd[c] = 1 -- both transforms then only shift it -- when rows == 1 or
+ * std[c] <= 1e-6 |mean[c]| (std == 0, and the fp32 noise a truly constant channel leaves).
+ * The variance is not taken as E[x^2] - E[x]^2 of raw values: slices of 4096 rows are each reduced about
+ * their own mean in two passes and merged exactly (Chan et al.), every difference between nearby values, so
+ * a channel like 1e4 + N(0, 1) keeps std to fp32 rounding.  Two fixed-order reduction stages, no atomics: the
+ * same arguments give the same bits on every run.  work: device scratch of
+ * gnot_channel_stats_work_floats(rows, C) floats (a function of rows and C alone; 0 for arguments out of
+ * range).  1 <= rows < 2^31, C >= 1.  GNOT_E_INVALID before any launch for: null pointers; rows < 1 or
+ * rows >= 2^31; C < 1; eps negative or not finite.  Two kernel launches; stateless, stream-ordered, no
+ * allocation, capturable. */
+size_t gnot_channel_stats_work_floats(int64_t rows, int C);
+int gnot_channel_stats(const float* src, int64_t rows, int C, float eps, float* work, float* stats, void* stream);
+
+/* gnot_gather_rows with the normalisation applied as the rows are copied: the same table, validation and
+ * permutation, and every copied value s of channel c is written as (s - mean[c]) * rstd[c] from `stats` (a
+ * stats block for C channels).  The difference and the product are each rounded to fp32, so dst holds, bit
+ * for bit, what gnot_gather_rows followed by torch's (g - mean) * rstd gives; a block of mean 0, rstd 1
+ * reproduces the plain gather.  A null stats is GNOT_E_INVALID.  One kernel launch; stateless, stream-ordered,
+ * no allocation. */
+int gnot_gather_rows_affine(const float* src, int C, const int64_t* table_dev, const int64_t* table_host, int B,
+                            const float* stats, float* dst, void* stream);
+
+/* gnot_rel_l2_loss / gnot_mse_loss of a NORMALISED prediction against the RAW target: the loss of
+ * p' = pred * std[c] + mean[c] (out_stats: the targets' stats block for C channels), the product and the sum
+ * each rounded to fp32, and, if dpred != NULL, d loss / d pred = ((p' - t) * scale[b, c]) * std[c] with the last
+ * product rounded on its own.  Loss and gradient are bit for bit the plain entry applied to torch's
+ * pred * std + mean, the gradient then multiplied by std -- without the two elementwise passes and the two
+ * prediction-sized temporaries.  Same arguments otherwise, the same work sizes
+ * (gnot_rel_l2_work_floats / gnot_mse_work_floats), the same refusals; a null out_stats is GNOT_E_INVALID. */
+int gnot_rel_l2_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
+                            int B, int C, const float* out_stats, float* work, float* loss, float* dpred,
+                            void* stream);
+int gnot_mse_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B,
+                         int C, const float* out_stats, float* work, float* loss, float* dpred, void* stream);
+
 /* Live kernel timing for the bench's roofline: while enabled, every launch of kernel class `kind`
  * ("moe_fwd" fused expert chains forward, "moe_bwd" their backward, "wgrad" weight-gradient GEMMs;
  * "" disables) is bracketed by hipEvents on its stream.  gnot_profile_read synchronizes on those

@@ -7,12 +7,14 @@
     host           the same loader on this tree (the loss is read back once per epoch instead of per step)
     device         fit over a DeviceLoader on this tree (the dataset in device memory, batches gathered there)
     device_sub     the same with points_per_mesh (--points-per-mesh, default 2500)
+    device_norm    `device` with unit-Gaussian normalisation: Normalizer.fit over the dataset (before the warm-up
+                   epoch), DeviceLoader(normalizer=) and RelL2Loss(normalizer=)
 
 Every arm runs in a process of its own (one warm-up epoch, then --epochs timed ones, wall time from one
 epoch's end to the next, each behind a device synchronise); the arms are interleaved and the round repeated
 --reps times, so every arm shows its own spread.  Prints one JSON line.
 
-    python scripts/loader_cost.py [--parent DIR] [--epochs 20] [--reps 3] [--out FILE]
+    python scripts/loader_cost.py [--parent DIR] [--epochs 20] [--reps 3] [--arms device,device_norm] [--out FILE]
 """
 import argparse
 import json
@@ -41,8 +43,13 @@ def child(args):
     rng = np.random.default_rng(0)
     samples = [data.synthetic_sample(rng, POINTS, fn_points=FN_POINTS) for _ in range(MESHES)]
     gen = torch.Generator().manual_seed(1)
+    kw = {}
     if args.child.startswith("device"):
-        loader = data.DeviceLoader(data.DeviceDataset(samples, dev), BATCH, shuffle=True, generator=gen,
+        ds = data.DeviceDataset(samples, dev)
+        if args.child == "device_norm":
+            kw["normalizer"] = data.Normalizer.fit(ds)
+            kw["loss_fn"] = train.RelL2Loss(kw["normalizer"])
+        loader = data.DeviceLoader(ds, BATCH, shuffle=True, generator=gen, normalizer=kw.get("normalizer"),
                                    points_per_mesh=args.points_per_mesh if args.child == "device_sub" else None)
     else:
         loader = torch.utils.data.DataLoader(data.NS2dData(samples), batch_size=BATCH, shuffle=True, generator=gen,
@@ -53,7 +60,7 @@ def child(args):
         torch.cuda.synchronize()
         stamps.append(time.perf_counter())
 
-    train.fit(model, loader, None, epochs=1 + args.epochs, per_epoch_schedule=False, log=log)
+    train.fit(model, loader, None, epochs=1 + args.epochs, per_epoch_schedule=False, log=log, **kw)
     print(json.dumps({"epoch_ms": [round((b - a) * 1e3, 3) for a, b in zip(stamps, stamps[1:])], "lib": _lib.LIB_PATH}))
 
 
@@ -63,6 +70,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=20, help="timed epochs per process, after one warm-up epoch")
     ap.add_argument("--reps", type=int, default=3, help="processes per arm")
     ap.add_argument("--points-per-mesh", type=int, default=2500)
+    ap.add_argument("--arms", default=None, help="comma-separated arms to run (default: all)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
@@ -70,7 +78,10 @@ def main():
     if args.child:
         return child(args)
     arms = ([("parent_host", "host", os.path.abspath(args.parent))] if args.parent else []) + \
-        [("host", "host", ROOT), ("device", "device", ROOT), ("device_sub", "device_sub", ROOT)]
+        [("host", "host", ROOT), ("device", "device", ROOT), ("device_sub", "device_sub", ROOT),
+         ("device_norm", "device_norm", ROOT)]
+    if args.arms:
+        arms = [a for a in arms if a[0] in args.arms.split(",")]
     runs = {name: [] for name, _, _ in arms}
     for _ in range(args.reps):
         for name, kind, tree in arms:                # interleaved: every round runs all of them

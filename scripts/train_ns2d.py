@@ -4,7 +4,8 @@ main.py:15-23, batch 4, AdamW lr 1e-3, OneCycleLR stepped per epoch, RelL2 metri
 with plain tensors instead of dgl graphs.  Batches are zero-padded exactly like main.py:60-89 by
 default (the pad rows enter the attention sums, as in the reference); --packed uses packed offsets.
 --device-data keeps the datasets in device memory and gathers the packed batches there; --points-per-mesh K
-trains on K randomly chosen points of every mesh per step.
+trains on K randomly chosen points of every mesh per step.  --normalize trains on unit-Gaussian inputs and
+targets (statistics of the training set, computed on the device) and writes a checkpoint that takes raw inputs.
 
     python scripts/train_ns2d.py --train train.pkl --test test.pkl [--epochs 100 ...]
     python scripts/train_ns2d.py --synthetic 64 --epochs 2          # generated meshes, same format
@@ -67,8 +68,15 @@ def main():
                     help="train on a fresh uniform subsample of K points of every mesh per step (meshes of fewer "
                          "points whole); input functions stay whole and the test set is evaluated at full "
                          "resolution (implies --device-data)")
+    ap.add_argument("--normalize", nargs="?", const="x,theta,fns,y", default=None, metavar="ARRAYS",
+                    help="normalise per channel to zero mean and unit variance with the training set's statistics: "
+                         "all four arrays, or a comma-separated subset of x,theta,fns,y.  Loss and metric stay in "
+                         "physical units and the checkpoint has the statistics folded in (implies --device-data)")
     args = ap.parse_args()
-    args.device_data = args.device_data or args.points_per_mesh is not None
+    norm = None if args.normalize is None else set(filter(None, args.normalize.split(",")))
+    if norm is not None and (not norm or norm - {"x", "theta", "fns", "y"}):
+        ap.error("--normalize takes a comma-separated subset of x,theta,fns,y")
+    args.device_data = args.device_data or args.points_per_mesh is not None or norm is not None
     if args.synthetic:
         rng = np.random.default_rng(0)
         tr = data.NS2dData([data.synthetic_sample(rng, int(rng.integers(1000, 4000))) for _ in range(args.synthetic)])
@@ -83,18 +91,22 @@ def main():
     dl = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=args.batch, shuffle=sh,
                                                     collate_fn=data.collate_packed if args.packed
                                                     else data.collate_padded)
+    nz = None
     if args.device_data:       # the test set stays at full resolution
-        loaders = (data.DeviceLoader(data.DeviceDataset(tr, dev), args.batch, shuffle=True,
-                                     points_per_mesh=args.points_per_mesh),
-                   data.DeviceLoader(data.DeviceDataset(te, dev), args.batch))
+        dtr = data.DeviceDataset(tr, dev)
+        if norm is not None:   # the training set's statistics serve both loaders
+            nz = data.Normalizer.fit(dtr, **{k: k in norm for k in ("x", "theta", "fns", "y")})
+        loaders = (data.DeviceLoader(dtr, args.batch, shuffle=True, points_per_mesh=args.points_per_mesh,
+                                     normalizer=nz),
+                   data.DeviceLoader(data.DeviceDataset(te, dev), args.batch, normalizer=nz))
     else:
         loaders = dl(tr, True), dl(te, False)
     _, test = train.fit(model, *loaders, epochs=args.epochs,
                         per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint,
-                        loss_fn=train.MSELoss() if args.loss == "mse" else train.RelL2Loss(),
+                        loss_fn=train.MSELoss(nz) if args.loss == "mse" else train.RelL2Loss(nz),
                         max_grad_norm=args.grad_clip, accum_steps=args.accum_steps,
                         skip_nonfinite=args.skip_nonfinite, state_path=args.state, resume=args.resume,
-                        ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
+                        ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup, normalizer=nz)
     print(f"\nBest Test Metric: {min(test)}")
 
 
