@@ -1,5 +1,6 @@
 // Host-side planning check, built with AddressSanitizer on the HOST code only (csrc/Makefile `asan`):
-// exercises every C-ABI entry point that needs no GPU -- plan creation for the supported widths, packed
+// exercises every C-ABI entry point that needs no GPU -- plan creation for the supported widths and for the edges
+// of the other constructor arguments (depth, blocks, theta_dim 0, experts, input functions, input / output widths), packed
 // batch geometries (ragged, empty samples, many meshes, padded-equal strides), MoE recompute and
 // precision switches, workspace sizing, gradient offsets, the caller-owned gradient arena, the flag
 // validation of gnot_backward_ex, the point-shard exchange tables and the error paths -- so heap overflows / use-after-free in engine.cpp's table building show up on the CPU.
@@ -222,6 +223,32 @@ int main() {
       c.n_input_functions = I;
       exercise(c, rng);
     }
+  // configuration edges (tests/test_gpu_config_edges.py): one argument at a time away from a base of
+  // (in 2, theta 1, fn 3, out 2), L = 1, two-layer MLPs, 2 experts, 1 input function
+  auto edge = [](int d, int H) {
+    gnot_config c{};
+    c.input_dim = 2; c.theta_dim = 1; c.input_func_dim = 3; c.out_dim = 2; c.n_attn_layers = 1;
+    c.n_attn_hidden_dim = c.n_mlp_hidden_dim = c.n_input_hidden_dim = d;
+    c.n_mlp_num_layers = 2; c.n_expert = 2; c.n_head = H; c.n_input_functions = 1;
+    return c;
+  };
+  const int fams[][2] = {{64, 4}, {256, 8}, {320, 10}};
+  for (const auto& f : fams) {
+    const int d = f[0], H = f[1];
+    for (int nl : {0, 6}) { gnot_config c = edge(d, H); c.n_mlp_num_layers = nl; exercise(c, rng); }
+    for (int L : {0, 5}) { gnot_config c = edge(d, H); c.n_attn_layers = L; c.n_mlp_num_layers = 1; exercise(c, rng); }
+    { gnot_config c = edge(d, H); c.n_attn_layers = 0; c.n_input_functions = 0; exercise(c, rng); }
+    { gnot_config c = edge(d, H); c.theta_dim = 0; exercise(c, rng); }
+    for (int E : {1, 16, 17, 64}) { gnot_config c = edge(d, H); c.n_expert = E; exercise(c, rng); }
+    for (int I : {3, 8}) { gnot_config c = edge(d, H); c.n_input_functions = I; exercise(c, rng); }
+    // the first full-width input / output set (ragged), and every width equal to d
+    { gnot_config c = edge(d, H); c.input_dim = 9; c.theta_dim = 8; c.input_func_dim = c.out_dim = 17; exercise(c, rng); }
+    { gnot_config c = edge(d, H); c.input_dim = d - 24; c.theta_dim = 24; c.input_func_dim = c.out_dim = d; exercise(c, rng); }
+  }
+  { gnot_config c = edge(64, 4); c.n_expert = 64; c.n_input_functions = 0; exercise(c, rng); }   // E = d, the cap
+  // internal width 640: 2 L = 10 d(fn) segments in launches of 4, 4, 2; 8 input functions on the K-split tables
+  { gnot_config c = edge(640, 10); c.n_attn_layers = 5; c.n_mlp_num_layers = 1; c.n_input_functions = 2; exercise(c, rng); }
+  { gnot_config c = edge(640, 10); c.n_input_functions = 8; exercise(c, rng); }
   // bad configurations are refused without leaking
   gnot_config bad{};
   bad.input_dim = 2; bad.theta_dim = 1; bad.input_func_dim = 3; bad.out_dim = 1; bad.n_attn_layers = 1;
@@ -229,6 +256,22 @@ int main() {
   bad.n_expert = 2; bad.n_head = 4;
   gnot_plan* p = nullptr;
   CHECK(gnot_plan_create(&bad, &p) == GNOT_E_INVALID);
+  // a negative theta_dim is refused (0 is a width), and so is an input function of width 0 (with no input
+  // function the width is unused and 0 is accepted)
+  {
+    gnot_config c = edge(64, 4);
+    c.input_dim = 3; c.theta_dim = -1;
+    CHECK(gnot_plan_create(&c, &p) == GNOT_E_INVALID);
+    c.theta_dim = 0;
+    CHECK(gnot_plan_create(&c, &p) == GNOT_OK);
+    gnot_plan_destroy(p);
+    c = edge(64, 4);
+    c.input_func_dim = 0;
+    CHECK(gnot_plan_create(&c, &p) == GNOT_E_INVALID);
+    c.n_input_functions = 0;
+    CHECK(gnot_plan_create(&c, &p) == GNOT_OK);
+    gnot_plan_destroy(p);
+  }
   exchange(rng);
   std::printf("layout digest: %016llx\n", (unsigned long long)g_digest);
   std::printf("asan_plan_check: %s (%d failed checks)\n", g_fail ? "FAILED" : "ok", g_fail);

@@ -404,6 +404,9 @@ extern "C" int gnot_plan_create(const gnot_config* cfg, gnot_plan** out) {
   if (c.input_dim + c.theta_dim > Dr || c.input_dim > Dr || c.input_func_dim > Dr || c.out_dim > Dr ||
       c.n_expert > Dr || c.input_dim < 1 || c.out_dim < 1)
     return fail(GNOT_E_INVALID, "input/output widths must be in [1, hidden width]");
+  if (c.theta_dim < 0) return fail(GNOT_E_INVALID, "theta_dim must not be negative");
+  if (c.n_input_functions > 0 && c.input_func_dim < 1)
+    return fail(GNOT_E_INVALID, "input_func_dim must be in [1, hidden width] when n_input_functions > 0");
   gnot_plan* p = new gnot_plan();
   p->c = c;
   p->D = D; p->Dr = Dr; p->H = c.n_head; p->dh = dh; p->dhr = dhr; p->E = c.n_expert; p->L = c.n_attn_layers;
@@ -2129,7 +2132,8 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
                         void* stream) {
   if (!p || !p->ws_bound) return fail(GNOT_E_STATE, "bind_workspace first");
   if (!p->packed) return fail(GNOT_E_STATE, "gnot_pack_weights must run before gnot_forward");
-  if (!x || !theta || !out || (p->I > 0 && !fns)) return fail(GNOT_E_INVALID, "null input");
+  // theta_dim = 0: theta is [B, 0], whose pointer may be null
+  if (!x || (!theta && p->th > 0) || !out || (p->I > 0 && !fns)) return fail(GNOT_E_INVALID, "null input");
   Ctx c{p, static_cast<hipStream_t>(stream)};
   const long P = p->P;
   const int D = p->D;
@@ -2146,7 +2150,8 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   }
   // inputs into the workspace (row pitch rounded to 16 B)
   GNOT_CK(hipMemcpy2DAsync(p->P_("x"), p->bufs["x"].ld * 4, x, p->in * 4, p->in * 4, P, hipMemcpyDeviceToDevice, c.s));
-  GNOT_CK(hipMemcpyAsync(p->P_("theta"), theta, (size_t)p->B * p->th * 4, hipMemcpyDeviceToDevice, c.s));
+  if (p->th > 0)
+    GNOT_CK(hipMemcpyAsync(p->P_("theta"), theta, (size_t)p->B * p->th * 4, hipMemcpyDeviceToDevice, c.s));
   GNOT_CK(launch_concat_theta(p->P_("x"), p->bufs["x"].ld, p->in, p->P_("theta"), p->th, p->d_xoff, p->B,
                               p->P_("xin"), p->bufs["xin"].ld, (int)P, c.s));
   // one encoder / decoder chain: C's input -> Y, keeping the pre-activations when training

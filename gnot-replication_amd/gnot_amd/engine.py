@@ -206,14 +206,15 @@ class Engine:
         s = self.stream()
         _lib.check(self.lib.gnot_pack_weights(self.plan, s))
         fptr = _ptr_array([f.data_ptr() for f in fns]) if fns else None
-        _lib.check(self.lib.gnot_forward(self.plan, x.data_ptr(), theta.data_ptr(), fptr, out.data_ptr(), s))
+        tptr = theta.data_ptr() if theta.numel() else None     # theta_dim = 0: an empty [B, 0] theta, no pointer
+        _lib.check(self.lib.gnot_forward(self.plan, x.data_ptr(), tptr, fptr, out.data_ptr(), s))
         self.fwd_token += 1
         return self.fwd_token
 
     def input_grads_into(self, dx, dtheta, dfns):
         """Gradients of x [P, in], theta [B, th] and the input functions [Q_i, F] of the last backward
         (None entries are skipped); launched on torch's current stream."""
-        ptr = lambda t: t.data_ptr() if t is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # an empty one (theta_dim = 0) is skipped
         fptr = _ptr_array([ptr(f) for f in dfns]) if dfns else None
         self._own_comms()
         with torch.cuda.device(self.ws.device):

@@ -36,7 +36,12 @@ typedef struct gnot_plan gnot_plan; /* opaque */
  * is at most 1024: a head width that is not a multiple of 4 runs on heads padded to one (n_head x that many
  * internal columns), and the internal width is the next multiple of 16 up to 192, 256 (heads of 16 / 32 / 64 /
  * 128 / 256, unpadded), the next multiple of 64 up to 512, else the next multiple of 128 (heads dividing 64),
- * with exact-zero pad columns; parameters, gradients and outputs keep d. */
+ * with exact-zero pad columns; parameters, gradients and outputs keep d.
+ * input_dim, input_dim + theta_dim, out_dim and n_expert are in [1, d]; input_func_dim is at most d and, when
+ * n_input_functions > 0, at least 1; theta_dim may be 0 (theta is then [B, 0]: gnot_forward takes a null theta
+ * and gnot_input_grads writes no dtheta), never negative; n_input_functions is in [0, 8]; n_attn_layers >= 0
+ * (0: encoder and decoder only, the input functions then do not reach the output and their gradients are
+ * zero); n_mlp_num_layers <= 1 gives two Linears per MLP.  GNOT_E_INVALID otherwise. */
 typedef struct gnot_config {
   int input_dim;
   int theta_dim;
@@ -155,7 +160,7 @@ int gnot_pack_weights(gnot_plan* plan, void* stream);
 
 /* Forward (reference GNOT.forward, model.py:154-173).
  * x [P, input_dim], theta [B, theta_dim], fns[i] [Q_i, input_func_dim] (packed, device, fp32,
- * contiguous); out [P, out_dim]. */
+ * contiguous); out [P, out_dim].  theta may be null when theta_dim = 0. */
 int gnot_forward(gnot_plan* plan, const float* x, const float* theta, const float* const* fns,
                  float* out, void* stream);
 

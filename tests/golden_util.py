@@ -98,8 +98,11 @@ def _port_pass(cfg, params, xs, thetas, fns_ps, Gs, groups, dtype):
         out = torch_port.gnot_forward(p, cfg, x, t, fs)
         (out * torch.tensor(np.stack([Gs[b] for b in grp]), dtype=dt)).sum().backward()   # param grads accumulate
         f64 = lambda a: a.detach().double().numpy().copy()
+        # an input the output does not depend on has no .grad: zeros of its shape, as for the parameters below
+        gx, gt, gf = [torch.zeros_like(v) if v.grad is None else v.grad for v in (x, t)] + \
+                     [[torch.zeros_like(f) if f.grad is None else f.grad for f in fs]]
         for k, b in enumerate(grp):
-            res[b] = dict(out=f64(out[k]), dx=f64(x.grad[k]), dtheta=f64(t.grad[k]), dfns=[f64(f.grad[k]) for f in fs])
+            res[b] = dict(out=f64(out[k]), dx=f64(gx[k]), dtheta=f64(gt[k]), dfns=[f64(g[k]) for g in gf])
     grads = {k: (np.zeros(v.shape) if v.grad is None else v.grad.double().numpy().copy()) for k, v in p.items()}
     return res, grads
 

@@ -159,7 +159,8 @@ def _assert_finite_and_empty_rows_zero(got, fx):
                 assert (got["dfns"][i][o[b]:o[b + 1]] == 0.0).all(), (b, i)
 
 
-def _log(kind, family, geom, path, got, fx):
+def _log(kind, family, geom, path, got, fx, tag="GEOM"):
+    """one log line per case; tag: the line's first word (tests/test_gpu_config_edges.py prints "CFGE")"""
     figs = per_sample_errors(got, fx)
     ws, ws_at, wr, wr_at = worst_relative(figs)
     live = [s for s in fx["samples"] if s["N"]]
@@ -167,16 +168,17 @@ def _log(kind, family, geom, path, got, fx):
     e_o = max(s["e32"]["out"] / nz(np.linalg.norm(s["out"])) for s in live)
     e_x = max(s["e32"]["dx"] / nz(np.linalg.norm(s["dx"])) for s in live)
     e_t = max(s["e32"]["dtheta"] / nz(np.linalg.norm(s["dtheta"])) for s in live)
-    e_f = max(s["e32"]["dfns"][i] / nz(np.linalg.norm(s["dfns"][i])) for s in live for i in range(len(s["dfns"])))
+    e_f = max((s["e32"]["dfns"][i] / nz(np.linalg.norm(s["dfns"][i])) for s in live for i in range(len(s["dfns"]))),
+              default=0.0)                  # no input function: nothing to report
     e_r = max(float((f["rows"]["e32"] / np.maximum(np.maximum(f["rows"]["ref"], f["rows"]["rms"]), 1e-300)).max())
               for f in figs if f is not None)
-    print(f"\nGEOM {kind} {family}/{geom} {path}: out {rel(got['out'], fx['out']):.2e} worst-sample {ws:.2e} ({ws_at}) "
+    print(f"\n{tag} {kind} {family}/{geom} {path}: out {rel(got['out'], fx['out']):.2e} worst-sample {ws:.2e} ({ws_at}) "
           f"worst-row {wr:.2e} ({wr_at}) | reference e32 per sample: out {e_o:.1e} dx {e_x:.1e} dtheta {e_t:.1e} dfns {e_f:.1e} "
           f"per row {e_r:.1e}")
     for b, f in enumerate(figs):
         if f is not None and kind == "bf16":
             s = fx["samples"][b]
-            print(f"GEOM bf16   sample {b} N={s['N']} M={s['M']}: " +
+            print(f"{tag} bf16   sample {b} N={s['N']} M={s['M']}: " +
                   " ".join(f"{k} {v['err'] / nz(v['ref']):.2e}" for k, v in f.items() if k != "rows"))
 
 

@@ -97,6 +97,15 @@ def test_plan_rejects_bad_config_and_batch():
         cfg = _lib.GnotConfig(**{**good, **bad})
         assert lib.gnot_plan_create(ctypes.byref(cfg), ctypes.byref(plan)) == -1
         assert lib.gnot_last_error()
+    # widths are in [1, hidden width]; theta_dim alone may be 0, never negative, and an input function has a width
+    for bad, ok in ((dict(input_dim=3, theta_dim=-1), dict(input_dim=3, theta_dim=0)),
+                    (dict(input_func_dim=0), dict(input_func_dim=0, n_input_functions=0))):
+        cfg = _lib.GnotConfig(**{**good, **bad})
+        assert lib.gnot_plan_create(ctypes.byref(cfg), ctypes.byref(plan)) == -1
+        assert lib.gnot_last_error()
+        cfg = _lib.GnotConfig(**{**good, **ok})
+        assert lib.gnot_plan_create(ctypes.byref(cfg), ctypes.byref(plan)) == 0
+        lib.gnot_plan_destroy(plan)
     cfg = _lib.GnotConfig(**good)
     _lib.check(lib.gnot_plan_create(ctypes.byref(cfg), ctypes.byref(plan)))
     try:
