@@ -125,6 +125,9 @@ struct gnot_plan {
   // the projections' feature-softmax pad columns: features past the H heads of dh are written as 0
   int attn_dreal() const { return hd() < D ? hd() : 0; }
   int in = 0, th = 0, F = 0, out = 0;
+  // Fourier embedding (gnot_plan_set_fourier): orders of x and of the input functions (0: none) and the widths
+  // of the caller's rows; in / F above stay the embedded widths, which the Linears and the workspace have
+  int nx = 0, nf = 0, in_raw = 0, F_raw = 0;
   std::vector<int> lin_o, lin_i;   // out / in features per canonical Linear
   std::vector<const float*> W, b;
   bool params_bound = false;
@@ -413,6 +416,7 @@ extern "C" int gnot_plan_create(const gnot_config* cfg, gnot_plan** out) {
   p->I = c.n_input_functions; p->KI = std::max(p->I, 1); p->DT = D / 16;
   p->NL = std::max(c.n_mlp_num_layers, 1) + 1;   // MLP(nl) has max(nl,1)+1 Linears (model.py:9-14)
   p->in = c.input_dim; p->th = c.theta_dim; p->F = c.input_func_dim; p->out = c.out_dim;
+  p->in_raw = p->in; p->F_raw = p->F;
   const int NL = p->NL;
   // canonical Linears at the model's width Dr (= named_parameters() shapes)
   auto mlp = [&](int in, int outd) {
@@ -1392,6 +1396,26 @@ extern "C" int gnot_plan_set_precision(gnot_plan* p, int bf16) {
   return GNOT_OK;
 }
 
+extern "C" int gnot_plan_set_fourier(gnot_plan* p, int nx, int nf) {
+  if (!p) return fail(GNOT_E_INVALID, "null plan");
+  if (nx < 0 || nx > 8 || nf < 0 || nf > 8)
+    return fail(GNOT_E_INVALID, "Fourier orders must be in [0, 8] (0: no embedding)");
+  const int Wx = nx > 0 ? 4 * nx + 3 : 1, Wf = nf > 0 ? 4 * nf + 3 : 1;
+  if (p->in % Wx != 0)
+    return fail(GNOT_E_INVALID, "input_dim must be the embedded width, a multiple of 4 x_fourier + 3 "
+                                "(gnot_config carries the embedded widths)");
+  if (p->F % Wf != 0)
+    return fail(GNOT_E_INVALID, "input_func_dim must be the embedded width, a multiple of 4 fn_fourier + 3 "
+                                "(gnot_config carries the embedded widths)");
+  if (p->nx != nx || p->nf != nf) {
+    p->nx = nx; p->nf = nf;
+    p->in_raw = p->in / Wx; p->F_raw = p->F / Wf;
+    p->batch_set = false;          // the staging of the inputs changes: set_batch + bind again
+    p->ws_bound = false;
+  }
+  return GNOT_OK;
+}
+
 extern "C" int gnot_plan_set_moe_recompute(gnot_plan* p, int on) {
   if (!p) return fail(GNOT_E_INVALID, "null plan");
   if (p->moe_recompute != (on != 0)) {
@@ -2148,8 +2172,12 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
     GNOT_CK(hipEventRecord(fork, c.s));
     GNOT_CK(hipStreamWaitEvent(cf.s, fork, 0));
   }
-  // inputs into the workspace (row pitch rounded to 16 B)
-  GNOT_CK(hipMemcpy2DAsync(p->P_("x"), p->bufs["x"].ld * 4, x, p->in * 4, p->in * 4, P, hipMemcpyDeviceToDevice, c.s));
+  // inputs into the workspace (row pitch rounded to 16 B); with a Fourier order the caller's rows are the raw
+  // ones and the staging embeds them (fourier.hip), the pad columns written as zeros
+  if (p->nx > 0)
+    GNOT_CK(launch_fourier_embed(x, p->in_raw, p->in_raw, p->nx, p->P_("x"), p->bufs["x"].ld, P, c.s));
+  else
+    GNOT_CK(hipMemcpy2DAsync(p->P_("x"), p->bufs["x"].ld * 4, x, p->in * 4, p->in * 4, P, hipMemcpyDeviceToDevice, c.s));
   if (p->th > 0)
     GNOT_CK(hipMemcpyAsync(p->P_("theta"), theta, (size_t)p->B * p->th * 4, hipMemcpyDeviceToDevice, c.s));
   GNOT_CK(launch_concat_theta(p->P_("x"), p->bufs["x"].ld, p->in, p->P_("theta"), p->th, p->d_xoff, p->B,
@@ -2166,7 +2194,10 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   GNOT_RUN(chain_fwd(c, p->ch_x(), p->P_("query0"), D));
   for (int i = 0; i < p->I; ++i) {
     const std::string n = "fn" + std::to_string(i);
-    if (p->Q[i] > 0)
+    if (p->Q[i] <= 0) continue;
+    if (p->nf > 0)
+      GNOT_CK(launch_fourier_embed(fns[i], p->F_raw, p->F_raw, p->nf, p->P_(n), p->bufs[n].ld, p->Q[i], cf.s));
+    else
       GNOT_CK(hipMemcpy2DAsync(p->P_(n), p->bufs[n].ld * 4, fns[i], p->F * 4, p->F * 4, p->Q[i],
                                hipMemcpyDeviceToDevice, cf.s));
   }
@@ -2374,7 +2405,14 @@ extern "C" int gnot_input_grads(gnot_plan* p, float* dx, float* dtheta, float* c
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const Buf& xin = p->bufs.at("dxin");
   const Buf& xg = p->bufs.at("dxg");
-  if (dx) GNOT_CK(launch_add_cols(xin.p, xin.ld, xg.p, xg.ld, p->in, dx, p->P, s));
+  // with a Fourier order the embedded rows of the forward still sit in "x" / "fn{i}": their cos / sin columns
+  // are the factors of the embedding's derivative (fourier.hip), and dx / dfns have the raw widths
+  if (dx && p->nx > 0) {
+    const Buf& xe = p->bufs.at("x");
+    GNOT_CK(launch_fourier_embed_bwd(xe.p, xe.ld, xin.p, xin.ld, xg.p, xg.ld, p->in_raw, p->nx, dx, p->P, s));
+  } else if (dx) {
+    GNOT_CK(launch_add_cols(xin.p, xin.ld, xg.p, xg.ld, p->in, dx, p->P, s));
+  }
   // point-sharded: x's rows are local, but theta (broadcast over ALL points of a sample) and the input
   // functions (replicated on every rank, reached through every rank's attention states) get one partial
   // gradient per rank -- summed over the ranks (every rank must call this: the sums are collectives)
@@ -2392,7 +2430,13 @@ extern "C" int gnot_input_grads(gnot_plan* p, float* dx, float* dtheta, float* c
       Ctx c{p, s};
       GNOT_RUN(shard_allreduce(c, f.p, p->Q[i] * f.ld));
     }
-    if (dfns && dfns[i]) GNOT_CK(launch_add_cols(f.p, f.ld, nullptr, 0, p->F, dfns[i], p->Q[i], s));
+    if (!dfns || !dfns[i]) continue;
+    if (p->nf > 0) {
+      const Buf& fe = p->bufs.at("fn" + std::to_string(i));
+      GNOT_CK(launch_fourier_embed_bwd(fe.p, fe.ld, f.p, f.ld, nullptr, 0, p->F_raw, p->nf, dfns[i], p->Q[i], s));
+    } else {
+      GNOT_CK(launch_add_cols(f.p, f.ld, nullptr, 0, p->F, dfns[i], p->Q[i], s));
+    }
   }
   p->ig_reduced = true;
   return GNOT_OK;
@@ -2630,6 +2674,29 @@ extern "C" int gnot_channel_stats(const float* src, int64_t rows, int C, float e
 extern "C" int gnot_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, int64_t n, void* stream) {
   if (!x || !y || !dy || !y2 || !dy2 || n < 1) return fail(GNOT_E_INVALID, "bad debug_gelu arguments");
   GNOT_CK(launch_debug_gelu(x, y, dy, y2, dy2, n, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_fourier_embed(const float* src, int64_t rows, int C, int n, float* dst, int64_t ld, void* stream) {
+  if (!src || !dst) return fail(GNOT_E_INVALID, "fourier_embed: null pointer");
+  if (rows < 1 || C < 1) return fail(GNOT_E_INVALID, "fourier_embed: rows and C must be at least 1");
+  if (n < 1 || n > 8) return fail(GNOT_E_INVALID, "fourier_embed: the order must be in [1, 8]");
+  if (ld < (int64_t)C * (4 * n + 3)) return fail(GNOT_E_INVALID, "fourier_embed: ld is less than C (4 n + 3)");
+  if (ld >= (1LL << 31)) return fail(GNOT_E_INVALID, "fourier_embed: ld must be below 2^31 (32-bit column indices)");
+  GNOT_CK(launch_fourier_embed(src, C, C, n, dst, ld, rows, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_fourier_embed_bwd(const float* emb, int64_t ld, const float* g, int64_t ldg, const float* g2,
+                                      int64_t ldg2, int64_t rows, int C, int n, float* dv, void* stream) {
+  if (!emb || !g || !dv) return fail(GNOT_E_INVALID, "fourier_embed_bwd: null pointer");
+  if (rows < 1 || C < 1) return fail(GNOT_E_INVALID, "fourier_embed_bwd: rows and C must be at least 1");
+  if (n < 1 || n > 8) return fail(GNOT_E_INVALID, "fourier_embed_bwd: the order must be in [1, 8]");
+  const int64_t CW = (int64_t)C * (4 * n + 3);
+  if (ld < CW || ldg < CW || (g2 && ldg2 < CW))
+    return fail(GNOT_E_INVALID, "fourier_embed_bwd: a row pitch is less than C (4 n + 3)");
+  if (CW >= (1LL << 31)) return fail(GNOT_E_INVALID, "fourier_embed_bwd: C (4 n + 3) must be below 2^31");
+  GNOT_CK(launch_fourier_embed_bwd(emb, ld, g, ldg, g2, ldg2, C, n, dv, rows, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

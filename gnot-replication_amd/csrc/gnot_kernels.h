@@ -299,6 +299,14 @@ hipError_t launch_add_cols(const float* a, long lda, const float* b, long ldb, i
 // out[b][t] = sum over rows [off[b], off[b+1]) of a[row][c0 + t], t < ncols (fixed order)
 hipError_t launch_seg_colsum(const float* a, long lda, int c0, int ncols, const long* off, int B, float* out,
                              hipStream_t s);
+// Fourier embedding of order n in [1, 8] (fourier.hip), W = 4 n + 3: src [rows, C] (pitch lds) -> dst [rows, ld],
+// channel c as columns c W .. c W + W - 1 = [v, cos(2^(k-n) v), sin(2^(k-n) v)], k = 0 .. 2 n; columns C W .. ld - 1
+// zeros.  The backward reads cos / sin from the embedded rows emb and the gradient as ga + gb (gb may be null):
+// dv [rows, C] dense
+hipError_t launch_fourier_embed(const float* src, long lds, int C, int n, float* dst, long ld, long rows,
+                                hipStream_t s);
+hipError_t launch_fourier_embed_bwd(const float* emb, long ld, const float* ga, long ldga, const float* gb, long ldgb,
+                                    int C, int n, float* dv, long rows, hipStream_t s);
 // test hook: y = gelu(x), dy = gelu_grad(x), (y2, dy2) = gelu_and_grad(x) over n contiguous floats
 hipError_t launch_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, long n, hipStream_t s);
 // segmented copy: dst[seg.dst + i] = src[seg.src + i], i < seg.len (floats); reverse swaps the roles of

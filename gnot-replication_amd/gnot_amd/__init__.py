@@ -8,10 +8,14 @@
 The training step around it lives in `gnot_amd.train` (`RelL2Loss`, `MSELoss`, `FlatAdamW` with optional
 global-norm gradient clipping, `OneCycle`, `fit`), datasets, loaders and unit-Gaussian normalisation
 (`Normalizer`, `DeviceDataset`, `DeviceLoader`) in `gnot_amd.data`, and the multi-GPU glue in
-`gnot_amd.parallel`.
+`gnot_amd.parallel`.  `GNOT(..., x_fourier=n, fn_fourier=n)` embeds x and the input functions in multi-scale
+Fourier features inside the model (`gnot_amd.fourier`: `fourier_features` is the same map in plain torch,
+`fourier_embed` the library's kernel).
 """
 from .model import GNOT, MLP, LinearAttention, HeterogeneousNormalizedAttentionBlock  # noqa: F401
 from . import _lib  # noqa: F401
 from .data import Normalizer  # noqa: F401
+from .fourier import fourier_embed, fourier_features  # noqa: F401
 
-__all__ = ["GNOT", "MLP", "LinearAttention", "HeterogeneousNormalizedAttentionBlock", "Normalizer"]
+__all__ = ["GNOT", "MLP", "LinearAttention", "HeterogeneousNormalizedAttentionBlock", "Normalizer",
+           "fourier_features", "fourier_embed"]

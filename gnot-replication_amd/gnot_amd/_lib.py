@@ -35,7 +35,7 @@ EXPORTS = [
     "gnot_plan_set_grad_arena", "gnot_backward_ex", "gnot_grad_norm", "gnot_adamw_step_guarded",
     "gnot_ema_update", "gnot_adamw_step_ema", "gnot_gather_rows", "gnot_debug_gelu",
     "gnot_channel_stats_work_floats", "gnot_channel_stats", "gnot_gather_rows_affine", "gnot_rel_l2_loss_affine",
-    "gnot_mse_loss_affine",
+    "gnot_mse_loss_affine", "gnot_plan_set_fourier", "gnot_fourier_embed", "gnot_fourier_embed_bwd",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -66,7 +66,7 @@ def build(jobs=8, quiet=True):
 # every file the library's code depends on (csrc/Makefile's SRCS, its headers and its flags)
 SOURCES = ["Makefile", "gnot_common.h", "gnot_kernels.h", "x6_core.h", "pack.hip", "linear.hip", "linear2.hip",
            "chain.hip", "chain2.hip", "chainw.hip", "wgrad.hip", "state.hip", "attn.hip", "attn_mfma.hip", "misc.hip",
-           "train.hip", "gather.hip", "stats.hip", "engine.cpp"]
+           "fourier.hip", "train.hip", "gather.hip", "stats.hip", "engine.cpp"]
 
 
 def source_hash():
@@ -142,6 +142,9 @@ def _declare(lib):
     lib.gnot_gather_rows_affine.argtypes = [P, i32, P, ctypes.POINTER(i64), i32, P, P, P]
     lib.gnot_rel_l2_loss_affine.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, P, P, P, P, P]
     lib.gnot_mse_loss_affine.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, P, P, P, P, P]
+    lib.gnot_plan_set_fourier.argtypes = [P, i32, i32]
+    lib.gnot_fourier_embed.argtypes = [P, i64, i32, i32, P, i64, P]
+    lib.gnot_fourier_embed_bwd.argtypes = [P, i64, P, i64, P, i64, i64, i32, i32, P, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p
@@ -167,3 +170,20 @@ def load():
 def check(rc):
     if rc != 0:
         raise RuntimeError(f"libgnot_hip error {rc}: {load().gnot_last_error().decode()}")
+
+
+def probe_plan(cfg, nx=0, nf=0):
+    """Create and destroy a plan for `cfg` (the gnot_config as a dict) with the Fourier orders nx / nf: host
+    only.  ValueError with the library's message if it refuses the configuration."""
+    lib = load()
+    c = GnotConfig(**cfg)
+    plan = ctypes.c_void_p()
+    rc = lib.gnot_plan_create(ctypes.byref(c), ctypes.byref(plan))
+    if rc == 0:
+        rc = lib.gnot_plan_set_fourier(plan, nx, nf)
+        msg = lib.gnot_last_error().decode() if rc != 0 else ""
+        lib.gnot_plan_destroy(plan)
+    else:
+        msg = lib.gnot_last_error().decode()
+    if rc != 0:
+        raise ValueError(f"libgnot_hip refuses this model ({rc}): {msg}")

@@ -17,13 +17,18 @@ def _ptr_array(ptrs):
 
 
 class Engine:
-    def __init__(self, cfg: dict, linears):
-        """cfg: the 12 constructor arguments; linears: nn.Linear modules in state_dict order."""
+    def __init__(self, cfg: dict, linears, fourier=(0, 0)):
+        """cfg: the 12 constructor arguments (the gnot_config: with a Fourier embedding input_dim and
+        input_func_dim are the embedded widths, the Linears'); linears: nn.Linear modules in state_dict order;
+        fourier: the orders (x, input functions) of gnot_plan_set_fourier -- the caller's x, the input functions
+        and their gradients then have the raw widths."""
         self.lib = _lib.load()
         c = _lib.GnotConfig(**cfg)
         plan = ctypes.c_void_p()
         _lib.check(self.lib.gnot_plan_create(ctypes.byref(c), ctypes.byref(plan)))
         self.plan = plan
+        if any(fourier):           # the default model issues the calls it always did
+            _lib.check(self.lib.gnot_plan_set_fourier(plan, int(fourier[0]), int(fourier[1])))
         n = self.lib.gnot_plan_num_linears(plan)
         dims = (ctypes.c_int32 * (2 * n))()
         _lib.check(self.lib.gnot_plan_linear_dims(plan, dims))

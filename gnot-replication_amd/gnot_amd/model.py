@@ -21,7 +21,9 @@ import weakref
 import torch
 import torch.nn as nn
 
+from . import _lib
 from .engine import Engine
+from .fourier import check_order, width
 
 
 class MLP(nn.Module):
@@ -141,8 +143,21 @@ class GNOT(nn.Module):
     """Drop-in replacement of the reference GNOT (model.py:142-173)."""
 
     def __init__(self, input_dim, theta_dim, input_func_dim, out_dim, n_attn_layers, n_attn_hidden_dim,
-                 n_mlp_num_layers, n_mlp_hidden_dim, n_input_hidden_dim, n_expert, n_head, n_input_functions=0):
+                 n_mlp_num_layers, n_mlp_hidden_dim, n_input_hidden_dim, n_expert, n_head, n_input_functions=0, *,
+                 x_fourier=0, fn_fourier=0):
+        """The reference's 12 arguments, then (keyword only, no reference counterpart) the orders of the
+        Fourier embedding of x and of the input functions (gnot_amd.fourier; 0: none).  input_dim and
+        input_func_dim stay the widths of the caller's tensors; with an order n the first Linears take
+        4 n + 3 columns per channel, and the module is the reference GNOT of those embedded widths applied to
+        fourier_features(x, x_fourier), the raw theta and fourier_features(fn_i, fn_fourier): its state_dict
+        has that model's keys, shapes and order and nothing else."""
         super().__init__()
+        nx = check_order(x_fourier, "x_fourier")
+        nf = check_order(fn_fourier, "fn_fourier")
+        if n_input_functions == 0:
+            nf = 0                 # no input function, nothing to embed: input_func_dim shapes no Linear
+        raw_in, raw_f = input_dim, input_func_dim
+        input_dim, input_func_dim = raw_in * width(nx), raw_f * width(nf)
         self.x = MLP(n_mlp_num_layers, input_dim + theta_dim, n_input_hidden_dim, n_input_hidden_dim)
         self.gating = MLP(n_mlp_num_layers, input_dim, n_mlp_hidden_dim, n_expert)
         self.input_func_mlps = nn.ModuleList(MLP(n_mlp_num_layers, input_func_dim, n_mlp_hidden_dim,
@@ -151,11 +166,18 @@ class GNOT(nn.Module):
             n_attn_hidden_dim, n_mlp_num_layers, n_mlp_hidden_dim, n_input_hidden_dim, n_expert, n_head,
             n_input_functions) for _ in range(n_attn_layers))
         self.out = MLP(n_mlp_num_layers, n_input_hidden_dim, n_mlp_hidden_dim, out_dim)
-        self._cfg = dict(input_dim=input_dim, theta_dim=theta_dim, input_func_dim=input_func_dim,
+        # _cfg: the constructor's arguments (raw widths); _plan_cfg: the gnot_config, which carries the embedded
+        # widths (the Linear shapes); the two are equal without an embedding
+        self._cfg = dict(input_dim=raw_in, theta_dim=theta_dim, input_func_dim=raw_f,
                          out_dim=out_dim, n_attn_layers=n_attn_layers, n_attn_hidden_dim=n_attn_hidden_dim,
                          n_mlp_num_layers=n_mlp_num_layers, n_mlp_hidden_dim=n_mlp_hidden_dim,
                          n_input_hidden_dim=n_input_hidden_dim, n_expert=n_expert, n_head=n_head,
                          n_input_functions=n_input_functions)
+        self._plan_cfg = dict(self._cfg, input_dim=input_dim, input_func_dim=input_func_dim)
+        self.x_fourier, self.fn_fourier = nx, nf
+        if nx or nf:
+            # widths that do not fit the hidden width are refused here, with the engine's message (host only)
+            _lib.probe_plan(self._plan_cfg, nx, nf)
         self._engine = None        # the primary engine: every forward whose predecessor's backward has run
         self._extra = []           # more engines, for forwards issued while earlier ones await their backward
         self.max_pending_backwards = 2
@@ -176,7 +198,7 @@ class GNOT(nn.Module):
         return out + self.out.linears()
 
     def _new_engine(self):
-        e = Engine(self._cfg, self.linears())
+        e = Engine(self._plan_cfg, self.linears(), fourier=(self.x_fourier, self.fn_fourier))
         e.comm = self._comm
         e.grad_comm = self._grad_comm
         e.moe_recompute = self._moe_recompute
@@ -351,6 +373,16 @@ class GNOT(nn.Module):
         x = x.contiguous().float()
         theta = theta.contiguous().float()
         fns = [f.contiguous().float() for f in fns]
+        if self.x_fourier or self.fn_fourier:
+            # the native staging reads rows of exactly the raw widths
+            if x.shape[-1] != self._cfg["input_dim"]:
+                raise ValueError(f"x has {x.shape[-1]} channels, the model's input_dim is {self._cfg['input_dim']} "
+                                 f"(the raw width; x_fourier={self.x_fourier} embeds it inside the model)")
+            for i, f in enumerate(fns):
+                if f.shape[-1] != self._cfg["input_func_dim"]:
+                    raise ValueError(f"input function {i} has {f.shape[-1]} channels, the model's input_func_dim is "
+                                     f"{self._cfg['input_func_dim']} (the raw width; fn_fourier={self.fn_fourier} "
+                                     "embeds it inside the model)")
         params = [l.weight for l in self.linears()] + [l.bias for l in self.linears()]
         grad = torch.is_grad_enabled()
         inputs_grad = grad and (x.requires_grad or theta.requires_grad or any(f.requires_grad for f in fns))

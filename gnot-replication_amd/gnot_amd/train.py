@@ -405,9 +405,41 @@ def save_checkpoint(model, path, normalizer=None):
     """torch.save(model.state_dict()) exactly as main.py:151 (reference-compatible keys/shapes).
     normalizer: the model was trained on normalised data; the statistics are folded into its first and last
     Linears (Normalizer.fold), so the file predicts physical outputs from raw inputs -- in gnot_amd.GNOT and in
-    the reference module alike -- and holds the reference's keys and nothing else."""
+    the reference module alike -- and holds the reference's keys and nothing else.  Statistics of a block the
+    model embeds in Fourier features cannot be folded: ValueError unless that block is the identity (_foldable)."""
     sd = model.state_dict()
-    torch.save(sd if normalizer is None else normalizer.fold(sd, model._cfg["n_mlp_num_layers"]), path)
+    torch.save(sd if normalizer is None else _foldable(model, normalizer).fold(sd, model._cfg["n_mlp_num_layers"]),
+               path)
+
+
+def _is_identity(block):
+    """a stats block of mean 0, rstd 1: encode returns its argument"""
+    b = block.detach().cpu()
+    return bool((b[0] == 0).all() and (b[2] == 1).all())
+
+
+def _foldable(model, normalizer):
+    """The normalizer whose fold fits `model`'s first Linears.  The Fourier embedding (GNOT's x_fourier /
+    fn_fourier) is not affine, so the statistics of an embedded block cannot move into the Linear behind it:
+    ValueError if the normalizer holds other than identity statistics for such a block; an identity block of
+    an embedded input is widened to the embedded width (it folds to nothing), and theta, y and every block
+    that is not embedded fold as always.  Host only."""
+    nx, nf = getattr(model, "x_fourier", 0), getattr(model, "fn_fourier", 0)
+    if normalizer is None or not (nx or nf):
+        return normalizer
+    from .data import Normalizer
+    from .fourier import width
+    bad = [name for name, b in normalizer.blocks().items()
+           if ((name == "x" and nx) or (name.startswith("fns.") and nf)) and not _is_identity(b)]
+    if bad:
+        what = {"x": f"x (x_fourier={nx})"}
+        names = ", ".join(what.get(n, f"{n} (fn_fourier={nf})") for n in bad)
+        raise ValueError(f"the normalizer holds statistics for {names}, which the model embeds in Fourier features: "
+                         "the embedding is not affine, so they cannot be folded into the checkpoint's first Linear.  "
+                         "Normalise that block in the dataset itself, or drop it from --normalize (an identity "
+                         "block); the state file (state_path / resume) is not affected")
+    wide = lambda b, n: Normalizer.identity(b.shape[1] * width(n), b.device) if n else b
+    return Normalizer(wide(normalizer.x, nx), normalizer.theta, normalizer.y, [wide(f, nf) for f in normalizer.fns])
 
 
 def load_checkpoint(model, path):
@@ -660,6 +692,10 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     The state file keeps the unfolded weights and the statistics in an entry of its own, "normalizer"; resume
     refuses a file whose statistics differ, one that has the entry when this call has no normalizer, and one
     that lacks it when this call has one.  Padded batches and the point-sharded losses are out of scope.
+    A block the model embeds in Fourier features (GNOT's x_fourier / fn_fourier) cannot be folded -- the
+    embedding is not affine: with a checkpoint, non-identity statistics for such a block are a ValueError before
+    any GPU work (normalise that block in the dataset, or leave it out of the statistics); the state file takes
+    any combination.
     None (default): raw data, every call what it was.
     No step reads its loss back: every step's 0-d loss (with accum_steps, every micro-batch's) stays on the
     device and the epoch reads them all at its end, then does the host arithmetic above on those fp32 values;
@@ -671,6 +707,8 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
         raise ValueError("accum_steps must be >= 1")
     if resume and not state_path:
         raise ValueError("resume needs a state_path")
+    if checkpoint:
+        _foldable(model, normalizer)     # statistics of a Fourier-embedded block cannot be folded: refuse now
     loss_fn = loss_fn or RelL2Loss(normalizer)
     _check_normalizer(getattr(loss_fn, "normalizer", None), normalizer, "fit: loss_fn")
     enc_train = _batch_encoder(train_loader, normalizer, "fit: train_loader")

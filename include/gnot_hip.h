@@ -112,6 +112,24 @@ int gnot_plan_set_moe_recompute(gnot_plan* plan, int on);
  * invalidates the batch (set_batch + bind again). */
 int gnot_plan_set_precision(gnot_plan* plan, int bf16);
 
+/* Multi-scale Fourier embedding of the inputs (off by default; the original GNOT code's horiz_fourier_dim -- the
+ * replicated model.py takes raw inputs).  For an order n >= 1, W = 4 n + 3 and f_k = 2^(k - n), k = 0 .. 2 n,
+ * channel c of a row (value v) becomes the W consecutive columns c W .. c W + W - 1
+ *     [ v, cos(f_0 v) .. cos(f_2n v), sin(f_0 v) .. sin(f_2n v) ]
+ * (channel-major).  nx embeds x (the gating MLP sees the embedded x too; theta is concatenated raw, behind it),
+ * nf every input function; 0 means none, orders run 0 .. 8 (GNOT_E_INVALID otherwise).  The gnot_config keeps
+ * carrying the EMBEDDED widths -- the Linear shapes, and what the width limits of gnot_config bound: input_dim
+ * must be a multiple of 4 nx + 3 and input_func_dim one of 4 nf + 3 (GNOT_E_INVALID otherwise), and the
+ * caller's rows have input_dim / (4 nx + 3) and input_func_dim / (4 nf + 3) columns.  gnot_forward then reads
+ * x and fns[i] with those raw widths and embeds them as it stages them into the workspace, and
+ * gnot_input_grads writes dx and dfns[i] with the raw widths,
+ *     dv = g_0 + sum_k f_k (cos(f_k v) g_sin,k - sin(f_k v) g_cos,k)   (g_0 first, then k = 0 .. 2 n),
+ * from the embedded rows of the forward: no trigonometry in the backward.  The model IS the reference model
+ * of the embedded widths applied to the embedded inputs; parameters, gradients and theta are untouched.
+ * Call after gnot_plan_create and before gnot_plan_set_batch; changing an order invalidates the batch
+ * (set_batch + bind again). */
+int gnot_plan_set_fourier(gnot_plan* plan, int nx, int nf);
+
 /* Input gradients (off by default).  The reference's autograd also differentiates w.r.t. x, theta and
  * the input functions when they require grad (model.py:154-173: x feeds the gating MLP and, through
  * torch.cat with the broadcast theta, the query encoder; the input functions feed their encoder
@@ -160,9 +178,23 @@ int gnot_pack_weights(gnot_plan* plan, void* stream);
 
 /* Forward (reference GNOT.forward, model.py:154-173).
  * x [P, input_dim], theta [B, theta_dim], fns[i] [Q_i, input_func_dim] (packed, device, fp32,
- * contiguous); out [P, out_dim].  theta may be null when theta_dim = 0. */
+ * contiguous); out [P, out_dim].  theta may be null when theta_dim = 0.  With gnot_plan_set_fourier x and
+ * fns[i] have the raw widths and are embedded on the way into the workspace. */
 int gnot_forward(gnot_plan* plan, const float* x, const float* theta, const float* const* fns,
                  float* out, void* stream);
+
+/* The embedding of gnot_plan_set_fourier on its own, for point-by-point tests and for feeding a model of the
+ * embedded width (no plan; one launch on `stream`; fp32 device pointers).
+ * gnot_fourier_embed: src [rows, C] contiguous -> dst [rows, ld], ld >= C (4 n + 3); column 0 of each channel's
+ * block is the input bit for bit, f_k v is an exact product, cos / sin are the full-range single-precision
+ * routines, and the pad columns C (4 n + 3) .. ld - 1 are written as zeros.
+ * gnot_fourier_embed_bwd: emb [rows, ld] as gnot_fourier_embed wrote it, the gradient of the embedded rows as
+ * g [rows, ldg] + g2 [rows, ldg2] (g2 may be null: g alone; the engine passes d x_in and d x_gate) ->
+ * dv [rows, C] contiguous, summed in the fixed order given above.
+ * n in [1, 8], rows >= 1, C >= 1, ld and C (4 n + 3) below 2^31; GNOT_E_INVALID before any launch otherwise. */
+int gnot_fourier_embed(const float* src, int64_t rows, int C, int n, float* dst, int64_t ld, void* stream);
+int gnot_fourier_embed_bwd(const float* emb, int64_t ld, const float* g, int64_t ldg, const float* g2, int64_t ldg2,
+                           int64_t rows, int C, int n, float* dv, void* stream);
 
 /* Backward of the last gnot_forward: dout [P, out_dim] -> every parameter gradient, written
  * (overwritten) into the gradient arena.  The same as gnot_backward_ex(plan, dout, 0, stream). */

@@ -6,6 +6,8 @@ default (the pad rows enter the attention sums, as in the reference); --packed u
 --device-data keeps the datasets in device memory and gathers the packed batches there; --points-per-mesh K
 trains on K randomly chosen points of every mesh per step.  --normalize trains on unit-Gaussian inputs and
 targets (statistics of the training set, computed on the device) and writes a checkpoint that takes raw inputs.
+--x-fourier N / --fn-fourier N embed the coordinates / the input functions in multi-scale Fourier features of
+order N inside the model (the original GNOT code's horiz_fourier_dim), behind the normalisation.
 
     python scripts/train_ns2d.py --train train.pkl --test test.pkl [--epochs 100 ...]
     python scripts/train_ns2d.py --synthetic 64 --epochs 2          # generated meshes, same format
@@ -72,10 +74,20 @@ def main():
                     help="normalise per channel to zero mean and unit variance with the training set's statistics: "
                          "all four arrays, or a comma-separated subset of x,theta,fns,y.  Loss and metric stay in "
                          "physical units and the checkpoint has the statistics folded in (implies --device-data)")
+    ap.add_argument("--x-fourier", type=int, default=0, metavar="N",
+                    help="embed every coordinate v as [v, cos(2^k v), sin(2^k v)], k = -N .. N, inside the model "
+                         "(4 N + 3 columns per channel, N up to 8; default 0: raw coordinates)")
+    ap.add_argument("--fn-fourier", type=int, default=0, metavar="N",
+                    help="the same embedding for every input function's channels (default 0)")
     args = ap.parse_args()
     norm = None if args.normalize is None else set(filter(None, args.normalize.split(",")))
     if norm is not None and (not norm or norm - {"x", "theta", "fns", "y"}):
         ap.error("--normalize takes a comma-separated subset of x,theta,fns,y")
+    for flag, order, block in (("--x-fourier", args.x_fourier, "x"), ("--fn-fourier", args.fn_fourier, "fns")):
+        if order and norm is not None and block in norm and args.checkpoint:
+            ap.error(f"{flag} with --normalize {block}: the embedding is not affine, so the statistics of {block} "
+                     f"cannot be folded into the checkpoint; normalise {block} in the dataset itself or drop it "
+                     "from --normalize")
     args.device_data = args.device_data or args.points_per_mesh is not None or norm is not None
     if args.synthetic:
         rng = np.random.default_rng(0)
@@ -87,7 +99,7 @@ def main():
     dev = torch.device("cuda", args.gpu_id)
     model = GNOT(x0.shape[1], len(np.atleast_1d(th0)), f0[0].shape[1], y0.shape[1], args.n_attn_layers,
                  args.n_attn_hidden_dim, args.n_mlp_num_layers, args.n_mlp_hidden_dim, args.n_input_hidden_dim,
-                 args.n_expert, args.n_head, len(f0)).to(dev)
+                 args.n_expert, args.n_head, len(f0), x_fourier=args.x_fourier, fn_fourier=args.fn_fourier).to(dev)
     dl = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=args.batch, shuffle=sh,
                                                     collate_fn=data.collate_packed if args.packed
                                                     else data.collate_padded)
