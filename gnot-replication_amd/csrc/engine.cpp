@@ -42,7 +42,6 @@ static inline int tiles16(int x) { return (x + 15) / 16; }
 
 constexpr int kSeg = 64;             // points per attention segment (one wave of the apply kernels)
 constexpr int kPTile = 128;          // output tile edge of the point-reduction GEMM (wgrad.hip)
-constexpr int kTargetWGs = 512;      // aim for ~2 workgroups per CU per point-reduction launch
 constexpr int kMinSplitPoints = 128; // never split below this many points
 
 struct Img {                 // one packed MFMA A-operand image in the packed arena
@@ -62,16 +61,13 @@ struct WgradGroup {
   std::vector<int> wg_prefix, red_prefix;
   int total_wgs = 0, total_red = 0;
   size_t slab_floats = 0;
-  bool x6 = false;                   // plain weight-gradient jobs: the bf16x6 MFMA kernel
-  bool wide = false;                 // ... on the 256 x 256-tile kernel (d = 256: one workgroup per job split)
-  int tw = 256;                      // wide geometry's output edge: 256, or 128 (d <= 128, jobs within 128 x 128)
-  bool b16 = false;                  // bf16-storage jobs (bf16 mode soft-MoE): pgemm_b16_kernel, wide geometry
-  bool scaled = false;               // some job has a per-point scale (WgradJob::scale): the wide kernel's scaled form
+  WgradKernel kind = WgradKernel::Tile128;   // weight-gradient groups: the kernel they run (finish_group)
+  bool scaled = false;               // Wide256: some job has a per-point scale (WgradJob::scale), the scaled form
   std::vector<int> lins;             // weight-gradient groups: the canonical Linears whose (dW, db) they write
   int state_pts = 0, state_nw = 0;
   bool state_mfma = false;   // state groups: points per workgroup, per-point weights (0 or H)
-  // balanced wide groups: per-workgroup point ranges {job, slot, begin, end} (launch_wgrad segs) and the
-  // first range of every workgroup (+ the end)
+  // balanced groups: per-workgroup point ranges {job, slot, begin, end} (WgradTables::segs) and the first
+  // range of every workgroup (+ the end)
   std::vector<int4> segs;
   std::vector<int> seg_start;
   WgradJob* d_jobs = nullptr;        // device copies (workspace tables)
@@ -79,6 +75,9 @@ struct WgradGroup {
   int* d_red_prefix = nullptr;
   int4* d_segs = nullptr;
   int* d_seg_start = nullptr;
+  WgradTables tables() const {
+    return {d_jobs, (int)jobs.size(), d_wg_prefix, total_wgs, d_red_prefix, total_red, d_segs, d_seg_start};
+  }
 };
 
 // One MLP chain call site: gating, the query encoder, an input-function encoder, one soft-MoE call of a block
@@ -292,9 +291,12 @@ struct gnot_plan {
   // operand pieces of the kernels this plan runs: the bf16 mode covers every width up to 256 (chain.hip /
   // linear.hip / the 128-tile weight gradients at d <= 192 as well); above 256 (chainw.hip) the fp32 path
   int npk() const { return D <= 256 ? np : 3; }
-  // linear.hip's image kind of the attention projections (LinearArgs::img): d <= 192 one-piece (bf16 mode) or
-  // x6 (kLinearX6), else fp32 fragment images (also d > 256)
-  int lin_img() const { return D > 192 ? 0 : npk() == 1 ? 1 : kLinearX6 ? 3 : 0; }
+  // linear.hip's image kind of the attention projections (LinearArgs::img).  d <= 192: output-major bf16-piece
+  // images, one RNE piece in the bf16 mode (1), the exact three-piece split in the fp32 mode (3: bf16x6, as
+  // linear2.hip at d = 256; round 5, in place of the exact fp32 MFMA on fp32 fragment images -- configs[1]
+  // (d = 128), one box, interleaved x2: 3.37 / 3.35 ms per step against 3.44 / 3.44, profiles/r05o*).
+  // d > 256: fp32 fragment images (0), the form chainw.hip's Linears run too
+  int lin_img() const { return D > 192 ? 0 : npk() == 1 ? 1 : 3; }
   std::string msave(int l, bool m1) const {
     return moe_recompute ? std::string("mrsave") : "b" + std::to_string(l) + (m1 ? ".m1save" : ".m2save");
   }
@@ -646,7 +648,7 @@ static void plan_images(gnot_plan* p) {
   auto attn_imgs = [&](gnot_plan::AttnImgs& A, int iq, int io, const std::vector<int>& ik,
                        const std::vector<int>& iv, bool selftype) {
     const int D = p->D;
-    const bool lx6 = p->lin_img() == 3;   // fp32 mode at d <= 192 (kLinearX6): output-major x6
+    const bool lx6 = p->lin_img() == 3;   // fp32 mode at d <= 192: output-major x6
     const int x6 = c2 ? c2x6 : b1 ? 3 : lx6 ? 2 : 0;
     auto img = [&](int OT, int KT) {
       return c2 ? new_img_x6(OT, KT, c2np) : b1 ? new_img_x6(OT, KT, 1) : lx6 ? new_img_x6(OT, KT, 3) : new_img(OT, KT);
@@ -709,27 +711,43 @@ static void plan_images(gnot_plan* p) {
 }
 
 // ====================================================================== point-reduction GEMM groups
-// split-K target of the 128-wide kernel
-constexpr long kWide128Wgs = 128;
-// balanced point ranges for a wide group (finish_group) when a per-job split count would leave CUs idle and
-// every job has a point range of its own (no zero-point jobs)
+// the workgroup count balanced_wgrad tests the job count against
+constexpr long kBalanceWgs = 256;
+// balanced point ranges for a Wide256 / B16Rows group (finish_group) when a per-job split count would leave CUs
+// idle and every job has a point range of its own (no zero-point jobs).
+// kBalanceWgs is the large plans' target; a small plan's group aims at 128 or 64 workgroups (finish_group) and is
+// still tested against 256 here.  Kept as it is on purpose: testing against the group's own target would move
+// range boundaries, hence the summation order and the bits of those plans' gradients
 static bool balanced_wgrad(const WgradGroup& G) {
   if (G.jobs.size() < 2) return false;
   for (const auto& J : G.jobs)
     if (J.P <= 0) return false;
-  return 256 % (long)G.jobs.size() != 0;
+  return kBalanceWgs % (long)G.jobs.size() != 0;
 }
-static void finish_group(gnot_plan* p, WgradGroup& G) {
-  G.x6 = true;
+// One weight-gradient group (jobs of lin_job: dz, x, out, in, P): its kernel, split-K counts, slab offsets and
+// launch tables.  b16_rows: the jobs' rows are bf16 storage (moe_group_b16)
+static void finish_group(gnot_plan* p, WgradGroup& G, bool b16_rows = false) {
+  // the kernel.  d = 256: every job's whole 256 x 256 gradient in one workgroup (8 waves, 96 KiB LDS: one per
+  // CU).  d <= 128 (configs[1]): the same design at a 128 x 128 output (4 waves, staging interleaved with the
+  // MFMAs, raw rows by LDS-DMA) instead of the 128-tile kernel (round 5: configs[1] 3.44 -> 3.37 ms)
+  auto within = [&](int edge) {
+    for (const auto& J : G.jobs)
+      if (J.out > edge || J.in > edge) return false;
+    return !G.jobs.empty();
+  };
+  G.kind = b16_rows                     ? WgradKernel::B16Rows
+           : p->D == 256 && within(256) ? WgradKernel::Wide256
+           : p->D <= 128 && within(128) ? WgradKernel::Wide128
+                                        : WgradKernel::Tile128;
+  const bool tiled = G.kind == WgradKernel::Tile128;   // else one workgroup per (job, split)
+  G.scaled = false;
   for (const auto& J : G.jobs)
-    if (J.ldw > 0 || J.state_dh > 0 || J.diag_only) G.x6 = false;   // ldw > 0: per-point weights
-  // the x6 kernel holds ~240 registers per lane: one workgroup per CU leaves the other half of
-  // every SIMD's register file to the concurrent main-stream kernels
-  constexpr long x6_wgs = 256;
-  // d = 256: every job's whole 256 x 256 gradient in one workgroup (8 waves, 96 KiB LDS: one per CU).
-  // The split-K target is fixed (r02bh: 192-512 all within noise), so the split counts the parity
-  // tests exercise are the ones every run uses
-  // plans below kWgradSerialPoints fork their weight gradients beside the caller's stream (serial_wgrad): a
+    if (J.scale != nullptr || J.ldscale != 0) G.scaled = true;   // (ldscale: the sizing pass has null pointers)
+  // the split-K target, in workgroups.  The 128-tile kernel holds ~240 registers per lane: one workgroup per CU
+  // leaves the other half of every SIMD's register file to the concurrent main-stream kernels.  The 256 x 256
+  // kernels' target is fixed (r02bh: 192-512 all within noise), so the split counts the parity tests exercise
+  // are the ones every run uses.
+  // Plans below kWgradSerialPoints fork their weight gradients beside the caller's stream (serial_wgrad): a
   // group holding every CU's register file (the 256 x 256 kernel: 8 waves of 256 registers per CU) leaves the
   // concurrent critical-path kernels no room, so such plans' groups take fewer workgroups.  Keyed on the plan
   // size, not on the fork itself, so a plan gives bitwise the same gradients forked or serial
@@ -738,46 +756,38 @@ static void finish_group(gnot_plan* p, WgradGroup& G) {
   // 64 in the bf16 mode (5.88 -> 5.47); configs[1] (the 128 x 128 kernel) 192 in fp32 (3.28 -> 3.21), 128 in
   // the bf16 mode (the round-5 value)
   const bool small = p->P < gnot_plan::kWgradSerialPoints;
-  const long wide_wgs = !small ? 256 : p->npk() == 1 ? 64 : 128;
-  const long w128_wgs = small && p->npk() != 1 ? 192 : kWide128Wgs;
-  G.wide = G.x6 && p->D == 256 && !G.jobs.empty();
-  for (const auto& J : G.jobs)
-    if (J.out > 256 || J.in > 256) G.wide = false;
-  G.tw = 256;
-  // d <= 128 (configs[1]): the wide kernel's design at a 128 x 128 output (4 waves, staging interleaved with
-  // the MFMAs, raw rows by LDS-DMA) instead of the 128-tile kernel (round 5: configs[1] 3.44 -> 3.37 ms)
-  if (G.x6 && !G.wide && p->D <= 128 && !G.jobs.empty()) {
-    bool fits = true;
-    for (const auto& J : G.jobs)
-      if (J.out > 128 || J.in > 128) fits = false;
-    if (fits) { G.wide = true; G.tw = 128; }
-  }
-  if (G.b16) G.wide = true;          // the bf16-storage kernel has the wide kernel's geometry
-  G.scaled = false;
-  for (const auto& J : G.jobs)
-    if (J.scale != nullptr || J.ldscale != 0) G.scaled = true;   // (ldscale: the sizing pass has null pointers)
-  const long target = G.wide ? (G.tw == 128 ? w128_wgs : wide_wgs) : G.x6 ? x6_wgs : kTargetWGs;
+  const bool bf16 = p->npk() == 1;
+  const long target = tiled                          ? 256
+                      : G.kind == WgradKernel::Wide128 ? (small && !bf16 ? 192 : 128)
+                                                       : (!small ? 256 : bf16 ? 64 : 128);
   long tiles = 0;
   for (auto& J : G.jobs) {
     J.tiles_o = (J.out + kPTile - 1) / kPTile;
     J.tiles_i = (J.in + kPTile - 1) / kPTile;
-    tiles += G.wide ? 1 : J.diag_only ? J.tiles_o : J.tiles_o * J.tiles_i;
+    tiles += tiled ? J.tiles_o * J.tiles_i : 1;
   }
   // floor, not ceil: never more than `target` workgroups, so no CU runs one more than planned
   const long want = std::max<long>(1, target / std::max<long>(tiles, 1));
+  // the one-workgroup-per-split kernels address a split through a buffer resource based at its first row with
+  // 32-bit offsets: a split's rows (+ the stage loaded past its end) stay below 2^31 bytes (every kind is
+  // split by this bound)
+  auto row_bytes = [&](const WgradJob& J) {
+    return b16_rows ? 512L : 4L * std::max<long>(std::max<long>(J.lddz, J.ldx), 1);
+  };
   G.wg_prefix.clear();
   G.red_prefix.clear();
   G.segs.clear();
   G.seg_start.clear();
   G.slab_floats = 0;
-  if (G.wide && G.tw == 256 && balanced_wgrad(G)) {
+  const bool balanced = (G.kind == WgradKernel::Wide256 || G.kind == WgradKernel::B16Rows) && balanced_wgrad(G);
+  if (balanced) {
     // the 256 x 256 kernel holds one workgroup per CU: a per-job split count leaves target % jobs CUs idle
     // (the 40 soft-MoE jobs of configs[2]: 6 splits each = 240 of 256), so cut the group's concatenated
     // points into `target` equal ranges instead (a range crossing a job boundary runs as two segments)
     long T = 0, maxrow = 1;
     for (const auto& J : G.jobs) {
       T += J.P;
-      maxrow = std::max<long>(maxrow, G.b16 ? 512L : 4L * std::max<long>(std::max<long>(J.lddz, J.ldx), 1));
+      maxrow = std::max<long>(maxrow, row_bytes(J));
     }
     long C = std::max<long>((T + target - 1) / target, kMinSplitPoints);
     C = (C + 31) / 32 * 32;                                 // whole stages (kWStage 16, kBStage 32 points)
@@ -796,45 +806,30 @@ static void finish_group(gnot_plan* p, WgradGroup& G) {
       }
     }
     G.seg_start.push_back((int)G.segs.size());
-    int red = 0;
-    for (size_t j = 0; j < G.jobs.size(); ++j) {
-      auto& J = G.jobs[j];
-      J.splits = std::max(1, nslots[j]);
-      const int nt = J.tiles_o * J.tiles_i;
-      J.slab_off = (long)G.slab_floats;
-      G.slab_floats += (size_t)J.splits * nt * kPTile * (kPTile + 1);
-      G.wg_prefix.push_back(0);
-      G.red_prefix.push_back(red);
-      red += nt * kPTile * (kPTile + 1);
+    for (size_t j = 0; j < G.jobs.size(); ++j) G.jobs[j].splits = std::max(1, nslots[j]);
+  } else {
+    for (auto& J : G.jobs) {
+      const long minpts = kMinSplitPoints;   // >= 4 LDS stages per workgroup: bounds the split-K slab traffic
+      const long maxs = std::max<long>(1, (J.P + minpts - 1) / minpts);
+      J.splits = (int)std::min<long>(std::min<long>(want, maxs), 256);
+      const long max_pts = ((1L << 31) - 1) / row_bytes(J) - 64;
+      J.splits = (int)std::max<long>(J.splits, (J.P + max_pts - 1) / max_pts);
     }
-    G.total_wgs = (int)G.seg_start.size() - 1;
-    G.total_red = red;
-    size_t& slab = p->slab_wgrad_floats;
-    slab = std::max(slab, G.slab_floats);
-    return;
   }
+  // slab offsets and the two prefixes (balanced: the workgroups are the ranges, the kernel reads no prefix)
   int wg = 0, red = 0;
   for (auto& J : G.jobs) {
-    const long minpts = kMinSplitPoints;   // >= 4 LDS stages per workgroup: bounds the split-K slab traffic
-    const long maxs = std::max<long>(1, (J.P + minpts - 1) / minpts);
-    J.splits = (int)std::min<long>(std::min<long>(want, maxs), 256);
-    // the wide / bf16-row kernels address one split through a buffer resource based at its first row
-    // with 32-bit offsets: a split's rows (+ the stage loaded past its end) stay below 2^31 bytes
-    const long row_bytes = G.b16 ? 512L : 4L * std::max<long>(std::max<long>(J.lddz, J.ldx), 1);
-    const long max_pts = ((1L << 31) - 1) / row_bytes - 64;
-    J.splits = (int)std::max<long>(J.splits, (J.P + max_pts - 1) / max_pts);
-    const int nt = J.diag_only ? J.tiles_o : J.tiles_o * J.tiles_i;
+    const int nt = J.tiles_o * J.tiles_i;
     J.slab_off = (long)G.slab_floats;
     G.slab_floats += (size_t)J.splits * nt * kPTile * (kPTile + 1);
-    G.wg_prefix.push_back(wg);
-    wg += (G.wide ? 1 : nt) * J.splits;
+    G.wg_prefix.push_back(balanced ? 0 : wg);
+    wg += (tiled ? nt : 1) * J.splits;
     G.red_prefix.push_back(red);
     red += nt * kPTile * (kPTile + 1);
   }
-  G.total_wgs = wg;
+  G.total_wgs = balanced ? (int)G.seg_start.size() - 1 : wg;
   G.total_red = red;
-  size_t& slab = (!G.jobs.empty() && G.jobs[0].state_dh > 0) ? p->slab_state_floats : p->slab_wgrad_floats;
-  slab = std::max(slab, G.slab_floats);
+  p->slab_wgrad_floats = std::max(p->slab_wgrad_floats, G.slab_floats);
 }
 
 // attention-state group (state.hip): one job per sample, ceil(P / kStatePts) partial states each
@@ -970,8 +965,7 @@ static void build_groups(gnot_plan* p) {
         const float* x = at(save, (j == 0 ? NL : (long)c * 2 * NL + NL + j) * lay);
         lin_job(C.wg, C.firsts[c] + j, at(dz, ((long)c * NL + j) * lay), D, x, D, 0, P);
       }
-    C.wg.b16 = true;
-    finish_group(p, C.wg);
+    finish_group(p, C.wg, true);
   };
   auto state_group = [&](WgradGroup& G, const float* A, long lda, const float* Bm, long ldb, const float* w,
                          long ldw, const std::vector<long>& off, float* state) {
@@ -982,8 +976,8 @@ static void build_groups(gnot_plan* p) {
       J.out = p->hd(); J.in = p->hd();            // H heads of dh (the internal head width)
       J.dW = at(state, b * per_state);
       J.db = J.dW;
-      J.w = at(w, off[b] * ldw); J.ldw = ldw; J.wdh = dh;
-      J.state_dh = dh; J.diag_only = 1;
+      J.w = at(w, off[b] * ldw); J.ldw = ldw;
+      J.state_dh = dh;
       J.P = (int)(off[b + 1] - off[b]);
       G.jobs.push_back(J);
     }
@@ -1021,8 +1015,8 @@ static void build_groups(gnot_plan* p) {
           WgradJob J{};
           const long o = p->fnoff[i][b];
           J.dz = at(kv, o * 2 * D); J.lddz = 2 * D; J.x = at(kv, D + o * 2 * D); J.ldx = 2 * D;
-          J.out = p->hd(); J.in = p->hd(); J.dW = at(st, b * per_state); J.db = J.dW; J.wdh = dh;
-          J.state_dh = dh; J.diag_only = 1; J.P = (int)(p->fnoff[i][b + 1] - o);
+          J.out = p->hd(); J.in = p->hd(); J.dW = at(st, b * per_state); J.db = J.dW;
+          J.state_dh = dh; J.P = (int)(p->fnoff[i][b + 1] - o);
           p->st_fn.jobs.push_back(J);
         }
       }
@@ -1810,8 +1804,7 @@ double group_flops(const WgradGroup& G) {
 int run_state(Ctx& c, const WgradGroup& G) {
   if (G.jobs.empty()) return GNOT_OK;
   ProfScope ps(c, "state", group_flops(G));
-  GNOT_CK(launch_state(G.d_jobs, G.d_wg_prefix, (int)G.jobs.size(), G.total_wgs, G.d_red_prefix,
-                       G.total_red, c.p->P_("slab_state"), G.jobs[0].out, G.jobs[0].state_dh, G.state_pts,
+  GNOT_CK(launch_state(G.tables(), c.p->P_("slab_state"), G.jobs[0].out, G.jobs[0].state_dh, G.state_pts,
                        G.state_nw, G.state_mfma, c.s));
   return GNOT_OK;
 }
@@ -1850,14 +1843,11 @@ int guard_write(Ctx& c, const float* buf) {
 
 // one weight-gradient group's launches (point-reduction GEMM + split-K reduce)
 int launch_group(gnot_plan* p, const WgradGroup& G, float* slab, hipStream_t s) {
-  if (G.b16)
-    GNOT_CK(launch_wgrad_b16(G.d_jobs, G.d_wg_prefix, (int)G.jobs.size(), G.total_wgs, G.d_red_prefix, G.total_red,
-                             slab, s, G.d_segs, G.d_seg_start, p->bwd_accumulate));
-  else
-    GNOT_CK(launch_wgrad(G.d_jobs, G.d_wg_prefix, (int)G.jobs.size(), G.total_wgs, G.d_red_prefix, G.total_red, slab,
-                         s, G.x6, G.wide, p->npk(), G.tw, G.d_segs, G.d_seg_start, p->bwd_accumulate, G.scaled));
+  GNOT_CK(launch_wgrad(G.kind, G.tables(), slab, p->npk(), G.scaled, p->bwd_accumulate, s));
   return GNOT_OK;
 }
+// its profiling class: the bf16-row MoE weight gradients are HBM-bound, the others are not
+const char* wgrad_class(const WgradGroup& G) { return G.kind == WgradKernel::B16Rows ? "wgrad_b16" : "wgrad"; }
 
 // the group's gradient ranges summed over the ranks (gnot_plan_set_grad_comm) on the comm stream, once
 // the event `done` (the group's kernels) has passed: consecutive canonical Linears are adjacent in the
@@ -1883,7 +1873,7 @@ int grad_allreduce(gnot_plan* p, const WgradGroup& G, hipEvent_t done) {
 int run_wgrad_here(Ctx& c, const WgradGroup& G, float* slab) {
   if (G.jobs.empty()) return GNOT_OK;
   {
-    ProfScope ps(c, G.b16 ? "wgrad_b16" : "wgrad", group_flops(G));
+    ProfScope ps(c, wgrad_class(G), group_flops(G));
     GNOT_RUN(launch_group(c.p, G, slab, c.s));
   }
   if (c.p->grad_comm_live) {
@@ -1931,8 +1921,7 @@ int flush_deferred(Ctx& c) {
   for (const auto& d : pend) {
     GNOT_CK(hipStreamWaitEvent(p->side, d.fork, 0));
     {
-      // profiled as its own class: the bf16-row MoE weight gradients are HBM-bound, the others are not
-      ProfScope ps(c, d.G->b16 ? "wgrad_b16" : "wgrad", group_flops(*d.G), p->side);
+      ProfScope ps(c, wgrad_class(*d.G), group_flops(*d.G), p->side);
       GNOT_RUN(launch_group(p, *d.G, p->P_("slab_wgrad"), p->side));
     }
     hipEvent_t done = next_event(p);

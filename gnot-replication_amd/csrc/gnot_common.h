@@ -142,35 +142,12 @@ GNOT_DEV void store_rows(const float (&a)[KT][4], float* __restrict__ Y, long ld
   }
 }
 
-// OUT^T(16*OT x 16 points) = W(16*OT x 16*KT) * IN^T with W given in packed fragment order:
-// Wp[(o*KT + T)*64 + lane] = { W[16o + (lane&15)][16T + 4(lane>>4) + r] : r = 0..3 }
-// acc must be pre-initialised (bias or zero).
-template <int KT, int OT>
-GNOT_DEV void mm_tiles(const float4* __restrict__ Wp, const float (&in)[KT][4], f32x4 (&acc)[OT],
-                       int lane) {
-#pragma unroll
-  for (int T = 0; T < KT; ++T) {
-    float4 w[OT];
-#pragma unroll
-    for (int o = 0; o < OT; ++o) w[o] = Wp[(o * KT + T) * WAVE + lane];
-#pragma unroll
-    for (int o = 0; o < OT; ++o) acc[o] = mfma_k16(w[o], in[T], acc[o]);
-  }
-}
-
 // ---- LDS-staged weight images ---------------------------------------------------------------
-// A layer's packed A-operand image (OT x KT tiles of 1 KiB) is copied into LDS by the whole
-// workgroup with global_load_lds (16 B per lane, one 1 KiB wave-instruction each, no VGPRs), then every
-// wave of the workgroup reads its fragments with ds_read_b128 (contiguous -> conflict free).  Images
-// larger than kLdsImageKB are processed in chunks of `och` output tiles.
-constexpr int kLdsImageKB = 64;
-
-constexpr int lds_och(int KT, int OT) {
-  int c = OT;
-  while (c > 1 && (c * KT > kLdsImageKB || OT % c != 0)) --c;
-  return c;
-}
-
+// A layer's packed A-operand image (tiles of 1 KiB) is copied into LDS by the whole workgroup with
+// global_load_lds (16 B per lane, one 1 KiB wave-instruction each, no VGPRs), then every wave of the
+// workgroup reads its fragments with ds_read_b128 (contiguous -> conflict free).  The image layout of the
+// fp32 fragment form: Wp[(o*KT + T)*64 + lane] = { W[16o + (lane&15)][16T + 4(lane>>4) + r] : r = 0..3 }
+// (output tile o, k-tile T; pack.hip).
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 typedef __attribute__((address_space(1))) const void* global_cvoid_ptr;
 
@@ -187,46 +164,6 @@ GNOT_DEV void stage_image(float4* lds, const float4* __restrict__ g, int n4, int
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(g), (short)0, n4 * 16, 0x00020000);
   for (int base = wave * WAVE; base < n4; base += nwaves * WAVE)
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_ptr)(lds + base), 16, lane * 16, base * 16, 0, 0);
-}
-
-// acc[o] (o < OT) += W x in  with W (OT x KT tiles, packed) streamed through the LDS buffer `lds`
-// (capacity >= lds_och(KT,OT)*KT*64 float4).  Contains __syncthreads(): call uniformly.
-template <int KT, int OT>
-GNOT_DEV void mm_tiles_lds(const float4* __restrict__ Wg, float4* lds, const float (&in)[KT][4], f32x4 (&acc)[OT],
-                           int nwaves, int wave, int lane) {
-  constexpr int OCH = lds_och(KT, OT);
-#pragma unroll
-  for (int c = 0; c < OT / OCH; ++c) {
-    __syncthreads();                                   // previous readers of lds are done
-    stage_image(lds, Wg + c * OCH * KT * WAVE, OCH * KT * WAVE, nwaves, wave, lane);
-    lds_dma_wait();
-    __syncthreads();
-    // fragments of k-tile T+1 are read from LDS while the MFMAs of k-tile T run; within a k-tile the
-    // MFMA order is k-step-outer / output-tile-inner, so consecutive MFMAs use independent
-    // accumulators (the f32 16x16x4 MFMA has a 40-cycle dependent latency vs 32-cycle issue)
-    float4 wc[OCH], wn[OCH];
-#pragma unroll
-    for (int o = 0; o < OCH; ++o) wc[o] = lds[(o * KT + 0) * WAVE + lane];
-#pragma unroll
-    for (int T = 0; T < KT; ++T) {
-      if (T + 1 < KT) {
-#pragma unroll
-        for (int o = 0; o < OCH; ++o) wn[o] = lds[(o * KT + T + 1) * WAVE + lane];
-      }
-#pragma unroll
-      for (int o = 0; o < OCH; ++o) acc[c * OCH + o] = mfma4(wc[o].x, in[T][0], acc[c * OCH + o]);
-#pragma unroll
-      for (int o = 0; o < OCH; ++o) acc[c * OCH + o] = mfma4(wc[o].y, in[T][1], acc[c * OCH + o]);
-#pragma unroll
-      for (int o = 0; o < OCH; ++o) acc[c * OCH + o] = mfma4(wc[o].z, in[T][2], acc[c * OCH + o]);
-#pragma unroll
-      for (int o = 0; o < OCH; ++o) acc[c * OCH + o] = mfma4(wc[o].w, in[T][3], acc[c * OCH + o]);
-      if (T + 1 < KT) {
-#pragma unroll
-        for (int o = 0; o < OCH; ++o) wc[o] = wn[o];
-      }
-    }
-  }
 }
 
 // ---- pipelined weight stream ------------------------------------------------------------------
@@ -360,9 +297,6 @@ GNOT_DEV rsrc_t make_rsrc(const void* p, unsigned bytes) {
 }
 GNOT_DEV float buf_load_f32(rsrc_t r, int voff, int soff) {
   return u2f(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-GNOT_DEV float4 buf_load_f32x4(rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
 // stores past the resource's `bytes` are dropped (tail lanes need no predicate).
 // The whole offset goes in the VGPR and soffset stays the constant 0: a 128-bit buffer store whose

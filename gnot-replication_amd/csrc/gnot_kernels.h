@@ -61,8 +61,8 @@ struct LinearArgs {
   int nsoft;                         // feature-softmax on output columns [0, nsoft)
   int dh;                            // head width for that softmax
   int np = 3;                        // linear2: operand pieces (3 = bf16x6, 1 = bf16 mode)
-  // linear.hip (d <= 192): 0 = fp32 fragment images on the fp32 MFMA; 1 / 3 = output-major bf16-piece images
-  // (the bf16 mode / the fp32 mode's bf16x6, kLinearX6)
+  // linear.hip: 0 = fp32 fragment images on the fp32 MFMA (widths 16 and 320 .. 512); 1 / 3 = output-major
+  // bf16-piece images (d <= 192: the bf16 mode / the fp32 mode's bf16x6).  The plan's rule: gnot_plan::lin_img
   int img = 0;
   // padded hidden width (the plan runs a real width dr < D in tiles of D, engine.cpp gnot_plan_create):
   // output column c with c % D >= dreal is written as 0 (the softmax of a head's features must not leak
@@ -78,7 +78,8 @@ struct LinearArgs {
   int kcols[kMaxSeg] = {};           // per-segment input columns when they differ (K-split); 0 = K
 };
 // D: the K width the kernel is instantiated at (the internal width for the projections, a layer's input
-// tiles x 16 for the chains).  D in (512, 1024] (a multiple of 128): the contraction runs as two K-halves of
+// tiles x 16 for the chains).  img = 0 runs at D = 16 and 320 .. 512 only (what a plan reaches: chainw.hip's
+// Linears and the d > 256 projections); any other width is hipErrorInvalidValue.  D in (512, 1024] (a multiple of 128): the contraction runs as two K-halves of
 // every segment on the D / 2 kernels -- X[s] + D / 2 for the second half and an image made of two half
 // images (PackJob::kh), the second (NO / 16) x (D / 32) tiles after the first -- in launches of at most
 // kMaxSeg segments (later ones accumulate; a softmax epilogue must fit one launch); a.K must then be D
@@ -146,10 +147,6 @@ struct ChainArgs {
   // pair-interleaved rows (the strides are the fp32 stage's), summed by launch_moe_combine_b16
   int stage_b16 = 0;
 };
-// d <= 192 projections in the fp32 mode: bf16x6 on output-major 3-piece images (pack x6 = 2), as linear2.hip
-// at d = 256 (round 5; exact fp32 MFMA on fp32 fragment images before -- the form d > 192 keeps).
-// configs[1] (d = 128), one box, interleaved x2: 3.37 / 3.35 ms per step against 3.44 / 3.44 (profiles/r05o*)
-constexpr bool kLinearX6 = true;
 // d > 256: chains one Linear at a time (linear.hip + elementwise passes, chainw.hip)
 hipError_t launch_chainw(const ChainArgs& a, bool bwd, hipStream_t s);
 hipError_t launch_chain_fwd(const ChainArgs& a, hipStream_t s);
@@ -158,8 +155,9 @@ hipError_t launch_chain_bwd(const ChainArgs& a, hipStream_t s);
 // AND WpT
 hipError_t launch_chain2(const ChainArgs& a, bool bwd, hipStream_t s);
 
-// ------------------------------------------------------------------ point-reduction GEMM (wgrad.hip)
-// C[out, in] = sum_p dz[p, :out]^T x[p, :in] over a point range, plus column sums of dz.
+// ------------------------------------------------------------------ point-reduction GEMM (wgrad.hip, state.hip)
+// One job of a point reduction.  Weight gradients (wgrad.hip): dW[out, in] = sum_p dz[p, :out]^T x[p, :in] over the
+// job's points, db = the column sums of dz.  Attention states (state.hip): the same sums per head, see below.
 // (alignas(16): 128 bytes per job, so that in the device tables -- 256-byte aligned, engine.cpp bind -- no job
 // straddles a 128-byte line and the kernels' scalar loads of its fields stay aligned)
 struct alignas(16) WgradJob {
@@ -170,9 +168,10 @@ struct alignas(16) WgradJob {
   int ldscale;                       // stride (floats) between two points' scale
   float* dW;                         // [out, in] row-major, or the state [H][dh*dh + dh] (state_dh > 0)
   float* db;                         // [out] column sums of A, or null
-  const float* w; long ldw; int wdh; // optional per-(point, column/wdh) weight of the column sums
-  int state_dh;                      // > 0: keep only dh x dh diagonal blocks, state layout
-  int diag_only;                     // compute only the diagonal 128x128 tiles
+  const float* w; long ldw;          // state jobs: optional per-(point, head) weight of the column sums
+  int pad0_;                         // (keeps every field's offset and the 128 bytes)
+  int state_dh;                      // state jobs: the head width dh (> 0); weight-gradient jobs: 0
+  int pad1_;
   int P;
   int tiles_o, tiles_i;              // 128x128 output tiles
   int splits;                        // split-K count over points
@@ -184,34 +183,41 @@ struct alignas(16) WgradJob {
   const float* scale;
 };
 static_assert(sizeof(WgradJob) == 128, "WgradJob: one 128-byte line per job");
-// one workgroup per (job, tile, split); wg_prefix / red_prefix: per-job prefix sums of workgroups and
-// of reduce elements (ntile * 128 * 129)
-// x6: plain weight-gradient jobs only (no w, state_dh, diag_only) on the bf16x6 MFMA kernel
-// wide: the same on the 256 x 256-tile kernel (out, in <= 256; ONE workgroup per (job, split), so
-//       wg_prefix counts splits only)
-// tw: the wide kernel's output edge, 256 (d = 256) or 128 (d <= 128: every job within 128 x 128)
-// segs / seg_start (wide kernel only, optional): the balanced form -- workgroup w runs the point ranges
-// segs[seg_start[w] .. seg_start[w+1]) = {job, slab slot, first point, end point}; each job's J.splits
-// then counts the ranges that touch it (slots 0 .. splits-1)
+// A group's device tables: its jobs, the per-job prefix sums of workgroups and of reduce elements, and (the
+// balanced form of the two one-workgroup-per-split kernels, optional) per-workgroup point ranges -- workgroup w runs
+// segs[seg_start[w] .. seg_start[w+1]) = {job, slab slot, first point, end point}; each job's `splits` then counts
+// the ranges that touch it (slots 0 .. splits-1)
+struct WgradTables {
+  const WgradJob* jobs = nullptr;
+  int njobs = 0;
+  const int* wg_prefix = nullptr;    // [njobs]
+  int total_wgs = 0;
+  const int* red_prefix = nullptr;   // [njobs]; weight gradients: ntile * 128 * 129 elements per job
+  int total_red = 0;
+  const int4* segs = nullptr;
+  const int* seg_start = nullptr;
+};
+// The weight-gradient kernels (all bf16 MFMA, one slab layout, one reduce):
+enum class WgradKernel {
+  Tile128,   // any out / in: one workgroup per (job, 128 x 128 tile, split)
+  Wide256,   // out, in <= 256 (d = 256): one workgroup per (job, split) owns the whole gradient
+  Wide128,   // out, in <= 128 (d <= 128): the same design at a 128 x 128 output
+  B16Rows,   // bf16-storage jobs (ChainArgs::b16s): dz and x are bf16 pair-interleaved rows [P, 256] (x already
+             // the Linear's input, no GELU), out = in = 256, one workgroup per (job, split)
+};
+// np: operand pieces of the fp32-row kernels (3 = bf16x6, 1 = the bf16 mode); B16Rows ignores it
+// scaled: the group holds jobs with WgradJob::scale (Wide256 at np = 3 only, else hipErrorInvalidValue): the
+// kernel instantiation that stages them; a scale in any other launch is ignored
 // accumulate: the split-K finish adds its sum onto dW / db instead of overwriting them (per launch, not in
-// the job tables: one bound plan overwrites in one backward and accumulates in the next); jobs with
-// state_dh > 0 always overwrite
-// scaled: the group holds jobs with WgradJob::scale (wide, np = 3, tw = 256 only): the kernel instantiation
-// that stages them; jobs with a scale in any other launch are an error of the caller (the scale is ignored)
-hipError_t launch_wgrad(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
-                        const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, bool x6 = false,
-                        bool wide = false, int np = 3, int tw = 256,    // np: operand pieces (1 = bf16 mode)
-                        const int4* segs = nullptr, const int* seg_start = nullptr, bool accumulate = false,
-                        bool scaled = false);
-// bf16-storage jobs (ChainArgs::b16s): dz and x point at bf16 pair-interleaved rows [P, 256] (x already
-// the Linear's input, no GELU), out = in = 256, one workgroup per (job, split) as the wide kernel
-hipError_t launch_wgrad_b16(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
-                            const int* red_prefix_dev, int total_red, float* slab, hipStream_t s,
-                            const int4* segs = nullptr, const int* seg_start = nullptr, bool accumulate = false);
+// the job tables: one bound plan overwrites in one backward and accumulates in the next)
+// segs / seg_start: Wide256 and B16Rows only
+hipError_t launch_wgrad(WgradKernel kind, const WgradTables& t, float* slab, int np, bool scaled, bool accumulate,
+                        hipStream_t s);
 
 // ------------------------------------------------------------------ attention states (state.hip)
 // Jobs are WgradJobs with state_dh > 0: A = dz/lddz, B = x/ldx, optional w/ldw, out = dW as
-// [H][dh*dh + dh], `splits` partials of state_pts(d) points each at slab + slab_off.
+// [H][dh*dh + dh], `splits` partials of state_pts(d) points each at slab + slab_off.  state.hip has its own
+// partial-state kernels and its own reduce (always overwrites); it reads the tables' jobs and two prefixes.
 // Two kernels: state_mfma (fp32 MFMA, rows straight from HBM, dh = 16/32/64 with H % 4 == 0;
 // below GNOT_STATE_MFMA_MIN points the VALU form) and the VALU state_partial (LDS-staged rows, any width).
 // (the instantiated state_mfma_kernel<DH, HPW> forms, HPW = heads per wave = d / dh / 4: 1 / 2 / 4 at dh 16 and
@@ -233,10 +239,8 @@ inline long state_mfma_min_points() {
   const char* e = std::getenv("GNOT_STATE_MFMA_MIN");
   return e ? std::atol(e) : 65536;
 }
-hipError_t launch_state(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
-                        const int* red_prefix_dev, int total_red, float* slab, int d, int dh, int pts, int nw,
-                        bool mfma, hipStream_t s);   // d: row width, pts: points per workgroup, nw: per-point
-                                                     // weights (0 or H), mfma: state_mfma_kernel (state_mfma_ok)
+// d: row width, pts: points per workgroup, nw: per-point weights (0 or H), mfma: state_mfma_kernel (state_mfma_ok)
+hipError_t launch_state(const WgradTables& t, float* slab, int d, int dh, int pts, int nw, bool mfma, hipStream_t s);
 
 // ------------------------------------------------------------------ attention (attn.hip)
 struct AttnApplyArgs {

@@ -19,7 +19,7 @@
 namespace gnot {
 
 // NP-piece forms (round 5): the images are OUTPUT-MAJOR bf16 pieces (pack x6 = 3 for one RNE piece, the
-// bf16 arithmetic mode; x6 = 2 for the exact three-piece split of the fp32 mode, kLinearX6, as linear2.hip's): block (o, kb) = 16 outputs x 32 contraction slots, piece q at Wg[((o * KB + kb) * NP + q) *
+// bf16 arithmetic mode; x6 = 2 for the exact three-piece split of the fp32 mode, as linear2.hip's): block (o, kb) = 16 outputs x 32 contraction slots, piece q at Wg[((o * KB + kb) * NP + q) *
 // 64 + lane], so a workgroup's OC output tiles are one contiguous run of OC * KB blocks.  Chunks of OCH tiles
 // (OCH * KB * NP KiB <= the buffer) stream through two LDS buffers; the input is split once per segment (bp,
 // NP 16x16x32 B operands per k-block); per block one v_mfma_f32_16x16x32_bf16 (NP = 1) or the six order <= 2
@@ -220,7 +220,15 @@ int linear_oc(int D, int NO, int nsoft, int dh) {
   GNOT_LIN(384, 1) GNOT_LIN(384, 2) GNOT_LIN(384, 4) GNOT_LIN(448, 1) GNOT_LIN(448, 2) GNOT_LIN(448, 4)   \
   GNOT_LIN(512, 1) GNOT_LIN(512, 2) GNOT_LIN(512, 4) GNOT_LIN(320, 20) GNOT_LIN(384, 24) GNOT_LIN(448, 28) \
   GNOT_LIN(512, 32)
-// the d <= 192 cases of GNOT_LIN_CASES (the bf16 mode's one-piece kernels)
+// the fp32-image widths launch_linear can be asked for: 16 (a chainw.hip Linear with a one-tile input) and
+// 320 .. 512 (the d > 256 projections and chainw.hip Linears, whole or as the K-halves of 640 .. 1024); d <= 192
+// runs the bf16-piece kernels below and d = 256 is linear2.hip's.  launch_linear_batch runs fp32 images at every
+// width: it keeps all of GNOT_LIN_CASES
+#define GNOT_LIN_F32_CASES                                                                              \
+  GNOT_LIN(16, 1) GNOT_LIN(320, 1) GNOT_LIN(320, 2) GNOT_LIN(320, 4) GNOT_LIN(320, 20) GNOT_LIN(384, 1)   \
+  GNOT_LIN(384, 2) GNOT_LIN(384, 4) GNOT_LIN(384, 24) GNOT_LIN(448, 1) GNOT_LIN(448, 2) GNOT_LIN(448, 4)  \
+  GNOT_LIN(448, 28) GNOT_LIN(512, 1) GNOT_LIN(512, 2) GNOT_LIN(512, 4) GNOT_LIN(512, 32)
+// the d <= 192 cases of GNOT_LIN_CASES (the bf16-piece kernels: NP = 1, the bf16 mode, and NP = 3, bf16x6)
 #define GNOT_LIN_B1_CASES                                                                                         \
   GNOT_LIN_B1(16, 1) GNOT_LIN_B1(32, 1) GNOT_LIN_B1(32, 2) GNOT_LIN_B1(48, 1) GNOT_LIN_B1(48, 3) GNOT_LIN_B1(64, 1)   \
   GNOT_LIN_B1(64, 2) GNOT_LIN_B1(64, 4) GNOT_LIN_B1(80, 1) GNOT_LIN_B1(80, 5) GNOT_LIN_B1(96, 1) GNOT_LIN_B1(96, 2)   \
@@ -270,7 +278,7 @@ hipError_t launch_linear(const LinearArgs& a, int D, hipStream_t s) {
 #define GNOT_LIN(DD, OO) \
   if (D == DD && oc == OO) { hipLaunchKernelGGL((linear_kernel<DD, OO>), grid, block, 0, s, a); return hipGetLastError(); }
   // d <= 192 on output-major bf16-piece images (LinearArgs::img): the bf16 mode (1) and the fp32 mode's bf16x6
-  // (3, kLinearX6); the d = 256 projections are linear2.hip's
+  // (3); the d = 256 projections are linear2.hip's
 #define GNOT_LIN_B1(DD, OO)                                                                              \
   if (D == DD && oc == OO) {                                                                              \
     if (a.img == 1) hipLaunchKernelGGL((linear_kernel<DD, OO, 1>), grid, block, 0, s, a);                 \
@@ -282,7 +290,7 @@ hipError_t launch_linear(const LinearArgs& a, int D, hipStream_t s) {
     GNOT_LIN_B1_CASES
     return hipErrorInvalidValue;
   }
-  GNOT_LIN_CASES
+  GNOT_LIN_F32_CASES
 #undef GNOT_LIN
 #undef GNOT_LIN_B1
   return hipErrorInvalidValue;

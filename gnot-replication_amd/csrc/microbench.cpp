@@ -172,6 +172,7 @@ int main(int argc, char** argv) {
     LinearArgs l{};
     l.nseg = 1; l.X[0] = X; l.Wp[0] = W; l.ldx = D; l.nsum = 1; l.K = D; l.bias = bias; l.Y = Y; l.ldy = NO;
     l.NO = NO; l.P = P; l.epi = EPI_STORE; l.nsoft = 0; l.dh = 16;
+    l.img = 3;   // linear.hip (D != 256): the fp32 mode's bf16x6 images, what a plan runs at d <= 192
     t = time_us([&] { CK(D == 256 ? launch_linear2(l, nullptr) : launch_linear(l, D, nullptr)); });
     std::printf("linear     P=%d K=%d NO=%d: %8.2f us  %6.1f TFLOP/s\n", P, D, NO, t, 2.0 * P * D * NO / t / 1e6);
     if (D == 256) {
@@ -197,8 +198,8 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(save, fresh, (size_t)E * NL * P * D * 4, hipMemcpyDeviceToDevice));
     CK(hipFree(fresh));
   }
-  // weight-gradient point-reduction GEMM of one MoE chain group: E*NL jobs of D x D over P points,
-  // split-K exactly as the engine sizes it (<= 512 workgroups, >= 128 points per split)
+  // weight-gradient point-reduction GEMM of one MoE chain group: E*NL jobs of D x D over P points on the
+  // 128-tile kernel, split-K as the engine sizes it (<= 256 workgroups, >= 128 points per split)
   {
     std::vector<WgradJob> jobs;
     std::vector<int> wg_pre, red_pre;
@@ -207,7 +208,7 @@ int main(int argc, char** argv) {
     float* dW = dalloc((size_t)E * NL * (D * D + D), 0.f);
     const int njobs = E * NL;
     const int tiles = ((D + 127) / 128) * ((D + 127) / 128);
-    const long want = std::max<long>(1, 512 / ((long)njobs * tiles));
+    const long want = std::max<long>(1, 256 / ((long)njobs * tiles));
     for (int k = 0; k < njobs; ++k) {
       WgradJob J{};
       J.dz = dz + (size_t)k * P * D; J.lddz = D; J.x = save + (size_t)k * P * D; J.ldx = D; J.x_gelu = 1;
@@ -229,19 +230,20 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&dpre, pre.size() * sizeof(int)));
     CK(hipMemcpy(dpre, pre.data(), pre.size() * sizeof(int), hipMemcpyHostToDevice));
     float* slab = dalloc((size_t)slab_off, 0.f);
-    t = time_us([&] { CK(launch_wgrad(djobs, dpre, njobs, wg, dpre + njobs, red, slab, nullptr)); }, 20);
-    std::printf("wgrad MoE  %d jobs P=%d D=%d (%d WGs): %8.2f us  %6.1f TFLOP/s\n", njobs, P, D, wg, t, fl / t / 1e6);
+    const WgradTables tb{djobs, njobs, dpre, wg, dpre + njobs, red};
+    auto tile128 = [&](const WgradJob* j, hipStream_t st) {
+      WgradTables u = tb;
+      u.jobs = j;
+      CK(launch_wgrad(WgradKernel::Tile128, u, slab, 3, false, false, st));
+    };
+    t = time_us([&] { tile128(djobs, nullptr); }, 20);
+    std::printf("wgrad MoE  bf16x6 128-tile, %d jobs P=%d D=%d (%d WGs): %8.2f us  %6.1f TFLOP/s\n", njobs, P, D, wg, t,
+                fl / t / 1e6);
+    // its result: what the other kernels' rel-L2 columns compare against
     const size_t ndw = (size_t)E * NL * (D * D + D);
     std::vector<float> ref(ndw), got(ndw);
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(ref.data(), dW, ndw * 4, hipMemcpyDeviceToHost));
-    t = time_us([&] { CK(launch_wgrad(djobs, dpre, njobs, wg, dpre + njobs, red, slab, nullptr, true)); }, 20);
-    CK(hipDeviceSynchronize());
-    CK(hipMemcpy(got.data(), dW, ndw * 4, hipMemcpyDeviceToHost));
-    double num = 0, den = 0;
-    for (size_t i = 0; i < ndw; ++i) { num += (got[i] - ref[i]) * (double)(got[i] - ref[i]); den += (double)ref[i] * ref[i]; }
-    std::printf("wgrad MoE  bf16x6:                     %8.2f us  %6.1f TFLOP/s  (rel-L2 vs fp32 %.2e)\n", t, fl / t / 1e6,
-                std::sqrt(num / (den + 1e-30)));
     if (D == 256) {   // the 256 x 256-tile kernel: one workgroup per (job, split)
       for (int wgs : {256, 512}) {
         std::vector<WgradJob> wj(jobs);
@@ -263,19 +265,21 @@ int main(int argc, char** argv) {
         CK(hipMalloc(&dwpre, wpre.size() * sizeof(int)));
         CK(hipMemcpy(dwpre, wpre.data(), wpre.size() * sizeof(int), hipMemcpyHostToDevice));
         CK(hipMalloc(&wslab, soff * sizeof(float)));
-        t = time_us([&] { CK(launch_wgrad(dwj, dwpre, njobs, njobs * splits, dwpre + njobs, red, wslab, nullptr, true, true)); }, 20);
+        const WgradTables wt{dwj, njobs, dwpre, njobs * splits, dwpre + njobs, red};
+        auto wide = [&](int np, bool scaled) { CK(launch_wgrad(WgradKernel::Wide256, wt, wslab, np, scaled, false, nullptr)); };
+        t = time_us([&] { wide(3, false); }, 20);
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(got.data(), dW, ndw * 4, hipMemcpyDeviceToHost));
         double n2 = 0, d2 = 0;
         for (size_t i = 0; i < ndw; ++i) { n2 += (got[i] - ref[i]) * (double)(got[i] - ref[i]); d2 += (double)ref[i] * ref[i]; }
-        std::printf("wgrad MoE  bf16x6 wide 256x256 (%d WGs):  %8.2f us  %6.1f TFLOP/s  (rel-L2 vs fp32 %.2e)\n",
+        std::printf("wgrad MoE  bf16x6 wide 256x256 (%d WGs):  %8.2f us  %6.1f TFLOP/s  (rel-L2 vs 128-tile bf16x6 %.2e)\n",
                     njobs * splits, t, fl / t / 1e6, std::sqrt(n2 / (d2 + 1e-30)));
-        t = time_us([&] { CK(launch_wgrad(dwj, dwpre, njobs, njobs * splits, dwpre + njobs, red, wslab, nullptr, true, true, 1)); }, 20);
+        t = time_us([&] { wide(1, false); }, 20);
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(got.data(), dW, ndw * 4, hipMemcpyDeviceToHost));
         n2 = 0; d2 = 0;
         for (size_t i = 0; i < ndw; ++i) { n2 += (got[i] - ref[i]) * (double)(got[i] - ref[i]); d2 += (double)ref[i] * ref[i]; }
-        std::printf("wgrad MoE  bf16 wide 256x256 (%d WGs):    %8.2f us  %6.1f TFLOP/s  (rel-L2 vs fp32 %.2e)\n",
+        std::printf("wgrad MoE  bf16 wide 256x256 (%d WGs):    %8.2f us  %6.1f TFLOP/s  (rel-L2 vs 128-tile bf16x6 %.2e)\n",
                     njobs * splits, t, fl / t / 1e6, std::sqrt(n2 / (d2 + 1e-30)));
         {
           // the serial soft-MoE form (WgradJob::scale): every chain's last Linear reads ONE shared dZ (dquery)
@@ -284,10 +288,7 @@ int main(int argc, char** argv) {
           for (int k = 0; k < njobs; ++k)
             if (k % NL == NL - 1) { sj[k].dz = dz; sj[k].scale = scores + k / NL; sj[k].ldscale = 16; }
           CK(hipMemcpy(dwj, sj.data(), sj.size() * sizeof(WgradJob), hipMemcpyHostToDevice));
-          t = time_us([&] {
-            CK(launch_wgrad(dwj, dwpre, njobs, njobs * splits, dwpre + njobs, red, wslab, nullptr, true, true, 3, 256,
-                            nullptr, nullptr, false, true));
-          }, 20);
+          t = time_us([&] { wide(3, true); }, 20);
           std::printf("wgrad MoE  bf16x6 wide, last Linear scaled (%d WGs): %8.2f us  %6.1f TFLOP/s\n", njobs * splits, t,
                       fl / t / 1e6);
           CK(hipMemcpy(dwj, wj.data(), wj.size() * sizeof(WgradJob), hipMemcpyHostToDevice));
@@ -303,7 +304,7 @@ int main(int argc, char** argv) {
               if (v != 0) { J.lddz = 0; J.ldx = 0; }
             }
             CK(hipMemcpy(dwj, dj.data(), dj.size() * sizeof(WgradJob), hipMemcpyHostToDevice));
-            t = time_us([&] { CK(launch_wgrad(dwj, dwpre, njobs, njobs * splits, dwpre + njobs, red, wslab, nullptr, true, true)); }, 20);
+            t = time_us([&] { wide(3, false); }, 20);
             std::printf("wgrad MoE  bf16x6 wide, %-18s   %8.2f us  %6.1f TFLOP/s\n", what[v], t, fl / t / 1e6);
           }
         }
@@ -318,11 +319,11 @@ int main(int argc, char** argv) {
       WgradJob* dng = nullptr;
       CK(hipMalloc(&dng, ng.size() * sizeof(WgradJob)));
       CK(hipMemcpy(dng, ng.data(), ng.size() * sizeof(WgradJob), hipMemcpyHostToDevice));
-      t = time_us([&] { CK(launch_wgrad(dng, dpre, njobs, wg, dpre + njobs, red, slab, nullptr)); }, 20);
+      t = time_us([&] { tile128(dng, nullptr); }, 20);
       std::printf("wgrad MoE  no-GELU operand:            %8.2f us  %6.1f TFLOP/s\n", t, fl / t / 1e6);
       for (auto& J : ng) { J.x_gelu = 1; J.lddz = 0; J.ldx = 0; }   // every point reads row 0: no HBM traffic
       CK(hipMemcpy(dng, ng.data(), ng.size() * sizeof(WgradJob), hipMemcpyHostToDevice));
-      t = time_us([&] { CK(launch_wgrad(dng, dpre, njobs, wg, dpre + njobs, red, slab, nullptr)); }, 20);
+      t = time_us([&] { tile128(dng, nullptr); }, 20);
       std::printf("wgrad MoE  L2-resident rows (diag):    %8.2f us  %6.1f TFLOP/s\n", t, fl / t / 1e6);
     }
 
@@ -368,7 +369,7 @@ int main(int argc, char** argv) {
         std::printf("kv_bwd     P=%d H=%d dh=%d: %8.2f us  %6.0f GB/s\n", P, H, dh, t, 4.0 * P * D * 4 / t / 1e3);
       }
       // contention: wgrad launches queued on s2 while apply_bwd is timed on the null stream
-      for (int i = 0; i < 30; ++i) CK(launch_wgrad(djobs, dpre, njobs, wg, dpre + njobs, red, slab, s2));
+      for (int i = 0; i < 30; ++i) tile128(djobs, s2);
       t = time_us([&] { CK(launch_attn_apply_bwd(ap, nullptr)); }, 20);
       std::printf("apply_bwd  nsrc=%d under concurrent wgrad: %8.2f us\n", nsrc, t);
       CK(hipStreamSynchronize(s2));

@@ -263,23 +263,21 @@ __global__ void __launch_bounds__(256) state_reduce_kernel(const WgradJob* __res
   if (valid && lane8 == 0) jobs[j].dW[e] = s;
 }
 
-hipError_t launch_state(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
-                        const int* red_prefix_dev, int total_red, float* slab, int d, int dh, int pts, int nw,
-                        bool mfma, hipStream_t s) {
-  if (njobs <= 0 || total_wgs <= 0) return hipSuccess;
+hipError_t launch_state(const WgradTables& t, float* slab, int d, int dh, int pts, int nw, bool mfma, hipStream_t s) {
+  if (t.njobs <= 0 || t.total_wgs <= 0) return hipSuccess;
   if (mfma) {
     if (!state_mfma_ok(d, dh)) return hipErrorInvalidValue;
     const int hpw = d / dh / 4;
-    const dim3 grid(total_wgs), block(256);
+    const dim3 grid(t.total_wgs), block(256);
 #define GNOT_STATE_MFMA(DHV, HPWV)                                                                             \
     if (dh == DHV && hpw == HPWV) {                                                                            \
-      hipLaunchKernelGGL((state_mfma_kernel<DHV, HPWV>), grid, block, 0, s, jobs_dev, wg_prefix_dev, njobs, slab, pts); \
+      hipLaunchKernelGGL((state_mfma_kernel<DHV, HPWV>), grid, block, 0, s, t.jobs, t.wg_prefix, t.njobs, slab, pts); \
     } else
     GNOT_STATE_MFMA(16, 1) GNOT_STATE_MFMA(16, 2) GNOT_STATE_MFMA(16, 4) GNOT_STATE_MFMA(32, 1) GNOT_STATE_MFMA(32, 2)
     GNOT_STATE_MFMA(32, 4) GNOT_STATE_MFMA(64, 1) GNOT_STATE_MFMA(64, 2) return hipErrorInvalidValue;
 #undef GNOT_STATE_MFMA
-    hipLaunchKernelGGL(state_reduce_kernel, dim3((total_red * 8 + 255) / 256), dim3(256), 0, s, jobs_dev, red_prefix_dev,
-                       njobs, total_red, (const float*)slab);
+    hipLaunchKernelGGL(state_reduce_kernel, dim3((t.total_red * 8 + 255) / 256), dim3(256), 0, s, t.jobs, t.red_prefix,
+                       t.njobs, t.total_red, (const float*)slab);
     return hipGetLastError();
   }
   // dynamic LDS, what the workgroup stages: A and B rows (pts * d floats each, rounded up to whole
@@ -292,10 +290,10 @@ hipError_t launch_state(const WgradJob* jobs_dev, const int* wg_prefix_dev, int 
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)((2 * 8192 + 64 * 64) * sizeof(float)));
     attr = true;
   }
-  hipLaunchKernelGGL(state_partial_kernel, dim3(total_wgs), dim3(kStateThreads), lds, s, jobs_dev, wg_prefix_dev,
-                     njobs, slab, pts);
-  hipLaunchKernelGGL(state_reduce_kernel, dim3((total_red * 8 + 255) / 256), dim3(256), 0, s, jobs_dev, red_prefix_dev,
-                     njobs, total_red, (const float*)slab);
+  hipLaunchKernelGGL(state_partial_kernel, dim3(t.total_wgs), dim3(kStateThreads), lds, s, t.jobs, t.wg_prefix,
+                     t.njobs, slab, pts);
+  hipLaunchKernelGGL(state_reduce_kernel, dim3((t.total_red * 8 + 255) / 256), dim3(256), 0, s, t.jobs, t.red_prefix,
+                     t.njobs, t.total_red, (const float*)slab);
   return hipGetLastError();
 }
 

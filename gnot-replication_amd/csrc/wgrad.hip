@@ -1,19 +1,21 @@
-// Point-reduction GEMM:  C = sum_p A[p]^T B[p]  (+ column sums of A)  over a point range.
+// Weight gradients of every Linear:  dW = sum_p dZ[p]^T X[p],  db = sum_p dZ[p]  over a job's points (the
+// autograd of nn.Linear, reference model.py:9-14 / 43-51 behind main.py:102).  X may be a saved PRE-activation,
+// GELU'd on load (the input of hidden Linear l is gelu(h_{l-1}), model.py:10-13).
 //
-// Two users, one kernel:
-//  * weight gradients of every Linear: dW = sum_p dZ[p]^T X[p], db = sum_p dZ[p] (the autograd of
-//    nn.Linear, reference model.py:9-14 / 43-51 behind main.py:102).  X may be a saved
-//    PRE-activation, GELU'd on load (the input of hidden Linear l is gelu(h_{l-1}), model.py:10-13).
-//  * the linear-attention state of one sample: S = sum_m k_m^T v_m, z = sum_m k_m (model.py:77,79)
-//    and in the backward dS = sum_n q_n^T du_n, dz = sum_n dden_n q_n.  The GEMM computes the full
-//    128x128 tile and the reduce pass keeps only the per-head dh x dh diagonal blocks.
+// Four kernels, all on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (WgradKernel, gnot_kernels.h):
+//   pgemm_x6_kernel        128 x 128 tile per workgroup, any out / in (fp32 rows split into bf16 pieces)
+//   pgemm_x6w_kernel<256>  a job's whole gradient (out, in <= 256) per workgroup, d = 256
+//   pgemm_x6w_kernel<128>  the same design at out, in <= 128, d <= 128
+//   pgemm_b16_kernel       bf16-storage rows [P, 256] (the bf16 mode's soft-MoE chains)
+// NP = 3 splits every fp32 value exactly into three bf16 pieces and takes the six order <= 2 piece products
+// (bf16x6: fp32-level accuracy); NP = 1 is the bf16 mode's one RNE piece.
 //
-// Layout: one workgroup (4 waves) owns a 128x128 output tile of one job and one chunk of points.
-// Per stage kStage = 32 points of A and B rows (2 x 16 KiB, coalesced 16-B loads, GELU applied while
-// staging) go to LDS; the NEXT stage's rows are already in flight in registers while the current one
-// is consumed.  Each wave computes a 64x64 quadrant with v_mfma_f32_32x32x2_f32 (2 points per MFMA
-// k-step, 4 MFMAs per pair of A/B fragment loads).  Partial tiles go to a slab; the reduce pass sums
-// the splits in a fixed order (deterministic, no atomics).
+// One slab layout: a job's points are cut into `splits` ranges (split-K); each range's partial gradient goes to
+// slab[slab_off + (split * ntile + tile) * 128 * 129], tile = to * tiles_i + ti a 128 x 128 tile of dW stored
+// with a row pitch of 129 -- column 128 of the ti = 0 tiles holds the partial db.  One reduce pass
+// (pgemm_reduce_kernel) sums the splits in a fixed order: deterministic, no atomics.
+//
+// The linear-attention states, once the same GEMM with only the per-head diagonal blocks kept, are state.hip's.
 #include <cstdlib>
 #include <type_traits>
 
@@ -26,8 +28,6 @@ namespace gnot {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTile = 128;       // output tile edge
-constexpr int kStage = 32;       // points per LDS stage
-constexpr int kLdsRow = kTile;   // floats per staged row
 
 GNOT_DEV int find_job(const int* __restrict__ prefix, int njobs, int idx) {
   int lo = 0, hi = njobs - 1;
@@ -38,150 +38,14 @@ GNOT_DEV int find_job(const int* __restrict__ prefix, int njobs, int idx) {
   return lo;
 }
 
-// Staging geometry: thread t owns column group c4 = t & 31 (columns 4*c4 .. 4*c4+3 of the tile) and
-// rows r0 + 8k (r0 = t >> 5, k < kStage / 8) of each stage, for both A and B (64 points measured no faster).
-struct StageRegs {
-  float4 a[kStage / 8], b[kStage / 8];
-};
-
-GNOT_DEV float4 load4(const float* __restrict__ base, long p, long ld, int c, int ncols, bool pv) {
-  if (!pv) return make_float4(0.f, 0.f, 0.f, 0.f);
-  if (c + 3 < ncols && (ld & 3) == 0) return *reinterpret_cast<const float4*>(base + p * ld + c);
-  float t[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) t[r] = (c + r < ncols) ? base[p * ld + c + r] : 0.f;
-  return make_float4(t[0], t[1], t[2], t[3]);
-}
-
-GNOT_DEV void stage_load(StageRegs& R, const WgradJob& J, long pbase, long pend, int co, int ci, int r0) {
-#pragma unroll
-  for (int k = 0; k < kStage / 8; ++k) {
-    const long p = pbase + r0 + 8 * k;
-    const bool pv = p < pend;
-    R.a[k] = load4(J.dz, p, J.lddz, co, J.out, pv);
-    R.b[k] = load4(J.x, p, J.ldx, ci, J.in, pv);
-  }
-}
-
-__global__ void __launch_bounds__(256) pgemm_kernel(const WgradJob* __restrict__ jobs, const int* __restrict__ prefix,
-                                                    int njobs, float* __restrict__ slab) {
-  __shared__ __attribute__((aligned(16))) float smem[2 * kStage * kLdsRow];
-  float* As = smem;
-  float* Bs = smem + kStage * kLdsRow;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int j = find_job(prefix, njobs, blockIdx.x);
-  const WgradJob J = jobs[j];
-  int t = blockIdx.x - prefix[j];
-  const int split = t % J.splits;
-  t /= J.splits;
-  int to, ti;
-  if (J.diag_only) { to = t; ti = t; } else { ti = t % J.tiles_i; to = t / J.tiles_i; }
-  const int chunk = ((J.P + J.splits - 1) / J.splits + kStage - 1) / kStage * kStage;
-  const long pb = (long)split * chunk;
-  const long pe = min((long)J.P, pb + chunk);
-  const int c0o = to * kTile, c0i = ti * kTile;
-  const int wo = wave >> 1, wi = wave & 1;      // 64x64 quadrant of this wave
-  const int r32 = lane & 31, h = lane >> 5;
-  const int c4 = tid & 31, r0 = tid >> 5;       // staging role
-  const int co = c0o + 4 * c4, ci = c0i + 4 * c4;
-  const bool want_db = (J.db != nullptr) && (J.diag_only || ti == 0);
-  const bool use_w = J.w != nullptr;
-  const bool gel = J.x_gelu != 0;
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = f32x16{};
-  float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);   // column sums of this thread's A columns
-
-  StageRegs R;
-  if (pb < pe) stage_load(R, J, pb, pe, co, ci, r0);
-  for (long p0 = pb; p0 < pe; p0 += kStage) {
-    __syncthreads();                          // previous stage fully consumed
-#pragma unroll
-    for (int k = 0; k < kStage / 8; ++k) {
-      const int row = r0 + 8 * k;
-      float4 vb = R.b[k];
-      if (gel) { vb.x = gelu(vb.x); vb.y = gelu(vb.y); vb.z = gelu(vb.z); vb.w = gelu(vb.w); }
-      reinterpret_cast<float4*>(As)[row * 32 + c4] = R.a[k];
-      reinterpret_cast<float4*>(Bs)[row * 32 + c4] = vb;
-      if (want_db) {
-        const long p = p0 + row;
-        const float wgt = (use_w && p < pe && co < J.out) ? J.w[p * J.ldw + co / J.wdh] : 1.f;
-        dbacc.x = fmaf(wgt, R.a[k].x, dbacc.x);
-        dbacc.y = fmaf(wgt, R.a[k].y, dbacc.y);
-        dbacc.z = fmaf(wgt, R.a[k].z, dbacc.z);
-        dbacc.w = fmaf(wgt, R.a[k].w, dbacc.w);
-      }
-    }
-    __syncthreads();
-    if (p0 + kStage < pe) stage_load(R, J, p0 + kStage, pe, co, ci, r0);   // in flight during MFMAs
-    // 16 k-steps (2 points each) in four batches of 4: fragment reads first, then 16 MFMAs
-#pragma unroll
-    for (int half = 0; half < kStage / 8; ++half) {
-      float a0[4], a1[4], b0[4], b1[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int row = 2 * (4 * half + s) + h;
-        const float* ar = As + row * kLdsRow + wo * 64 + r32;
-        const float* br = Bs + row * kLdsRow + wi * 64 + r32;
-        a0[s] = ar[0]; a1[s] = ar[32];
-        b0[s] = br[0]; b1[s] = br[32];
-      }
-      __builtin_amdgcn_sched_barrier(0);   // keep the 8 LDS reads batched ahead of the 16 MFMAs
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b0[s], acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b1[s], acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b0[s], acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b1[s], acc[1][1], 0, 0, 0);
-      }
-    }
-  }
-
-  // partial tile -> slab [split][tile 128 x (128 + 1)]
-  const int ntile = J.diag_only ? J.tiles_o : J.tiles_o * J.tiles_i;
-  const int tile = J.diag_only ? to : to * J.tiles_i + ti;
-  float* S = slab + J.slab_off + ((long)split * ntile + tile) * (kTile * (kTile + 1));
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wo * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int col = wi * 64 + b * 32 + r32;
-        S[row * (kTile + 1) + col] = acc[a][b][r];
-      }
-  if (want_db) {
-    // sum the 8 row-owners of every column group through LDS (reuses the A stage buffer)
-    __syncthreads();
-    reinterpret_cast<float4*>(As)[r0 * 32 + c4] = dbacc;
-    __syncthreads();
-    if (r0 == 0) {
-      float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float4 v = reinterpret_cast<const float4*>(As)[k * 32 + c4];
-        tot.x += v.x; tot.y += v.y; tot.z += v.z; tot.w += v.w;
-      }
-      S[(4 * c4 + 0) * (kTile + 1) + kTile] = tot.x;
-      S[(4 * c4 + 1) * (kTile + 1) + kTile] = tot.y;
-      S[(4 * c4 + 2) * (kTile + 1) + kTile] = tot.z;
-      S[(4 * c4 + 3) * (kTile + 1) + kTile] = tot.w;
-    }
-  }
-}
-
-// ---------------------------------------------------------------- bf16x6 variant (plain weight-gradient jobs)
-// Same tiling, split-K and slab as pgemm_kernel, on v_mfma_f32_32x32x16_bf16: every staged fp32 value
-// is split exactly into three bf16 pieces (split8_x6) and each 32x32x16 block product is the six
-// order <= 2 piece products, accumulated in fp32 (the dropped terms are ~2^-24 relative: fp32-level,
-// like the forward chains; one accumulator per block keeps two workgroups per CU within the register
-// file): 6 x 32 = 192 matrix-pipe cycles per 32x32x16 block
-// instead of 8 x 64 = 512 on v_mfma_f32_32x32x2_f32.
+// ---------------------------------------------------------------- 128-tile kernel (any out / in)
+// One workgroup (4 waves, one 64 x 64 quadrant each) owns a 128 x 128 output tile of one job and one split of
+// its points.  Every staged fp32 value is split exactly into three bf16 pieces (split8_x6) and each 32x32x16
+// block product is the six order <= 2 piece products, accumulated in fp32 (the dropped terms are ~2^-24
+// relative: fp32-level, like the forward chains; one accumulator per block keeps two workgroups per CU within
+// the register file): 6 x 32 = 192 matrix-pipe cycles per 32x32x16 block (the exact fp32 MFMA this kernel
+// replaced, v_mfma_f32_32x32x2_f32, takes 8 x 64 = 512).  The next stage's rows are in flight in registers while
+// the current one is multiplied.
 // Staging: thread (pair fp = t & 63, octet o = t >> 6 = its wave) loads features 2fp, 2fp+1 of the
 // stage's points 8o .. 8o+7 (one float2 per point: a wave reads whole 512-byte rows), so 8 consecutive
 // points of one feature are register-local and go to LDS as one 16-byte vector per piece.  The LDS
@@ -332,7 +196,7 @@ __global__ void __launch_bounds__(256) pgemm_x6_kernel(const WgradJob* __restric
     }
   }
 
-  // partial tile -> slab [split][tile 128 x (128 + 1)] (same layout as pgemm_kernel)
+  // partial tile -> slab [split][tile 128 x (128 + 1)]
   const int ntile = J.tiles_o * J.tiles_i;
   const int tile = to * J.tiles_i + ti;
   float* S = slab + J.slab_off + ((long)split * ntile + tile) * (kTile * (kTile + 1));
@@ -386,7 +250,7 @@ __global__ void __launch_bounds__(256) pgemm_x6_kernel(const WgradJob* __restric
 //   MFMA:    wave (wr, wc) computes rows [128 wr, +128) x cols [64 wc, +64): 4 x 2 blocks, six order <= 2
 //            piece products each (smallest first), one accumulator per block.
 // Double-buffered fragment images: stage s+1 is split into the other buffer while stage s is multiplied.
-// Partials go to the same slab layout as pgemm_kernel (128-tiles).
+// Partials go to the same slab layout as the 128-tile kernel's.
 // TW = 128 (round 5): the same kernel at d <= 128 (configs[1]) with a 128 x 128 output per workgroup and 4
 // waves (one 64 x 64 quadrant each, 2 x 2 blocks), in place of the 128-tile kernel above, whose staging and
 // MFMAs run as separate phases on one wave per SIMD.
@@ -712,7 +576,7 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 
-  // partials -> slab [split][128-tile][128 x (128 + 1)] (the pgemm_kernel layout)
+  // partials -> slab [split][128-tile][128 x (128 + 1)] (the file header's layout)
   // (SCK: the job's fields are read again here -- holding them in SGPRs through the stage loops above, next
   // to the scaled form's resource, costs the loops registers they do not have)
   const WgradJob* jp = &J;
@@ -881,7 +745,7 @@ __global__ void __launch_bounds__(kWThreads) pgemm_b16_kernel(const WgradJob* __
     }
   }
 
-  // partials -> slab [split][128-tile][128 x (128 + 1)] (the pgemm_kernel layout)
+  // partials -> slab [split][128-tile][128 x (128 + 1)] (the file header's layout)
   const int ntile = J.tiles_o * J.tiles_i;
   float* S0 = slab + J.slab_off + (long)split * ntile * (kTile * (kTile + 1));
 #pragma unroll
@@ -904,11 +768,9 @@ __global__ void __launch_bounds__(kWThreads) pgemm_b16_kernel(const WgradJob* __
   }
 }
 
-// sum the split partials; normal jobs write dW[out, in] (+ db[out]); state jobs (state_dh > 0) write
-// the per-head diagonal blocks into [H][dh*dh + dh] (S row-major, then z).
-// accumulate (a launch argument, gnot_backward_ex GNOT_BWD_ACCUMULATE): parameter-gradient jobs add the
-// same fixed-order sum s onto the destination (one read, one add, no atomics: each element has one writer);
-// state jobs overwrite in every mode
+// sum the split partials into dW[out, in] and db[out] (the partial db: column 128 of the ti = 0 tiles).
+// accumulate (a launch argument, gnot_backward_ex GNOT_BWD_ACCUMULATE): add the same fixed-order sum s onto the
+// destination (one read, one add, no atomics: each element has one writer) instead of overwriting it
 __global__ void __launch_bounds__(256) pgemm_reduce_kernel(const WgradJob* __restrict__ jobs,
                                                            const int* __restrict__ prefix, int njobs, int total,
                                                            const float* __restrict__ slab, int accumulate) {
@@ -917,90 +779,82 @@ __global__ void __launch_bounds__(256) pgemm_reduce_kernel(const WgradJob* __res
   const int j = find_job(prefix, njobs, idx);
   const WgradJob& J = jobs[j];
   int e = idx - prefix[j];
-  const int ntile = J.diag_only ? J.tiles_o : J.tiles_o * J.tiles_i;
+  const int ntile = J.tiles_o * J.tiles_i;
   const int tile = e / (kTile * (kTile + 1));
   e -= tile * (kTile * (kTile + 1));
   const int rl = e / (kTile + 1), cl = e % (kTile + 1);
-  const int to = J.diag_only ? tile : tile / J.tiles_i;
-  const int ti = J.diag_only ? tile : tile % J.tiles_i;
+  const int to = tile / J.tiles_i, ti = tile % J.tiles_i;
   const int row = to * kTile + rl;
   const bool isdb = cl == kTile;
   const int col = ti * kTile + cl;
   if (row >= J.out) return;
   if (isdb) {
-    if (J.db == nullptr || (!J.diag_only && ti != 0)) return;
+    if (J.db == nullptr || ti != 0) return;
   } else if (col >= J.in) {
     return;
   }
-  if (J.state_dh > 0 && !isdb && (row / J.state_dh) != (col / J.state_dh)) return;
   const float* S = slab + J.slab_off + (long)tile * (kTile * (kTile + 1)) + rl * (kTile + 1) + cl;
   const long sstride = (long)ntile * (kTile * (kTile + 1));
   // 8 independent partial sums keep 8 slab loads in flight (the loop is latency-bound otherwise);
   // the combination order is fixed, so the result is still deterministic
   float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int k = 0;
-  for (; k + 8 <= J.splits; k += 8)
+  for (; k + 8 <= J.splits; k += 8) {
+    // split k's element, opaque to the compiler: it then steps ONE pointer through the splits.  Left to itself
+    // it keeps eight (63 registers against 43), and a backward step beside this kernel measured 0.3-0.6 %
+    // slower at configs[1] (profiles/LOG.md)
+    gfloat_ptr Sk = (gfloat_ptr)S + (long)k * sstride;
+    asm volatile("" : "+v"(Sk));
 #pragma unroll
-    for (int u = 0; u < 8; ++u) part[u] += S[(long)(k + u) * sstride];
+    for (int u = 0; u < 8; ++u) part[u] += Sk[(long)u * sstride];
+  }
   for (; k < J.splits; ++k) part[0] += S[(long)k * sstride];
   const float s = ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
-  float* dst;
-  if (J.state_dh > 0) {
-    const int dh = J.state_dh, hh = row / dh, i = row % dh;
-    float* base = J.dW + (long)hh * (dh * dh + dh);
-    dst = isdb ? base + dh * dh + i : base + i * dh + (col % dh);
-  } else {
-    dst = isdb ? (J.db + row) : (J.dW + (long)row * J.in + col);
-  }
-  *dst = (accumulate && J.state_dh == 0) ? (*dst + s) : s;
+  float* dst = isdb ? (J.db + row) : (J.dW + (long)row * J.in + col);
+  *dst = accumulate ? (*dst + s) : s;
 }
 
-hipError_t launch_wgrad_b16(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
-                            const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, const int4* segs,
-                            const int* seg_start, bool accumulate) {
-  if (njobs <= 0) return hipSuccess;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pgemm_b16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kBLds);
-    attr = true;
+// the kernel of `kind` over the group's splits, then the reduce
+hipError_t launch_wgrad(WgradKernel kind, const WgradTables& t, float* slab, int np, bool scaled, bool accumulate,
+                        hipStream_t s) {
+  if (t.njobs <= 0) return hipSuccess;
+  if (np != 1 && np != 3) return hipErrorInvalidValue;
+  if (scaled && !(kind == WgradKernel::Wide256 && np == 3)) return hipErrorInvalidValue;
+  const bool ranged = kind == WgradKernel::Wide256 || kind == WgradKernel::B16Rows;
+  if (t.segs != nullptr && !ranged) return hipErrorInvalidValue;
+  const dim3 grid(t.total_wgs);
+  // the two one-workgroup-per-split designs take more dynamic LDS than the default limit
+#define GNOT_WIDE(KERNEL, THREADS, LDS, ...)                                                                       \
+  do {                                                                                                             \
+    static bool attr = false;                                                                                      \
+    if (!attr) {                                                                                                   \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                (int)(LDS));                                                                       \
+      attr = true;                                                                                                 \
+    }                                                                                                              \
+    hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), LDS, s, t.jobs, t.wg_prefix, t.njobs, slab, __VA_ARGS__);      \
+  } while (0)
+  switch (kind) {
+    case WgradKernel::Tile128:
+      if (np == 1) hipLaunchKernelGGL(pgemm_x6_kernel<1>, grid, dim3(256), 0, s, t.jobs, t.wg_prefix, t.njobs, slab);
+      else hipLaunchKernelGGL(pgemm_x6_kernel<3>, grid, dim3(256), 0, s, t.jobs, t.wg_prefix, t.njobs, slab);
+      break;
+    case WgradKernel::Wide256:
+      if (scaled) GNOT_WIDE((pgemm_x6w_kernel<3, 256, true>), w_threads(256), w_lds_bytes(3, 256), t.segs, t.seg_start);
+      else if (np == 1) GNOT_WIDE((pgemm_x6w_kernel<1, 256, false>), w_threads(256), w_lds_bytes(1, 256), t.segs, t.seg_start);
+      else GNOT_WIDE((pgemm_x6w_kernel<3, 256, false>), w_threads(256), w_lds_bytes(3, 256), t.segs, t.seg_start);
+      break;
+    case WgradKernel::Wide128:
+      if (np == 1) GNOT_WIDE((pgemm_x6w_kernel<1, 128, false>), w_threads(128), w_lds_bytes(1, 128), t.segs, t.seg_start);
+      else GNOT_WIDE((pgemm_x6w_kernel<3, 128, false>), w_threads(128), w_lds_bytes(3, 128), t.segs, t.seg_start);
+      break;
+    case WgradKernel::B16Rows:
+      GNOT_WIDE(pgemm_b16_kernel, kWThreads, kBLds, t.segs, t.seg_start);
+      break;
   }
-  hipLaunchKernelGGL(pgemm_b16_kernel, dim3(total_wgs), dim3(kWThreads), kBLds, s, jobs_dev, wg_prefix_dev, njobs, slab,
-                     segs, seg_start);
-  hipLaunchKernelGGL(pgemm_reduce_kernel, dim3((total_red + 255) / 256), dim3(256), 0, s, jobs_dev, red_prefix_dev,
-                     njobs, total_red, (const float*)slab, accumulate ? 1 : 0);
-  return hipGetLastError();
-}
-
-hipError_t launch_wgrad(const WgradJob* jobs_dev, const int* wg_prefix_dev, int njobs, int total_wgs,
-                        const int* red_prefix_dev, int total_red, float* slab, hipStream_t s, bool x6, bool wide,
-                        int np, int tw, const int4* segs, const int* seg_start, bool accumulate, bool scaled) {
-  if (njobs <= 0) return hipSuccess;
-  if (scaled && !(wide && np == 3 && tw == 256)) return hipErrorInvalidValue;
-  if (wide) {
-    const size_t lds = w_lds_bytes(np, tw);
-#define GNOT_X6W(NP_, TW_, SC_)                                                                                \
-  if (np == NP_ && tw == TW_ && scaled == SC_) {                                                               \
-    static bool attr = false;                                                                                  \
-    if (!attr) {                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pgemm_x6w_kernel<NP_, TW_, SC_>),                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-      attr = true;                                                                                             \
-    }                                                                                                          \
-    hipLaunchKernelGGL((pgemm_x6w_kernel<NP_, TW_, SC_>), dim3(total_wgs), dim3(w_threads(TW_)), lds, s,       \
-                       jobs_dev, wg_prefix_dev, njobs, slab, segs, seg_start);                                 \
-  }
-    GNOT_X6W(3, 256, false) GNOT_X6W(3, 256, true) GNOT_X6W(1, 256, false) GNOT_X6W(3, 128, false)
-    GNOT_X6W(1, 128, false)
-#undef GNOT_X6W
-  } else if (x6) {
-    if (np == 1) hipLaunchKernelGGL(pgemm_x6_kernel<1>, dim3(total_wgs), dim3(256), 0, s, jobs_dev, wg_prefix_dev, njobs, slab);
-    else hipLaunchKernelGGL(pgemm_x6_kernel<3>, dim3(total_wgs), dim3(256), 0, s, jobs_dev, wg_prefix_dev, njobs, slab);
-  }
-  else
-    hipLaunchKernelGGL(pgemm_kernel, dim3(total_wgs), dim3(256), 0, s, jobs_dev, wg_prefix_dev, njobs, slab);
-  hipLaunchKernelGGL(pgemm_reduce_kernel, dim3((total_red + 255) / 256), dim3(256), 0, s, jobs_dev,
-                     red_prefix_dev, njobs, total_red, (const float*)slab, accumulate ? 1 : 0);
+#undef GNOT_WIDE
+  hipLaunchKernelGGL(pgemm_reduce_kernel, dim3((t.total_red + 255) / 256), dim3(256), 0, s, t.jobs, t.red_prefix,
+                     t.njobs, t.total_red, (const float*)slab, accumulate ? 1 : 0);
   return hipGetLastError();
 }
 
