@@ -602,66 +602,41 @@ static unsigned seg_split(int H) {
   return (unsigned)((64 * H * HeadSplit<DH>::G + 255) / 256);
 }
 
-hipError_t launch_attn_apply_fwd(const AttnApplyArgs& a, hipStream_t s) {
-  if (a.nchunks <= 0) return hipSuccess;
-  const hipError_t m = launch_attn_apply_mfma(a, false, s);   // attn_mfma.hip where it applies
-  if (m != hipErrorNotSupported) return m;
-  if (a.dh > 64) {
-    if (a.dh % 4 != 0) return hipErrorInvalidValue;
-    GNOT_WIDE_SWITCH(a.dh, hipLaunchKernelGGL(attn_apply_fwd_wide_kernel<NB>, dim3(a.nchunks, wide_split(a.H)),
-                                              dim3(256), 0, s, a));
-    return hipGetLastError();
+// The VALU launch of a pass, written once: NARROW<DH> / WIDE<NB> are the pass's two kernel templates, the grid
+// (NX chunks, the workgroups of a segment, NZ jobs).  Returns from the launcher; a form that is not the VALU
+// form of the head width is hipErrorInvalidValue
+#define GNOT_LAUNCH_VALU(FORM, DHV, HV, NARROW, WIDE, NX, NZ, ARG)                                                  \
+  {                                                                                                                 \
+    if ((FORM) == AttnKernel::Wide && (DHV) > 64 && (DHV) % 4 == 0) {                                               \
+      GNOT_WIDE_SWITCH(DHV, hipLaunchKernelGGL(WIDE<NB>, dim3(NX, wide_split(HV), NZ), dim3(256), 0, s, ARG));      \
+    } else if ((FORM) == AttnKernel::Narrow) {                                                                      \
+      GNOT_DH_SWITCH(DHV, hipLaunchKernelGGL(NARROW<DH>, dim3(NX, seg_split<DH>(HV), NZ), dim3(256), 0, s, ARG));   \
+    } else {                                                                                                        \
+      return hipErrorInvalidValue;                                                                                  \
+    }                                                                                                               \
+    return hipGetLastError();                                                                                       \
   }
-  GNOT_DH_SWITCH(a.dh, hipLaunchKernelGGL(attn_apply_fwd_kernel<DH>, dim3(a.nchunks, seg_split<DH>(a.H)), dim3(256),
-                                          0, s, a));
-  return hipGetLastError();
+
+// the AttnKernel::Mfma branches (attn_mfma.hip)
+hipError_t launch_attn_apply_mfma(const AttnApplyArgs& a, bool bwd, hipStream_t s);
+hipError_t launch_attn_kv_bwd_mfma(const AttnKVBwdArgs* a, const AttnKVBwdArgs* jobs_dev, int njobs, int maxchunks,
+                                   int H, int dh, hipStream_t s);
+
+hipError_t launch_attn_apply(AttnKernel form, const AttnApplyArgs& a, bool bwd, hipStream_t s) {
+  if (a.nchunks <= 0) return hipSuccess;
+  if (form == AttnKernel::Mfma) return launch_attn_apply_mfma(a, bwd, s);
+  if (!bwd) GNOT_LAUNCH_VALU(form, a.dh, a.H, attn_apply_fwd_kernel, attn_apply_fwd_wide_kernel, a.nchunks, 1, a)
+  GNOT_LAUNCH_VALU(form, a.dh, a.H, attn_apply_bwd_kernel, attn_apply_bwd_wide_kernel, a.nchunks, 1, a)
 }
 
-hipError_t launch_attn_apply_bwd(const AttnApplyArgs& a, hipStream_t s) {
-  if (a.nchunks <= 0) return hipSuccess;
-  const hipError_t m = launch_attn_apply_mfma(a, true, s);
-  if (m != hipErrorNotSupported) return m;
-  if (a.dh > 64) {
-    if (a.dh % 4 != 0) return hipErrorInvalidValue;
-    GNOT_WIDE_SWITCH(a.dh, hipLaunchKernelGGL(attn_apply_bwd_wide_kernel<NB>, dim3(a.nchunks, wide_split(a.H)),
-                                              dim3(256), 0, s, a));
-    return hipGetLastError();
-  }
-  GNOT_DH_SWITCH(a.dh, hipLaunchKernelGGL(attn_apply_bwd_kernel<DH>, dim3(a.nchunks, seg_split<DH>(a.H)), dim3(256),
-                                          0, s, a));
-  return hipGetLastError();
-}
-
-hipError_t launch_attn_kv_bwd(const AttnKVBwdArgs& a, hipStream_t s) {
-  if (a.nchunks <= 0) return hipSuccess;
-  const hipError_t m = launch_attn_kv_bwd_mfma(&a, nullptr, 1, a.nchunks, a.H, a.dh, s);
-  if (m != hipErrorNotSupported) return m;
-  if (a.dh > 64) {
-    if (a.dh % 4 != 0) return hipErrorInvalidValue;
-    GNOT_WIDE_SWITCH(a.dh, hipLaunchKernelGGL(attn_kv_bwd_wide_kernel<NB>, dim3(a.nchunks, wide_split(a.H)),
-                                              dim3(256), 0, s, a));
-    return hipGetLastError();
-  }
-  GNOT_DH_SWITCH(a.dh, hipLaunchKernelGGL(attn_kv_bwd_kernel<DH>, dim3(a.nchunks, seg_split<DH>(a.H)), dim3(256), 0,
-                                          s, a));
-  return hipGetLastError();
-}
-
-hipError_t launch_attn_kv_bwd_batch(const AttnKVBwdArgs* jobs_dev, int njobs, int maxchunks, int H, int dh,
-                                    hipStream_t s) {
-  if (njobs <= 0 || maxchunks <= 0) return hipSuccess;
-  // the batched jobs' pitches are 4-aligned by construction (rows of d floats)
-  const hipError_t m = launch_attn_kv_bwd_mfma(nullptr, jobs_dev, njobs, maxchunks, H, dh, s);
-  if (m != hipErrorNotSupported) return m;
-  if (dh > 64) {
-    if (dh % 4 != 0) return hipErrorInvalidValue;
-    GNOT_WIDE_SWITCH(dh, hipLaunchKernelGGL(attn_kv_bwd_wide_batch_kernel<NB>, dim3(maxchunks, wide_split(H), njobs),
-                                            dim3(256), 0, s, jobs_dev));
-    return hipGetLastError();
-  }
-  GNOT_DH_SWITCH(dh, hipLaunchKernelGGL(attn_kv_bwd_batch_kernel<DH>, dim3(maxchunks, seg_split<DH>(H), njobs),
-                                        dim3(256), 0, s, jobs_dev));
-  return hipGetLastError();
+hipError_t launch_attn_kv_bwd(AttnKernel form, const AttnKVBwdArgs* a, const AttnKVBwdArgs* jobs_dev, int njobs,
+                              int maxchunks, int H, int dh, hipStream_t s) {
+  if (a && (a->H != H || a->dh != dh)) return hipErrorInvalidValue;
+  if (a ? a->nchunks <= 0 : (njobs <= 0 || maxchunks <= 0)) return hipSuccess;
+  if (form == AttnKernel::Mfma) return launch_attn_kv_bwd_mfma(a, jobs_dev, njobs, maxchunks, H, dh, s);
+  if (a) GNOT_LAUNCH_VALU(form, dh, H, attn_kv_bwd_kernel, attn_kv_bwd_wide_kernel, a->nchunks, 1, *a)
+  GNOT_LAUNCH_VALU(form, dh, H, attn_kv_bwd_batch_kernel, attn_kv_bwd_wide_batch_kernel, maxchunks, njobs, jobs_dev)
 }
 
 }  // namespace gnot
+

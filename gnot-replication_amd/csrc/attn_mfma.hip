@@ -1,7 +1,7 @@
 // Attention apply passes on fp32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 sums) --
 // the Q . state contractions of reference LinearAttention.forward (model.py:78-80 / 99-101) and their
 // backward, for head widths dh = 16, 32, 64.  Same arguments and results as attn.hip's VALU kernels
-// (which stay for other head widths and for small meshes, GNOT_APPLY_MFMA_MIN).
+// (which stay for other head widths and for small meshes; attn_kernel below is the rule, the plan applies it).
 //
 // Point form (gnot_common.h): a wave owns 16 points; lane l holds, for every 16-feature tile T of a
 // head, features 16T + 4(l>>4) + r (r < 4) of point l & 15 -- which is both the B operand of the
@@ -13,8 +13,6 @@
 // one 64-point chunk per pass) walks `cpw` consecutive chunks and re-stages the images from the
 // L2-resident states only when the sample changes.  HBM traffic is the rows: q and res (forward),
 // q, dres, du, dq (backward).
-#include <cstdlib>
-
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
@@ -356,20 +354,26 @@ __global__ void __launch_bounds__(256) attn_kv_bwd_batch_mfma_kernel(const AttnK
 
 namespace {
 constexpr size_t kApplyLdsMax = 160 * 1024;
-// below this many 64-point chunks the MFMA passes run fewer than ~128 workgroups, each staging the
-// state images before its few chunks: the VALU kernels (attn.hip) are faster there (configs[1],
-// 10k points: apply bwd 23 vs 70 us per call; env GNOT_APPLY_MFMA_MIN overrides)
-static int mfma_min_chunks() {
-  const char* e = std::getenv("GNOT_APPLY_MFMA_MIN");    // read per launch: tests force either path
-  return e ? std::atoi(e) : 512;
+}  // namespace
+
+// The form of a pass (gnot_kernels.h).  The plan calls it once per batch geometry with its threshold; the
+// launchers below call it with a threshold of 0 to refuse an Mfma their arguments cannot run
+AttnKernel attn_kernel(AttnPass pass, int dh, int dhr, int H, int nsrc, long nchunks, bool aligned4, int min_chunks) {
+  const AttnKernel valu = dh > 64 ? AttnKernel::Wide : AttnKernel::Narrow;
+  const bool kv = pass == AttnPass::KVBwd, bwd = pass != AttnPass::ApplyFwd;
+  if (!kv && dhr != 0 && dhr != dh) return valu;   // padded heads: the VALU forms
+  if (nchunks < min_chunks || !aligned4 || nsrc < 1 || nsrc > 8) return valu;
+  size_t lds;
+  switch (dh) {
+    case 16: lds = apply_lds_bytes<16>(nsrc, H, bwd); break;
+    case 32: lds = apply_lds_bytes<32>(nsrc, H, bwd); break;
+    case 64: lds = apply_lds_bytes<64>(nsrc, H, bwd); break;
+    default: return valu;
+  }
+  return lds <= kApplyLdsMax ? AttnKernel::Mfma : valu;
 }
 
-template <int DH>
-bool mfma_ok(const AttnApplyArgs& a, bool bwd) {
-  return a.nchunks >= mfma_min_chunks() && a.nsrc >= 1 && a.nsrc <= 8 && (a.ldq & 3) == 0 &&
-         (!bwd || ((a.lddq & 3) == 0 && (a.lddu & 3) == 0)) && apply_lds_bytes<DH>(a.nsrc, a.H, bwd) <= kApplyLdsMax;
-}
-
+namespace {
 // the dynamic-LDS cap of a kernel, raised ONCE to the largest size any launch may ask for (it is a cap
 // only: occupancy follows each launch's own size), not per launch
 static void allow_max_lds(const void* f) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kApplyLdsMax); }
@@ -390,17 +394,18 @@ hipError_t launch_mfma(const AttnApplyArgs& a, hipStream_t s) {
 }
 }  // namespace
 
-// returns hipErrorNotSupported when the head width / LDS size has no MFMA variant (caller falls back)
+// The AttnKernel::Mfma branch of launch_attn_apply (attn.hip): hipErrorInvalidValue for arguments the MFMA
+// kernels cannot run
 hipError_t launch_attn_apply_mfma(const AttnApplyArgs& a, bool bwd, hipStream_t s) {
-  if (a.dhr != 0 && a.dhr != a.dh) return hipErrorNotSupported;   // padded heads: the VALU forms
-  if (a.nchunks <= 0) return hipSuccess;
+  const bool aligned4 = ((a.ldq | (bwd ? a.lddq | a.lddu : 0)) & 3) == 0;
+  if (attn_kernel(bwd ? AttnPass::ApplyBwd : AttnPass::ApplyFwd, a.dh, a.dhr, a.H, a.nsrc, a.nchunks, aligned4, 0) !=
+      AttnKernel::Mfma)
+    return hipErrorInvalidValue;
   switch (a.dh) {
-    case 16: if (mfma_ok<16>(a, bwd)) return bwd ? launch_mfma<16, true>(a, s) : launch_mfma<16, false>(a, s); break;
-    case 32: if (mfma_ok<32>(a, bwd)) return bwd ? launch_mfma<32, true>(a, s) : launch_mfma<32, false>(a, s); break;
-    case 64: if (mfma_ok<64>(a, bwd)) return bwd ? launch_mfma<64, true>(a, s) : launch_mfma<64, false>(a, s); break;
-    default: break;
+    case 16: return bwd ? launch_mfma<16, true>(a, s) : launch_mfma<16, false>(a, s);
+    case 32: return bwd ? launch_mfma<32, true>(a, s) : launch_mfma<32, false>(a, s);
+    default: return bwd ? launch_mfma<64, true>(a, s) : launch_mfma<64, false>(a, s);
   }
-  return hipErrorNotSupported;
 }
 
 namespace {
@@ -422,19 +427,18 @@ hipError_t launch_kv(const AttnKVBwdArgs* a, const AttnKVBwdArgs* jobs_dev, int 
 }
 }  // namespace
 
-// K/V backward on MFMA: `a` for one job, or (jobs_dev, njobs, maxchunks) for the batched form;
-// hipErrorNotSupported when the head width / LDS size has no MFMA variant
+// The AttnKernel::Mfma branch of launch_attn_kv_bwd (attn.hip): `a` for one job, or (jobs_dev, njobs, maxchunks)
+// for the batched form, whose pitches the host cannot see (the plan's are rows of d floats, 4-aligned by
+// construction); hipErrorInvalidValue for arguments the MFMA kernels cannot run
 hipError_t launch_attn_kv_bwd_mfma(const AttnKVBwdArgs* a, const AttnKVBwdArgs* jobs_dev, int njobs, int maxchunks,
                                    int H, int dh, hipStream_t s) {
-  if (a && ((a->ldkv & 3) || (a->lddkv & 3))) return hipErrorNotSupported;
-  if ((a ? a->nchunks : maxchunks * njobs) < mfma_min_chunks()) return hipErrorNotSupported;
+  const bool aligned4 = !a || ((a->ldkv | a->lddkv) & 3) == 0;
+  if (attn_kernel(AttnPass::KVBwd, dh, 0, H, 1, 0, aligned4, 0) != AttnKernel::Mfma) return hipErrorInvalidValue;
   switch (dh) {
-    case 16: if (apply_lds_bytes<16>(1, H, true) <= kApplyLdsMax) return launch_kv<16>(a, jobs_dev, njobs, maxchunks, H, s); break;
-    case 32: if (apply_lds_bytes<32>(1, H, true) <= kApplyLdsMax) return launch_kv<32>(a, jobs_dev, njobs, maxchunks, H, s); break;
-    case 64: if (apply_lds_bytes<64>(1, H, true) <= kApplyLdsMax) return launch_kv<64>(a, jobs_dev, njobs, maxchunks, H, s); break;
-    default: break;
+    case 16: return launch_kv<16>(a, jobs_dev, njobs, maxchunks, H, s);
+    case 32: return launch_kv<32>(a, jobs_dev, njobs, maxchunks, H, s);
+    default: return launch_kv<64>(a, jobs_dev, njobs, maxchunks, H, s);
   }
-  return hipErrorNotSupported;
 }
 
 }  // namespace gnot

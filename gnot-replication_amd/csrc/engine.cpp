@@ -200,13 +200,15 @@ struct gnot_plan {
   // against 236.8 / 236.7 forked -- the chains and GEMMs fill every CU, so overlapping them buys
   // nothing; configs[1] (10,000 points, d = 128) 4.12 / 4.12 serial against 3.64 / 3.72 forked and
   // configs[0] (16,384 points) 9.62 / 9.65 against 9.56 / 9.55 -- small launches leave CUs idle that
-  // the concurrent GEMMs fill.  So plans below kWgradSerialPoints fork, larger ones run serially; env
-  // GNOT_WGRAD_OVERLAP = 0 / 1 (read when the plan is created) forces either form (bitwise equal).
+  // the concurrent GEMMs fill.  So plans below kWgradSerialPoints fork, larger ones run serially;
+  // Tuning::wgrad_overlap = 0 / 1 (env GNOT_WGRAD_OVERLAP) forces either form (bitwise equal).
   static constexpr long kWgradSerialPoints = 65536;
   hipStream_t side = nullptr;
   hipStream_t side2 = nullptr;          // input-function branch, concurrent with the query branch
-  int wgrad_overlap_env = -1;
-  bool serial_wgrad() const { return wgrad_overlap_env >= 0 ? wgrad_overlap_env == 0 : P >= kWgradSerialPoints; }
+  // the switches of gnot_kernels.h Tuning, read from the environment once, in gnot_plan_create: every kernel
+  // form and size below that depends on one reads it here, so it cannot differ between set_batch, bind and launch
+  Tuning tune;
+  bool serial_wgrad() const { return tune.wgrad_overlap >= 0 ? tune.wgrad_overlap == 0 : P >= kWgradSerialPoints; }
   // The two row streams a fp32 d = 256 soft-MoE call does without; said once here, read by
   // moe_forward, the backward's chain launch and the call's weight-gradient jobs (chain_group):
   //   moe_direct_out: the training forward writes no [E, P, d] stage; the combine forms s_e y_e from the saved
@@ -215,10 +217,15 @@ struct gnot_plan {
   //                   expert's score column as their scale.  Only where the group runs on the caller's stream
   //                   right after the chain backward: a forked group reads later, beside main-stream kernels
   //                   that accumulate into dquery, and keeps the stored rows.
-  // env GNOT_MOE_STORED_STREAMS=1 (read when the plan is created) restores both stored forms (bitwise equal)
-  bool moe_stored_env = false;
-  bool moe_direct_out() const { return !moe_stored_env && D == 256 && npk() == 3; }
+  // Tuning::moe_stored (env GNOT_MOE_STORED_STREAMS=1) restores both stored forms (bitwise equal)
+  bool moe_direct_out() const { return !tune.moe_stored && D == 256 && npk() == 3; }
   bool moe_direct_dz() const { return moe_direct_out() && serial_wgrad(); }
+  // The kernel form of every attention pass, chosen by choose_attn_forms from the batch geometry and `tune`
+  // (attn_kernel, gnot_kernels.h).  [0] self attention (one set of states), [1] cross attention (the states of
+  // the I input functions; without input functions one set, the form of [0])
+  AttnKernel apply_fwd[2] = {}, apply_bwd[2] = {};
+  AttnKernel kv_bwd = {}, kv_bwd_batch = {};   // the query points' K/V backward; all (block, input function) jobs
+  int kv_batch_maxchunks = 0;                   // the largest chunk count among the batched jobs
   std::vector<hipEvent_t> evs;
   size_t ev_next = 0;
   // pinned staging ring for the table uploads of gnot_plan_bind_workspace_async: slot k is rewritten
@@ -439,8 +446,7 @@ extern "C" int gnot_plan_create(const gnot_config* cfg, gnot_plan** out) {
   }
   p->W.assign(p->n_lin(), nullptr);
   p->b.assign(p->n_lin(), nullptr);
-  if (const char* ov = std::getenv("GNOT_WGRAD_OVERLAP")) p->wgrad_overlap_env = ov[0] == '1' ? 1 : 0;
-  if (const char* ov = std::getenv("GNOT_MOE_STORED_STREAMS")) p->moe_stored_env = ov[0] == '1';
+  p->tune = tuning_from_env();
   *out = p;
   return GNOT_OK;
 }
@@ -839,7 +845,7 @@ static void finish_state_group(gnot_plan* p, WgradGroup& G) {
     const int dh = G.jobs[0].state_dh;
     long total = 0;
     for (const auto& J : G.jobs) total += J.P;
-    G.state_mfma = state_mfma_ok(d, dh) && total >= state_mfma_min_points();
+    G.state_mfma = state_mfma_ok(d, dh) && total >= p->tune.state_mfma_min_points;
     G.state_pts = state_pts(G.state_mfma, d);
     G.state_nw = 0;
     for (const auto& J : G.jobs)
@@ -1083,6 +1089,26 @@ static void ksplit_job(const gnot_plan* p, LinearArgs& a) {
   b.K = Kh;
   b.dblk = p->D;
   a = b;
+}
+
+// The kernel form of every attention pass of this batch geometry: a function of the shapes and p->tune alone,
+// so set_batch decides once and every launch obeys.  Every pitch the passes use (attn_forward, attn_backward,
+// build_attn_tables) is D, 2 D or 3 D floats, D a multiple of 16
+static void choose_attn_forms(gnot_plan* p) {
+  const int minch = p->tune.apply_mfma_min_chunks;
+  const long nq = (long)p->qchunks.size();
+  auto form = [&](AttnPass pass, int nsrc, long nchunks) {
+    return attn_kernel(pass, p->dh, p->dhr, p->H, nsrc, nchunks, true, minch);
+  };
+  for (int cross = 0; cross < 2; ++cross) {
+    const int nsrc = cross ? p->KI : 1;
+    p->apply_fwd[cross] = form(AttnPass::ApplyFwd, nsrc, nq);
+    p->apply_bwd[cross] = form(AttnPass::ApplyBwd, nsrc, nq);
+  }
+  p->kv_bwd = form(AttnPass::KVBwd, 1, nq);
+  p->kv_batch_maxchunks = 0;
+  for (int i = 0; i < p->I; ++i) p->kv_batch_maxchunks = std::max(p->kv_batch_maxchunks, (int)p->fchunks[i].size());
+  p->kv_bwd_batch = form(AttnPass::KVBwd, 1, (long)p->kv_batch_maxchunks * p->L * p->I);
 }
 
 // Device job tables of the batched input-function side of cross attention (pointers are null
@@ -1550,6 +1576,7 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
   p->fchunks.assign(I, {});
   p->fchunk_off.assign(I, {});
   for (int i = 0; i < I; ++i) make_chunks(p->fnoff[i], p->fchunks[i], p->fchunk_off[i]);
+  choose_attn_forms(p);
   if (tr) {
     C.add("dout", P * r4(p->out), r4(p->out));
     C.add("dquery", P * D, D);
@@ -1994,7 +2021,7 @@ int attn_forward(Ctx& c, int l, bool cross, const float* q_in, float* res_out, f
     GNOT_RUN(shard_allreduce(c, st, p->B * p->per_state()));   // S, z over all ranks
     ap.q = qkv; ap.ldq = 3 * D; ap.nsrc = 1; ap.state[0] = st;
   }
-  GNOT_CK(launch_attn_apply_fwd(ap, c.s));
+  GNOT_CK(launch_attn_apply(p->apply_fwd[cross], ap, false, c.s));
   if (p->sharded) GNOT_RUN(shard_exchange(c, p->P_("xb"), res_out, false));   // the scramble, across ranks
   // fc_out over the scramble rows: Dr columns per token (the head-major apply output viewed as rows of
   // H * dh = Dr floats, model.py:81-83), read zero-filled to the padded width
@@ -2032,7 +2059,7 @@ int attn_backward(Ctx& c, int l, bool cross) {
       ap.du[i] = p->P_("du" + si);
       ap.dden[i] = p->P_("dden" + si);
     }
-    GNOT_CK(launch_attn_apply_bwd(ap, c.s));
+    GNOT_CK(launch_attn_apply(p->apply_bwd[1], ap, true, c.s));
     // dS, dz per input function (kept per block: the dK/dV side of every block runs batched later)
     for (int i = 0; i < p->I; ++i) GNOT_RUN(run_state(c, p->dst_c[l][i]));
     GNOT_RUN(run_linear(c, dqkv, D, D, p->T_img[lq], nullptr, dquery, D, D, P, EPI_ACCUM, 0));
@@ -2043,14 +2070,14 @@ int attn_backward(Ctx& c, int l, bool cross) {
     const int lv = cross ? p->lin_cv(l, 0) : p->lin_sv(l);
     ap.q = qkv; ap.ldq = 3 * D; ap.nsrc = 1; ap.state[0] = p->P_(cross ? s + "cstate0" : s + "sstate");
     ap.lddq = 3 * D; ap.du[0] = p->P_("du0"); ap.dden[0] = p->P_("dden0");
-    GNOT_CK(launch_attn_apply_bwd(ap, c.s));
+    GNOT_CK(launch_attn_apply(p->apply_bwd[cross], ap, true, c.s));
     float* dst = p->P_("dstate0");
     GNOT_RUN(run_state(c, cross ? p->dst_c[l][0] : p->dst_s[l]));
     GNOT_RUN(shard_allreduce(c, dst, p->B * p->per_state()));   // dS, dz over all ranks
     AttnKVBwdArgs kb{};
     kb.k = qkv + D; kb.v = qkv + 2 * D; kb.ldkv = 3 * D; kb.dstate = dst; kb.chunks = ap.chunks;
     kb.nchunks = ap.nchunks; kb.H = p->H; kb.dh = p->dh; kb.dk = dqkv + D; kb.dv = dqkv + 2 * D; kb.lddkv = 3 * D;
-    GNOT_CK(launch_attn_kv_bwd(kb, c.s));
+    GNOT_CK(launch_attn_kv_bwd(p->kv_bwd, &kb, nullptr, 1, kb.nchunks, kb.H, kb.dh, c.s));
     GNOT_RUN(run_linear_seg(c, {{dqkv, &p->T_img[lq]}, {dqkv + D, &p->T_img[lk]}, {dqkv + 2 * D, &p->T_img[lv]}},
                             3 * D, dquery, D, P, EPI_ACCUM));
     GNOT_RUN(run_wgrad_side(c, cross ? p->wg_cross[l] : p->wg_self[l], {dsum, dqkv}));
@@ -2328,9 +2355,8 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
   // dK, dV of every (block, input function), the encodings' gradient and the key/value weight
   // gradients, batched over blocks
   if (p->I > 0 && p->L > 0) {
-    int maxch = 0;
-    for (int i = 0; i < p->I; ++i) maxch = std::max(maxch, (int)p->fchunks[i].size());
-    GNOT_CK(launch_attn_kv_bwd_batch(p->d_kvbwd_jobs, (int)p->kvbwd_jobs.size(), maxch, p->H, p->dh, cf.s));
+    GNOT_CK(launch_attn_kv_bwd(p->kv_bwd_batch, nullptr, p->d_kvbwd_jobs, (int)p->kvbwd_jobs.size(),
+                               p->kv_batch_maxchunks, p->H, p->dh, cf.s));
     for (size_t k = 0; k < p->d_dfn_jobs.size(); ++k)
       GNOT_CK(launch_linear_batch(p->d_dfn_jobs[k], p->I, (int)p->Qmax(), D, D > 512 ? D / 2 : D, p->dh, cf.s));
     GNOT_RUN(run_wgrad_side(cf, p->wg_fnkv, {}));
@@ -2455,6 +2481,29 @@ extern "C" int gnot_profile_read(gnot_plan* p, double* ms_total, int64_t* launch
   p->prof_used = 0;
   p->prof_flops = 0.0;
   p->prof_launches = 0;
+  return GNOT_OK;
+}
+
+extern "C" int gnot_debug_kernel_forms(const gnot_plan* p, char* text, size_t cap) {
+  if (!p || !text) return fail(GNOT_E_INVALID, "null argument");
+  if (!p->batch_set) return fail(GNOT_E_STATE, "set_batch first");
+  auto attn = [](AttnKernel k) { return k == AttnKernel::Mfma ? "mfma" : k == AttnKernel::Wide ? "wide" : "narrow"; };
+  auto state = [](const WgradGroup* G) { return !G || G->jobs.empty() ? "none" : G->state_mfma ? "mfma" : "valu"; };
+  std::string t;
+  auto put = [&](const char* key, const char* value) { t += (t.empty() ? "" : " ") + std::string(key) + "=" + value; };
+  put("apply_fwd.self", attn(p->apply_fwd[0]));
+  put("apply_fwd.cross", attn(p->apply_fwd[1]));
+  put("apply_bwd.self", attn(p->apply_bwd[0]));
+  put("apply_bwd.cross", attn(p->apply_bwd[1]));
+  put("kv_bwd", attn(p->kv_bwd));
+  put("kv_bwd_batch", p->I > 0 && p->L > 0 ? attn(p->kv_bwd_batch) : "none");
+  put("state.query", state(p->L > 0 ? &p->st_s[0] : nullptr));
+  put("state.fn", state(&p->st_fn));
+  put("serial_wgrad", p->serial_wgrad() ? "1" : "0");
+  put("moe_direct_out", p->moe_direct_out() ? "1" : "0");
+  put("moe_direct_dz", p->moe_direct_dz() ? "1" : "0");
+  if (t.size() + 1 > cap) return fail(GNOT_E_INVALID, "text buffer too small");
+  std::memcpy(text, t.c_str(), t.size() + 1);
   return GNOT_OK;
 }
 

@@ -1,7 +1,6 @@
 // Internal (C++) launcher interface between the engine and the HIP kernels.
 // The public C-ABI lives in include/gnot_hip.h; nothing here crosses the library boundary.
 #pragma once
-#include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,6 +39,23 @@ struct PackJob {
 inline int pack_tiles(const PackJob& J) { return J.x6 ? J.OTp * ((J.KTp + 1) / 2) : J.OTp * J.KTp; }
 hipError_t launch_pack(const PackJob* jobs_dev, const int* tile_prefix_dev, int njobs,
                        int total_tiles, hipStream_t s);
+
+// ------------------------------------------------------------------ tuning switches (tuning.cpp)
+// The plan's switches, read from the environment ONCE, when the plan is created (gnot_plan_create; microbench.cpp
+// for its own launches): a plan's kernel forms and workspace layout never change with the environment afterwards.
+struct Tuning {
+  int wgrad_overlap = -1;               // GNOT_WGRAD_OVERLAP: 0 serial / 1 forked weight gradients; -1 (unset): by size
+  bool moe_stored = false;              // GNOT_MOE_STORED_STREAMS=1: the stored soft-MoE row streams
+  // GNOT_STATE_MFMA_MIN: state_mfma_kernel only from this many points in a state group; below it the 256-point
+  // MFMA workgroups leave most CUs idle and the 64-point VALU kernel is faster (configs[1], 10k points: 3.60 vs
+  // 3.94 ms per step)
+  long state_mfma_min_points = 65536;
+  // GNOT_APPLY_MFMA_MIN: the fp32-MFMA attention passes only from this many 64-point chunks; below it they run
+  // fewer than ~128 workgroups, each staging the state images before its few chunks, and the VALU kernels are
+  // faster (configs[1], 10k points: apply bwd 23 vs 70 us per call)
+  int apply_mfma_min_chunks = 512;
+};
+Tuning tuning_from_env();
 
 // ------------------------------------------------------------------ projections (linear.hip)
 enum LinearEpi { EPI_STORE = 0, EPI_ACCUM = 1 };
@@ -219,10 +235,10 @@ hipError_t launch_wgrad(WgradKernel kind, const WgradTables& t, float* slab, int
 // [H][dh*dh + dh], `splits` partials of state_pts(d) points each at slab + slab_off.  state.hip has its own
 // partial-state kernels and its own reduce (always overwrites); it reads the tables' jobs and two prefixes.
 // Two kernels: state_mfma (fp32 MFMA, rows straight from HBM, dh = 16/32/64 with H % 4 == 0;
-// below GNOT_STATE_MFMA_MIN points the VALU form) and the VALU state_partial (LDS-staged rows, any width).
+// below Tuning::state_mfma_min_points points the VALU form) and the VALU state_partial (LDS-staged rows, any width).
 // (the instantiated state_mfma_kernel<DH, HPW> forms, HPW = heads per wave = d / dh / 4: 1 / 2 / 4 at dh 16 and
 // 32, 1 / 2 at 64; any other head count runs the VALU kernel -- round 6: 12 heads of 16 at d = 192 used to pass
-// this test and fail the launch on meshes past GNOT_STATE_MFMA_MIN)
+// this test and fail the launch on meshes past the threshold)
 inline bool state_mfma_ok(int d, int dh) {
   if (!((dh == 16 || dh == 32 || dh == 64) && d % dh == 0 && (d / dh) % 4 == 0)) return false;
   const int hpw = d / dh / 4;
@@ -232,13 +248,6 @@ inline bool state_mfma_ok(int d, int dh) {
 // the row bytes); VALU: the workgroup's A and B rows fill <= 32 KiB of LDS each (64 at d <= 128,
 // 8192 / d above; measured: 32 and 16 are slower at cfg2)
 inline int state_pts(bool mfma, int d) { return mfma ? 256 : d <= 128 ? 64 : 8192 / d; }
-// MFMA only from this many points in the group (env GNOT_STATE_MFMA_MIN, read per plan): below it the
-// 256-point MFMA workgroups leave most CUs idle and the 64-point VALU kernel is faster (configs[1],
-// 10k points: 3.60 vs 3.94 ms per step)
-inline long state_mfma_min_points() {
-  const char* e = std::getenv("GNOT_STATE_MFMA_MIN");
-  return e ? std::atol(e) : 65536;
-}
 // d: row width, pts: points per workgroup, nw: per-point weights (0 or H), mfma: state_mfma_kernel (state_mfma_ok)
 hipError_t launch_state(const WgradTables& t, float* slab, int d, int dh, int pts, int nw, bool mfma, hipStream_t s);
 
@@ -260,11 +269,6 @@ struct AttnApplyArgs {
   float* du[8]; long lddu;           // per source du, point-major
   float* dden[8];                    // per source [P, H]
 };
-hipError_t launch_attn_apply_fwd(const AttnApplyArgs& a, hipStream_t s);
-hipError_t launch_attn_apply_bwd(const AttnApplyArgs& a, hipStream_t s);
-// fp32-MFMA variants (attn_mfma.hip, dh = 16/32/64); hipErrorNotSupported when not applicable
-hipError_t launch_attn_apply_mfma(const AttnApplyArgs& a, bool bwd, hipStream_t s);
-
 struct AttnKVBwdArgs {
   const float* k; const float* v; long ldkv;   // post-softmax k, v (point-major)
   const float* dstate;               // [B][H][dh*dh + dh]  (dS, dz)
@@ -272,14 +276,27 @@ struct AttnKVBwdArgs {
   int H, dh;
   float* dk; float* dv; long lddkv;  // pre-softmax dK, dV
 };
-hipError_t launch_attn_kv_bwd(const AttnKVBwdArgs& a, hipStream_t s);
-// independent K/V backward jobs (every block x input function) in one launch, job = grid.y
-hipError_t launch_attn_kv_bwd_batch(const AttnKVBwdArgs* jobs_dev, int njobs, int maxchunks, int H, int dh,
-                                    hipStream_t s);
-// fp32-MFMA K/V backward (attn_mfma.hip): one job (a) or the batched jobs; hipErrorNotSupported
-// when not applicable
-hipError_t launch_attn_kv_bwd_mfma(const AttnKVBwdArgs* a, const AttnKVBwdArgs* jobs_dev, int njobs, int maxchunks,
-                                   int H, int dh, hipStream_t s);
+// The kernel form of an attention pass.  The plan chooses it once per batch geometry (attn_kernel, stored by
+// gnot_plan_set_batch); the launchers run the form they are given and return hipErrorInvalidValue for one the
+// arguments cannot run -- there is no fallback
+enum class AttnKernel {
+  Narrow,   // attn.hip's DH-templated VALU kernels: dh <= 64, a multiple of 4
+  Wide,     // attn.hip's NB-templated VALU kernels: 64 < dh <= 256, a multiple of 4
+  Mfma,     // attn_mfma.hip, fp32 MFMA: dh = 16 / 32 / 64, 4-aligned pitches, the state images within 160 KiB of LDS
+};
+enum class AttnPass { ApplyFwd, ApplyBwd, KVBwd };
+// The form of one pass (attn_mfma.hip), a function of shapes and the threshold alone.  Mfma where all of these
+// hold: dh is 16, 32 or 64; the heads are not padded (dhr is 0 or dh; the K/V backward's rows are whole internal
+// heads, it ignores dhr); the images of nsrc sets of states (1 .. 8; the K/V backward: 1) fit the LDS; aligned4:
+// every row pitch the pass uses (apply forward: ldq; backward: ldq, lddq, lddu; K/V: ldkv, lddkv) is a multiple
+// of 4; the pass has at least min_chunks (Tuning::apply_mfma_min_chunks) 64-point chunks, the batched K/V
+// backward counting maxchunks * njobs.  Otherwise Wide above a head width of 64 and Narrow up to it
+AttnKernel attn_kernel(AttnPass pass, int dh, int dhr, int H, int nsrc, long nchunks, bool aligned4, int min_chunks);
+hipError_t launch_attn_apply(AttnKernel form, const AttnApplyArgs& a, bool bwd, hipStream_t s);
+// K/V backward: one job (a), or the independent jobs of jobs_dev (every block x input function, a == null) in
+// one launch, job = grid.z, maxchunks the largest chunk count among them; H and dh are those of every job
+hipError_t launch_attn_kv_bwd(AttnKernel form, const AttnKVBwdArgs* a, const AttnKVBwdArgs* jobs_dev, int njobs,
+                              int maxchunks, int H, int dh, hipStream_t s);
 
 // ------------------------------------------------------------------ small elementwise (misc.hip)
 hipError_t launch_concat_theta(const float* x, long ldx, int in_dim, const float* theta, int th_dim,

@@ -187,6 +187,8 @@ __global__ void __launch_bounds__(256) linear_batch_kernel(const LinearArgs* __r
 // 36: the divisors 1 and 3 of 9 tiles split a head, 9 does not).  GNOT_LINEAR_OC overrides the choice
 // (experiments); a choice that does not tile D and NO, or would split a head, falls back to the widest
 // valid one; -1 when none exists (the launch then fails instead of skipping the softmax).
+// The switch is read once per process, not per plan like gnot_kernels.h Tuning: it picks a template instantiation
+// inside launchers the chains reach too (launch_chain_fwd / bwd), with no plan in their arguments.
 int linear_oc(int D, int NO, int nsoft, int dh) {
   static const int env = [] {
     const char* e = getenv("GNOT_LINEAR_OC");

@@ -190,7 +190,8 @@ bool linear2_supported(const LinearArgs& a, int D) {
 
 // output-tile chunks per launch: enough workgroups for two per CU (their register budget) on small batches
 // (configs[0]: 16,384 points = 256 workgroups of 4 waves, each streaming the whole image tile by tile, one wave
-// per SIMD); a divisor of the head groups, 1 from 512 point workgroups up (GNOT_LINEAR2_CHUNKS overrides)
+// per SIMD); a divisor of the head groups, 1 from 512 point workgroups up (GNOT_LINEAR2_CHUNKS overrides: an
+// experiment switch read once per process, not per plan like gnot_kernels.h Tuning, for linear.hip's reason)
 static int l2_chunks(int nwg, int groups) {
   static const int env = [] {
     const char* e = std::getenv("GNOT_LINEAR2_CHUNKS");

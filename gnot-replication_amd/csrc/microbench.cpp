@@ -346,6 +346,8 @@ int main(int argc, char** argv) {
     float* dq = dalloc((size_t)P * 3 * D, 0.f);
     hipStream_t s2;
     CK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+    // the forms a plan with these shapes and this environment would choose
+    const int minch = tuning_from_env().apply_mfma_min_chunks;
     for (int nsrc : {1, 2}) {
       AttnApplyArgs ap{};
       ap.q = q; ap.ldq = nsrc == 1 ? 3 * D : D; ap.nsrc = nsrc; ap.chunks = dch; ap.nchunks = (int)ch.size();
@@ -357,20 +359,23 @@ int main(int argc, char** argv) {
       }
       // algorithmic HBM bytes: fwd reads q, writes res; bwd reads q, dres, writes du (per source), dq, dden
       const double bf = 2.0 * P * D * 4, bb = (3.0 + nsrc) * P * D * 4 + 4.0 * nsrc * P * H;
-      t = time_us([&] { CK(launch_attn_apply_fwd(ap, nullptr)); });
+      const AttnKernel ffwd = attn_kernel(AttnPass::ApplyFwd, dh, 0, H, nsrc, ap.nchunks, true, minch);
+      const AttnKernel fbwd = attn_kernel(AttnPass::ApplyBwd, dh, 0, H, nsrc, ap.nchunks, true, minch);
+      t = time_us([&] { CK(launch_attn_apply(ffwd, ap, false, nullptr)); });
       std::printf("apply_fwd  nsrc=%d P=%d H=%d dh=%d: %8.2f us  %6.0f GB/s\n", nsrc, P, H, dh, t, bf / t / 1e3);
-      t = time_us([&] { CK(launch_attn_apply_bwd(ap, nullptr)); });
+      t = time_us([&] { CK(launch_attn_apply(fbwd, ap, true, nullptr)); });
       std::printf("apply_bwd  nsrc=%d P=%d H=%d dh=%d: %8.2f us  %6.0f GB/s\n", nsrc, P, H, dh, t, bb / t / 1e3);
       if (nsrc == 1) {   // K/V backward of the self attention (k, v = the 2nd/3rd thirds of the qkv rows)
         AttnKVBwdArgs kb{};
         kb.k = q + D; kb.v = q + 2 * D; kb.ldkv = 3 * D; kb.dstate = st; kb.chunks = dch; kb.nchunks = (int)ch.size();
         kb.H = H; kb.dh = dh; kb.dk = dq + D; kb.dv = dq + 2 * D; kb.lddkv = 3 * D;
-        t = time_us([&] { CK(launch_attn_kv_bwd(kb, nullptr)); });
+        const AttnKernel fkv = attn_kernel(AttnPass::KVBwd, dh, 0, H, 1, kb.nchunks, true, minch);
+        t = time_us([&] { CK(launch_attn_kv_bwd(fkv, &kb, nullptr, 1, kb.nchunks, H, dh, nullptr)); });
         std::printf("kv_bwd     P=%d H=%d dh=%d: %8.2f us  %6.0f GB/s\n", P, H, dh, t, 4.0 * P * D * 4 / t / 1e3);
       }
       // contention: wgrad launches queued on s2 while apply_bwd is timed on the null stream
       for (int i = 0; i < 30; ++i) tile128(djobs, s2);
-      t = time_us([&] { CK(launch_attn_apply_bwd(ap, nullptr)); }, 20);
+      t = time_us([&] { CK(launch_attn_apply(fbwd, ap, true, nullptr)); }, 20);
       std::printf("apply_bwd  nsrc=%d under concurrent wgrad: %8.2f us\n", nsrc, t);
       CK(hipStreamSynchronize(s2));
     }

@@ -36,6 +36,7 @@ EXPORTS = [
     "gnot_ema_update", "gnot_adamw_step_ema", "gnot_gather_rows", "gnot_debug_gelu",
     "gnot_channel_stats_work_floats", "gnot_channel_stats", "gnot_gather_rows_affine", "gnot_rel_l2_loss_affine",
     "gnot_mse_loss_affine", "gnot_plan_set_fourier", "gnot_fourier_embed", "gnot_fourier_embed_bwd",
+    "gnot_debug_kernel_forms",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -66,7 +67,7 @@ def build(jobs=8, quiet=True):
 # every file the library's code depends on (csrc/Makefile's SRCS, its headers and its flags)
 SOURCES = ["Makefile", "gnot_common.h", "gnot_kernels.h", "x6_core.h", "pack.hip", "linear.hip", "linear2.hip",
            "chain.hip", "chain2.hip", "chainw.hip", "wgrad.hip", "state.hip", "attn.hip", "attn_mfma.hip", "misc.hip",
-           "fourier.hip", "train.hip", "gather.hip", "stats.hip", "engine.cpp"]
+           "fourier.hip", "train.hip", "gather.hip", "stats.hip", "engine.cpp", "tuning.cpp"]
 
 
 def source_hash():
@@ -114,6 +115,7 @@ def _declare(lib):
     lib.gnot_profile_read.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64),
                                       ctypes.POINTER(ctypes.c_double)]
     lib.gnot_debug_buffer.argtypes = [P, ctypes.c_char_p, ctypes.POINTER(P), ctypes.POINTER(i64)]
+    lib.gnot_debug_kernel_forms.argtypes = [P, ctypes.c_char_p, sz]
     lib.gnot_plan_set_shard.argtypes = [P, i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(GnotComm)]
     lib.gnot_plan_set_grad_comm.argtypes = [P, ctypes.POINTER(GnotComm)]
     lib.gnot_shard_range.argtypes = [i64, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)]
@@ -170,6 +172,13 @@ def load():
 def check(rc):
     if rc != 0:
         raise RuntimeError(f"libgnot_hip error {rc}: {load().gnot_last_error().decode()}")
+
+
+def kernel_forms(plan):
+    """gnot_debug_kernel_forms of a plan whose batch is set, as a dict of its key=value pairs (host only)."""
+    text = ctypes.create_string_buffer(512)
+    check(load().gnot_debug_kernel_forms(plan, text, len(text)))
+    return dict(kv.split("=") for kv in text.value.decode().split())
 
 
 def probe_plan(cfg, nx=0, nf=0):

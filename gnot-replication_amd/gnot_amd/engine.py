@@ -170,6 +170,11 @@ class Engine:
             last_o = self.dims[-1][0]
             self.grad_arena = wsf[base // 4: base // 4 + offs[2 * n - 1] + last_o]
 
+    def kernel_forms(self):
+        """The kernel forms the plan chose for the current batch geometry (gnot_debug_kernel_forms) as a dict,
+        e.g. {"apply_fwd.self": "narrow", ..., "state.query": "valu", "serial_wgrad": "0"}.  Needs no GPU."""
+        return _lib.kernel_forms(self.plan)
+
     def debug_ptr(self, name):
         ptr = ctypes.c_void_p()
         ld = ctypes.c_int64()

@@ -432,6 +432,24 @@ int gnot_profile_read(gnot_plan* plan, double* ms_total, int64_t* launches, doub
  * ("scores", "query0", "out_h0", ...); returns GNOT_E_INVALID for unknown names. */
 int gnot_debug_buffer(const gnot_plan* plan, const char* name, float** ptr, int64_t* ld);
 
+/* Debug/test hook: the kernel forms the plan chose for the current batch geometry, as one line of
+ * space-separated key=value pairs written into text (cap bytes with the terminator; 256 suffice;
+ * GNOT_E_INVALID when too small).  Needs gnot_plan_set_batch (GNOT_E_STATE before) and no GPU.  The keys:
+ *   apply_fwd.self  apply_fwd.cross  apply_bwd.self  apply_bwd.cross  kv_bwd  kv_bwd_batch
+ *       the attention passes: narrow | wide (the VALU kernels up to / above a head width of 64) | mfma.
+ *       self / cross: one set of states / those of the input functions (without input functions cross is one
+ *       set too); kv_bwd the K/V backward over the query points, kv_bwd_batch the one launch over every
+ *       (block, input function), none without input functions or blocks
+ *   state.query  state.fn
+ *       the attention-state groups: valu | mfma | none (no such group).  Every group over the query points
+ *       (forward and backward, self and cross) holds the same points and has one form; state.fn is the batched
+ *       forward group of all (block, input function, sample)
+ *   serial_wgrad  moe_direct_out  moe_direct_dz
+ *       0 | 1: weight gradients on the caller's stream instead of forked; the two soft-MoE row streams done
+ *       without
+ * The forms follow from the shapes and the GNOT_* switches read when the plan was created. */
+int gnot_debug_kernel_forms(const gnot_plan* plan, char* text, size_t cap);
+
 /* Debug/test hook: the device GELU every chain epilogue and weight-gradient loader inlines, evaluated
  * elementwise over n >= 1 contiguous floats (one launch on `stream`): y = gelu(x), dy = gelu'(x), and (y2, dy2)
  * the fused value-and-derivative form, bitwise equal to (y, dy).  No plan; the hot path never calls it. */

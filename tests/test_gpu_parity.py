@@ -34,12 +34,37 @@ def run_packed(m, fx, G):
 def attn_path(request, monkeypatch):
     """'auto': the size-based choice (VALU attention passes below 512 point chunks and VALU state
     reductions below 65,536 points, i.e. every fixture); 'mfma': GNOT_APPLY_MFMA_MIN=0 and
-    GNOT_STATE_MFMA_MIN=0 force the fp32-MFMA apply / K-V backward (attn_mfma.hip) and state
-    (state.hip) kernels wherever the head width has one."""
+    GNOT_STATE_MFMA_MIN=0 make the plan choose the fp32-MFMA apply / K-V backward (attn_mfma.hip) and
+    state (state.hip) kernels wherever the head width has one.  Both are read when the plan is created,
+    so the fixture sets them before the test builds its model; test_fixture_parity_packed asserts the
+    forms each parametrisation ran."""
     if request.param == "mfma":
         monkeypatch.setenv("GNOT_APPLY_MFMA_MIN", "0")
         monkeypatch.setenv("GNOT_STATE_MFMA_MIN", "0")
     return request.param
+
+
+def expected_forms(cfg, attn_path):
+    """What Engine.kernel_forms must report for a model of `cfg` on a fixture-sized batch (far below 512 chunks
+    and 65,536 points): the rule of csrc/attn_mfma.hip attn_kernel and gnot_kernels.h state_mfma_ok, restated."""
+    d, H, I = cfg["d"], cfg["n_head"], cfg["n_input_functions"]
+    dh = (d // H + 3) // 4 * 4                         # the internal head width (padded heads: the next multiple of 4)
+    valu = "wide" if dh > 64 else "narrow"
+
+    def attn(nsrc, bwd, padded_ok=False):
+        lds = ((2 if bwd else 1) * nsrc * H * (dh // 16) ** 2 * 64 * 4 + nsrc * H * dh) * 4
+        mfma = attn_path == "mfma" and dh in (16, 32, 64) and (padded_ok or dh * H == d) and lds <= 160 * 1024
+        return "mfma" if mfma else valu
+
+    hpw = H // 4                                       # state_mfma_ok: heads per wave 1 / 2, or 4 up to dh = 32
+    state_ok = dh in (16, 32, 64) and H % 4 == 0 and (hpw in (1, 2) or (hpw == 4 and dh <= 32))
+    state = "mfma" if attn_path == "mfma" and state_ok else "valu"
+    L = cfg["n_attn_layers"]
+    kv = attn(1, True, padded_ok=True)                 # K/V rows are whole internal heads
+    return {"apply_fwd.self": attn(1, False), "apply_bwd.self": attn(1, True),
+            "apply_fwd.cross": attn(max(I, 1), False), "apply_bwd.cross": attn(max(I, 1), True),
+            "kv_bwd": kv, "kv_bwd_batch": kv if L > 0 and I > 0 else "none",
+            "state.query": state if L > 0 else "none", "state.fn": state if L > 0 and I > 0 else "none"}
 
 
 @pytest.mark.parametrize("name", fixture_names())
@@ -49,6 +74,12 @@ def test_fixture_parity_packed(name, attn_path):
     out, grads = run_packed(m, fx, fx["G"])
     errs = check_parity(out, grads, fx)
     assert not errs, errs
+    # the kernels that ran: MFMA wherever it exists under 'mfma', the VALU forms under 'auto'
+    forms = m.engine().kernel_forms()
+    want = expected_forms(fx["cfg"], attn_path)
+    assert {k: forms[k] for k in want} == want
+    if attn_path == "auto":
+        assert not {"mfma"} & {forms[k] for k in want}
 
 
 @pytest.mark.parametrize("name", [n for n in fixture_names() if load(n)["meta"]["mode"] == "padded"])

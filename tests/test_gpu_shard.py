@@ -188,8 +188,9 @@ def test_point_sharded_configs3_widths_70k_points(mid_case, overlap):
     """configs[3]'s model widths (d=256, 8 heads, 8 experts, 4-layer MLPs, one 805-point input function;
     L = 1 block) on one 70,000-point mesh split over 2 ranks (35,000 points each, gloo host staging on one
     GPU) vs the float64 oracle at 1e-4: the sharded run takes the kernels a 1M / 8 rank does -- the MFMA
-    attention apply / K-V backward (>= 8,192 points), the MFMA state partials (GNOT_STATE_MFMA_MIN=16384
-    in the ranks: per-rank groups of 35,000 points), the wide weight gradients -- and real exchange
+    attention apply / K-V backward (from 512 chunks of 64 points: 547 per rank), the MFMA state partials
+    (GNOT_STATE_MFMA_MIN=16384 in the ranks' environment before they build the model -- the plan reads its
+    switches when it is created: per-rank groups of 35,000 points), the wide weight gradients -- and real exchange
     tables (the scramble of 8 heads over 70,000 points is 16 runs per rank pair).  Anchor: the all-point
     state sums model.py:98-100 (all-reduced) and the head-major reshape model.py:103-104 (all-to-all).
     overlap "auto": 35,000 points per rank fork their weight gradients onto the side stream; "0"
