@@ -2,12 +2,13 @@
 // exercises every C-ABI entry point that needs no GPU -- plan creation for the supported widths and for the edges
 // of the other constructor arguments (depth, blocks, theta_dim 0, experts, input functions, input / output widths), packed
 // batch geometries (ragged, empty samples, many meshes, padded-equal strides), MoE recompute and
-// precision switches, workspace sizing, gradient offsets, the caller-owned gradient arena, the flag
+// precision switches, the pre-norm option, workspace sizing, gradient offsets, the caller-owned gradient arena, the flag
 // validation of gnot_backward_ex, the point-shard exchange tables and the error paths -- so heap overflows / use-after-free in engine.cpp's table building show up on the CPU.
 // Run by tests/test_asan.py; exit status 0 = every check passed and ASan reported nothing.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <random>
 #include <vector>
 
@@ -201,6 +202,82 @@ static void exchange(std::mt19937& rng) {
   CHECK(gnot_shard_exchange(0, nullptr, 8, 32, 0, 1, nullptr, nullptr, nullptr, 0, &nseg) == GNOT_E_INVALID);
 }
 
+// pre-norm (gnot_plan_set_pre_norm): training and inference plans with and without input functions at a plain,
+// a padded and a layer-wise width; the option adds buffers and re-targets job tables, on-then-off restores the
+// plain layout, and the stand-alone entries refuse bad arguments before any launch.  (Its sizes stay out of
+// the layout digest, and it draws from a generator of its own: the digest keeps describing the plain plans.)
+static void pre_norm() {
+  std::mt19937 rng(777);
+  const int widths[][2] = {{64, 4}, {40, 2}, {30, 5}, {256, 8}, {320, 5}, {576, 9}};
+  for (const auto& wh : widths)
+    for (int I = 0; I <= 2; ++I) {
+      gnot_config c{};
+      c.input_dim = 2; c.theta_dim = 1; c.input_func_dim = 3; c.out_dim = 2; c.n_attn_layers = 1 + I;
+      c.n_attn_hidden_dim = c.n_mlp_hidden_dim = c.n_input_hidden_dim = wh[0];
+      c.n_mlp_num_layers = 2; c.n_expert = 3; c.n_head = wh[1]; c.n_input_functions = I;
+      gnot_plan* p = nullptr;
+      CHECK(gnot_plan_create(&c, &p) == GNOT_OK);
+      if (!p) continue;
+      CHECK(gnot_plan_set_pre_norm(p, 1, 0.f) == GNOT_E_INVALID);
+      CHECK(gnot_plan_set_pre_norm(p, 1, -1e-5f) == GNOT_E_INVALID);
+      CHECK(gnot_plan_set_pre_norm(p, 1, std::numeric_limits<float>::quiet_NaN()) == GNOT_E_INVALID);
+      for (int trial = 0; trial < 4; ++trial) {
+        const int B = 1 + (int)(rng() % 5);
+        std::vector<int64_t> n(B), m(B);
+        for (int b = 0; b < B; ++b) {
+          n[b] = (trial == 1 && b == 0 && B > 1) ? 0 : 1 + (int64_t)(rng() % 2000);   // an empty sample once
+          m[b] = n[b] ? 1 + (int64_t)(rng() % 300) : 0;
+        }
+        const auto xo = offsets(n);
+        std::vector<int64_t> fo;
+        for (int i = 0; i < I; ++i) {
+          const auto o = offsets(m);
+          fo.insert(fo.end(), o.begin(), o.end());
+        }
+        for (int tr = 0; tr < 2; ++tr)
+          for (int rc = 0; rc < 2; ++rc) {
+            CHECK(gnot_plan_set_moe_recompute(p, rc) == GNOT_OK);
+            CHECK(gnot_plan_set_pre_norm(p, 0, 1e-5f) == GNOT_OK);
+            CHECK(gnot_plan_set_batch(p, B, xo.data(), I ? fo.data() : nullptr, tr) == GNOT_OK);
+            const size_t plain = gnot_plan_workspace_bytes(p);
+            CHECK(gnot_plan_set_pre_norm(p, 1, 1e-5f) == GNOT_OK);
+            CHECK(gnot_plan_workspace_bytes(p) == 0);                  // batch invalidated
+            CHECK(gnot_plan_set_batch(p, B, xo.data(), I ? fo.data() : nullptr, tr) == GNOT_OK);
+            CHECK(gnot_plan_workspace_bytes(p) > plain);
+            CHECK(gnot_plan_set_pre_norm(p, 0, 1e-5f) == GNOT_OK);
+            CHECK(gnot_plan_set_batch(p, B, xo.data(), I ? fo.data() : nullptr, tr) == GNOT_OK);
+            CHECK(gnot_plan_workspace_bytes(p) == plain);              // on, then off: the plain layout
+          }
+        // sharded, with the option on
+        gnot_comm comm{nullptr, fake_allreduce, fake_alltoallv};
+        CHECK(gnot_plan_set_pre_norm(p, 1, 1e-5f) == GNOT_OK);
+        for (int r = 0; r < 2; ++r) {
+          CHECK(gnot_plan_set_shard(p, r, 2, B, n.data(), &comm) == GNOT_OK);
+          std::vector<int64_t> loc(B);
+          for (int b = 0; b < B; ++b) {
+            int64_t lo, hi;
+            CHECK(gnot_shard_range(n[b], r, 2, &lo, &hi) == GNOT_OK);
+            loc[b] = hi - lo;
+          }
+          const auto lo = offsets(loc);
+          const int st = gnot_plan_set_batch(p, B, lo.data(), I ? fo.data() : nullptr, 1);
+          CHECK(st == GNOT_OK || lo.back() == 0);
+        }
+        CHECK(gnot_plan_set_shard(p, 0, 1, B, n.data(), nullptr) == GNOT_OK);
+      }
+      gnot_plan_destroy(p);
+    }
+  alignas(16) static float buf[8];
+  CHECK(gnot_layer_norm(nullptr, 4, 1, 4, 1e-5f, buf, 4, nullptr, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_layer_norm(buf, 4, 0, 4, 1e-5f, buf + 4, 4, nullptr, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_layer_norm(buf, 4, 1, 1025, 1e-5f, buf + 4, 4, nullptr, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_layer_norm(buf, 2, 1, 2, 1e-5f, buf + 4, 4, nullptr, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_layer_norm(buf + 1, 4, 1, 3, 1e-5f, buf + 4, 4, nullptr, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_layer_norm(buf, 4, 1, 4, 0.f, buf + 4, 4, nullptr, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_layer_norm_bwd(buf, 4, nullptr, buf, 4, 1, 4, buf + 4, 4, 0, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_layer_norm_bwd(buf, 4, buf, buf, 4, 1, 4, buf + 4, 6, 0, nullptr) == GNOT_E_INVALID);
+}
+
 int main() {
   std::mt19937 rng(12345);
   // {width, heads}: 96 / 192 have head widths 12 / 24; 320 runs chainw.hip, 576 (internal width 640) the
@@ -273,6 +350,7 @@ int main() {
     gnot_plan_destroy(p);
   }
   exchange(rng);
+  pre_norm();
   std::printf("layout digest: %016llx\n", (unsigned long long)g_digest);
   std::printf("asan_plan_check: %s (%d failed checks)\n", g_fail ? "FAILED" : "ok", g_fail);
   return g_fail ? 1 : 0;

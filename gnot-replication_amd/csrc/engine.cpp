@@ -127,6 +127,15 @@ struct gnot_plan {
   // Fourier embedding (gnot_plan_set_fourier): orders of x and of the input functions (0: none) and the widths
   // of the caller's rows; in / F above stay the embedded widths, which the Linears and the workspace have
   int nx = 0, nf = 0, in_raw = 0, F_raw = 0;
+  // pre-norm (gnot_plan_set_pre_norm): the attention calls read the parameter-free LayerNorm (over the Dr real
+  // columns, norm.hip) of the residual stream ("b{l}.n1" / "b{l}.n2") and of the input-function encodings
+  // ("fnn{i}", shared by every block); the residual stream itself is untouched
+  bool pre_norm = false;
+  float norm_eps = 1e-5f;
+  std::string norm_buf(int l, bool cross) const { return "b" + std::to_string(l) + (cross ? ".n1" : ".n2"); }
+  std::string norm_rstd(int l, bool cross) const { return "b" + std::to_string(l) + (cross ? ".r1" : ".r2"); }
+  // the rows the key/value projections of input function i read (and their weight gradients)
+  std::string fn_rows(int i) const { return (pre_norm ? "fnn" : "fnenc") + std::to_string(i); }
   std::vector<int> lin_o, lin_i;   // out / in features per canonical Linear
   std::vector<const float*> W, b;
   bool params_bound = false;
@@ -1034,7 +1043,7 @@ static void build_groups(gnot_plan* p) {
     for (int l = 0; l < p->L; ++l)
       for (int i = 0; i < I; ++i) {
         const std::string dkv = p->dkv_buf(l, i);
-        const float* enc = p->P_("fnenc" + std::to_string(i));
+        const float* enc = p->P_(p->fn_rows(i));
         lin_job_heads(p->wg_fnkv, p->lin_ck(l, i), p->P_(dkv), 2 * D, enc, D, p->Q[i]);
         lin_job_heads(p->wg_fnkv, p->lin_cv(l, i), p->P_(dkv, D), 2 * D, enc, D, p->Q[i]);
       }
@@ -1050,7 +1059,7 @@ static void build_groups(gnot_plan* p) {
     {
       const std::string dqkv = p->dqkv_buf(false);
       WgradGroup& G = p->wg_self[l];
-      const float* q1 = p->P_(s + "query1");
+      const float* q1 = p->P_(p->pre_norm ? p->norm_buf(l, false) : s + "query1");
       lin_job(G, p->lin_so(l), p->P_(p->dsum_buf(false)), D, p->P_(s + "sres"), p->Dr, 0, P);
       lin_job_heads(G, p->lin_sq(l), p->P_(dqkv), 3 * D, q1, D, P);
       lin_job_heads(G, p->lin_sk(l), p->P_(dqkv, D), 3 * D, q1, D, P);
@@ -1060,7 +1069,7 @@ static void build_groups(gnot_plan* p) {
     {
       const std::string dqkv = p->dqkv_buf(true);
       WgradGroup& G = p->wg_cross[l];
-      const float* qin = p->P_(p->block_query(l));
+      const float* qin = p->P_(p->pre_norm ? p->norm_buf(l, true) : p->block_query(l));
       lin_job(G, p->lin_co(l), p->P_(p->dsum_buf(true)), D, p->P_(s + "cres"), p->Dr, 0, P);
       if (I > 0) {
         lin_job_heads(G, p->lin_cq(l), p->P_(dqkv), D, qin, D, P);   // key/value grads: wg_fnkv
@@ -1124,7 +1133,7 @@ static void build_attn_tables(gnot_plan* p) {
       const std::string s = "b" + std::to_string(l) + ".", si = std::to_string(i);
       const gnot_plan::AttnImgs& A = p->cross_img[l];
       LinearArgs a{};
-      a.nseg = 1; a.X[0] = p->P_("fnenc" + si); a.ldx = D; a.Wp[0] = A.kv[i].p; a.nsum = 1; a.K = D;
+      a.nseg = 1; a.X[0] = p->P_(p->fn_rows(i)); a.ldx = D; a.Wp[0] = A.kv[i].p; a.nsum = 1; a.K = D;
       a.bias = p->P_("pbias", A.bkv[i]); a.Y = p->P_(s + "ckv" + si); a.ldy = 2 * D; a.NO = 2 * D; a.P = (int)p->Q[i];
       a.epi = EPI_STORE; a.nsoft = D; a.dh = p->dh; a.dreal = p->attn_dreal();
       a.dhr = p->head_padded() ? p->dhr : 0;
@@ -1436,6 +1445,18 @@ extern "C" int gnot_plan_set_fourier(gnot_plan* p, int nx, int nf) {
   return GNOT_OK;
 }
 
+extern "C" int gnot_plan_set_pre_norm(gnot_plan* p, int on, float eps) {
+  if (!p) return fail(GNOT_E_INVALID, "null plan");
+  if (!std::isfinite(eps) || !(eps > 0.f)) return fail(GNOT_E_INVALID, "pre-norm: eps must be finite and positive");
+  if (p->pre_norm != (on != 0) || p->norm_eps != eps) {
+    p->pre_norm = on != 0;
+    p->norm_eps = eps;
+    p->batch_set = false;          // the workspace layout changes: set_batch + bind again
+    p->ws_bound = false;
+  }
+  return GNOT_OK;
+}
+
 extern "C" int gnot_plan_set_moe_recompute(gnot_plan* p, int on) {
   if (!p) return fail(GNOT_E_INVALID, "null plan");
   if (p->moe_recompute != (on != 0)) {
@@ -1570,6 +1591,21 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
   if (p->sharded) {                          // scramble exchange scratch: head-major rows / packed peers
     C.add("xa", P * D, p->Dr);
     C.add("xb", P * D, p->Dr);
+  }
+  if (p->pre_norm && p->L > 0) {
+    // the normalised attention inputs, kept per block (the q / k / v weight gradients read their Linear's
+    // input) and once per input function (no parameters: the same rows for every block); training keeps
+    // each row's rstd for the backward
+    for (int l = 0; l < p->L; ++l)
+      for (bool cross : {true, false}) {
+        C.add(p->norm_buf(l, cross), P * D, D);
+        if (tr) C.add(p->norm_rstd(l, cross), P, 1);
+      }
+    for (int i = 0; i < I; ++i) {
+      C.add("fnn" + std::to_string(i), p->Q[i] * D, D);
+      if (tr) C.add("fnr" + std::to_string(i), p->Q[i], 1);
+    }
+    if (tr) C.add("dnorm", P * D, D);          // d(normalised rows) of one attention call, origin stream only
   }
   // attention segments
   make_chunks(p->xoff, p->qchunks, p->qchunk_off);
@@ -2042,6 +2078,17 @@ int attn_backward(Ctx& c, int l, bool cross) {
   float* dres = p->P_("dres");
   float* dquery = p->P_("dquery");
   float* dqkv = p->P_(p->dqkv_buf(cross));
+  // pre-norm: the projections' backward-data is the gradient of the NORMALISED rows: stored into "dnorm"
+  // (written and read on this stream only; no forked weight gradient reads it), then pulled through the norm
+  // and added onto dquery
+  float* dq_dst = p->pre_norm ? p->P_("dnorm") : dquery;
+  const int dq_epi = p->pre_norm ? EPI_STORE : EPI_ACCUM;
+  auto norm_bwd = [&]() -> int {
+    if (!p->pre_norm) return GNOT_OK;
+    GNOT_CK(launch_layer_norm_bwd(p->P_(p->norm_buf(l, cross)), D, p->P_(p->norm_rstd(l, cross)), dq_dst, D, P, p->Dr,
+                                  dquery, D, 1, c.s));
+    return GNOT_OK;
+  };
   GNOT_RUN(guard_write(c, dqkv));
   // fc_out backward-data: dres = dout W_o (token order); sharded: back to this rank's head-major rows
   GNOT_RUN(run_linear(c, dsum, D, D, p->T_img[lo], nullptr, dres, p->Dr, D, P, EPI_STORE, 0, p->Dr));
@@ -2062,7 +2109,8 @@ int attn_backward(Ctx& c, int l, bool cross) {
     GNOT_CK(launch_attn_apply(p->apply_bwd[1], ap, true, c.s));
     // dS, dz per input function (kept per block: the dK/dV side of every block runs batched later)
     for (int i = 0; i < p->I; ++i) GNOT_RUN(run_state(c, p->dst_c[l][i]));
-    GNOT_RUN(run_linear(c, dqkv, D, D, p->T_img[lq], nullptr, dquery, D, D, P, EPI_ACCUM, 0));
+    GNOT_RUN(run_linear(c, dqkv, D, D, p->T_img[lq], nullptr, dq_dst, D, D, P, dq_epi, 0));
+    GNOT_RUN(norm_bwd());
     GNOT_RUN(run_wgrad_side(c, p->wg_cross[l], {dsum, dqkv}));
   } else {
     const float* qkv = p->P_(cross ? s + "cq" : s + "sq");
@@ -2079,7 +2127,8 @@ int attn_backward(Ctx& c, int l, bool cross) {
     kb.nchunks = ap.nchunks; kb.H = p->H; kb.dh = p->dh; kb.dk = dqkv + D; kb.dv = dqkv + 2 * D; kb.lddkv = 3 * D;
     GNOT_CK(launch_attn_kv_bwd(p->kv_bwd, &kb, nullptr, 1, kb.nchunks, kb.H, kb.dh, c.s));
     GNOT_RUN(run_linear_seg(c, {{dqkv, &p->T_img[lq]}, {dqkv + D, &p->T_img[lk]}, {dqkv + 2 * D, &p->T_img[lv]}},
-                            3 * D, dquery, D, P, EPI_ACCUM));
+                            3 * D, dq_dst, D, P, dq_epi));
+    GNOT_RUN(norm_bwd());
     GNOT_RUN(run_wgrad_side(c, cross ? p->wg_cross[l] : p->wg_self[l], {dsum, dqkv}));
   }
   return GNOT_OK;
@@ -2221,7 +2270,17 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   for (int i = 0; i < p->I; ++i) GNOT_RUN(chain_fwd(cf, p->ch_fn(i), p->P_("fnenc" + std::to_string(i)), D));
   // key/value projections (model.py:67-75) and states (model.py:77-79) of every (block, input
   // function): they depend only on the input-function encodings, so all L*I of them run batched here
+  // one normalisation of the rows an attention call reads (pre-norm): src [rows, D] -> dst, rstd kept in training
+  auto norm_fwd = [&](Ctx& cc, const float* src, long rows, const std::string& dst, const std::string& rstd) -> int {
+    GNOT_CK(launch_layer_norm(src, D, rows, p->Dr, p->norm_eps, p->P_(dst), D, tr ? p->P_(rstd) : nullptr, cc.s));
+    return GNOT_OK;
+  };
   if (p->I > 0 && p->L > 0) {
+    if (p->pre_norm)
+      for (int i = 0; i < p->I; ++i) {
+        const std::string si = std::to_string(i);
+        GNOT_RUN(norm_fwd(cf, p->P_("fnenc" + si), p->Q[i], "fnn" + si, "fnr" + si));
+      }
     GNOT_CK(launch_linear_batch(p->d_fwd_kv_jobs, (int)p->fwd_kv_jobs.size(), (int)p->Qmax(), 2 * D,
                                 D > 512 ? D / 2 : D, p->dh, cf.s));
     GNOT_RUN(run_state(cf, p->st_fn));
@@ -2235,12 +2294,23 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   for (int l = 0; l < p->L; ++l) {
     const std::string s = "b" + std::to_string(l) + ".";
     const float* qin = p->P_(p->block_query(l));
-    GNOT_RUN(attn_forward(c, l, true, qin, p->P_(s + "cres"), p->P_(s + "a")));
+    // pre-norm: the attention calls read LN(query) / LN(query1); the residual adds below keep the raw rows
+    const float* q_c = qin;
+    const float* q_s = p->P_(s + "query1");
+    if (p->pre_norm) {
+      GNOT_RUN(norm_fwd(c, qin, P, p->norm_buf(l, true), p->norm_rstd(l, true)));
+      q_c = p->P_(p->norm_buf(l, true));
+    }
+    GNOT_RUN(attn_forward(c, l, true, q_c, p->P_(s + "cres"), p->P_(s + "a")));
     // ffn1 experts: query1 = query + sum_e s_e ffn1_e(a)   (model.py:128-131)
     const bool keep = tr && !p->moe_recompute;   // recompute: the backward re-runs the call into "mrsave"
     const Chain &m1 = p->ch_moe(l, true), &m2 = p->ch_moe(l, false);
     GNOT_RUN(moe_forward(c, m1, qin, p->P_(s + "query1"), keep ? p->P_(m1.save) : nullptr));
-    GNOT_RUN(attn_forward(c, l, false, p->P_(s + "query1"), p->P_(s + "sres"), p->P_(s + "bb")));
+    if (p->pre_norm) {
+      GNOT_RUN(norm_fwd(c, q_s, P, p->norm_buf(l, false), p->norm_rstd(l, false)));
+      q_s = p->P_(p->norm_buf(l, false));
+    }
+    GNOT_RUN(attn_forward(c, l, false, q_s, p->P_(s + "sres"), p->P_(s + "bb")));
     // ffn2 experts: query2 = query1 + sum_e s_e ffn2_e(bb)   (model.py:134-137)
     GNOT_RUN(moe_forward(c, m2, p->P_(s + "query1"), p->P_(s + "query2"), keep ? p->P_(m2.save) : nullptr));
   }
@@ -2360,6 +2430,14 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
     for (size_t k = 0; k < p->d_dfn_jobs.size(); ++k)
       GNOT_CK(launch_linear_batch(p->d_dfn_jobs[k], p->I, (int)p->Qmax(), D, D > 512 ? D / 2 : D, p->dh, cf.s));
     GNOT_RUN(run_wgrad_side(cf, p->wg_fnkv, {}));
+    // pre-norm: dfn{i} is so far the gradient of the normalised encodings; pulled through the norm in place
+    // (a row is read whole before it is written) before the encoder's chain backward reads it
+    if (p->pre_norm)
+      for (int i = 0; i < p->I; ++i) {
+        const std::string si = std::to_string(i);
+        float* dfn = p->P_("dfn" + si);
+        GNOT_CK(launch_layer_norm_bwd(p->P_("fnn" + si), D, p->P_("fnr" + si), dfn, D, p->Q[i], p->Dr, dfn, D, 0, cf.s));
+      }
   }
   if (p->I > 0 && p->L == 0)   // encodings unused by the output: zero gradients
     for (int i = 0; i < p->I; ++i)
@@ -2735,6 +2813,46 @@ extern "C" int gnot_fourier_embed_bwd(const float* emb, int64_t ld, const float*
     return fail(GNOT_E_INVALID, "fourier_embed_bwd: a row pitch is less than C (4 n + 3)");
   if (CW >= (1LL << 31)) return fail(GNOT_E_INVALID, "fourier_embed_bwd: C (4 n + 3) must be below 2^31");
   GNOT_CK(launch_fourier_embed_bwd(emb, ld, g, ldg, g2, ldg2, C, n, dv, rows, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+// what both LayerNorm entries refuse about one [rows, ld] array of C real columns
+static const char* norm_array_error(const void* ptr, int64_t ld, int C) {
+  if (ld < C) return "a row pitch is less than C";
+  if (ld % 4 != 0) return "a row pitch is not a multiple of 4";
+  if (ld >= (1LL << 31)) return "a row pitch must be below 2^31";
+  if (reinterpret_cast<uintptr_t>(ptr) & 15) return "pointers must be 16-byte aligned";
+  return nullptr;
+}
+static const char* norm_shape_error(int64_t rows, int C) {
+  if (rows < 1 || rows >= (1LL << 31)) return "rows must be in [1, 2^31)";
+  if (C < 1 || C > 1024) return "C must be in [1, 1024]";
+  return nullptr;
+}
+
+extern "C" int gnot_layer_norm(const float* x, int64_t ldx, int64_t rows, int C, float eps, float* y, int64_t ldy,
+                               float* rstd, void* stream) {
+  if (!x || !y) return fail(GNOT_E_INVALID, "layer_norm: null pointer");
+  const char* e = norm_shape_error(rows, C);
+  if (!e) e = norm_array_error(x, ldx, C);
+  if (!e) e = norm_array_error(y, ldy, C);
+  if (!e && (reinterpret_cast<uintptr_t>(rstd) & 15)) e = "pointers must be 16-byte aligned";
+  if (!e && (!std::isfinite(eps) || !(eps > 0.f))) e = "eps must be finite and positive";
+  if (e) return fail(GNOT_E_INVALID, std::string("layer_norm: ") + e);
+  GNOT_CK(launch_layer_norm(x, ldx, rows, C, eps, y, ldy, rstd, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_layer_norm_bwd(const float* y, int64_t ldy, const float* rstd, const float* dy, int64_t lddy,
+                                   int64_t rows, int C, float* dx, int64_t lddx, int accumulate, void* stream) {
+  if (!y || !rstd || !dy || !dx) return fail(GNOT_E_INVALID, "layer_norm_bwd: null pointer");
+  const char* e = norm_shape_error(rows, C);
+  if (!e) e = norm_array_error(y, ldy, C);
+  if (!e) e = norm_array_error(dy, lddy, C);
+  if (!e) e = norm_array_error(dx, lddx, C);
+  if (!e && (reinterpret_cast<uintptr_t>(rstd) & 15)) e = "pointers must be 16-byte aligned";
+  if (e) return fail(GNOT_E_INVALID, std::string("layer_norm_bwd: ") + e);
+  GNOT_CK(launch_layer_norm_bwd(y, ldy, rstd, dy, lddy, rows, C, dx, lddx, accumulate, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

@@ -328,6 +328,15 @@ hipError_t launch_fourier_embed(const float* src, long lds, int C, int n, float*
                                 hipStream_t s);
 hipError_t launch_fourier_embed_bwd(const float* emb, long ld, const float* ga, long ldga, const float* gb, long ldgb,
                                     int C, int n, float* dv, long rows, hipStream_t s);
+// Parameter-free LayerNorm over the C <= 1024 real columns of a row (norm.hip), one wave per row.  Forward:
+// y[r, :C] = (x[r, :C] - mean) / sqrtf(var + eps), columns C .. ldy - 1 zeros, input pad columns masked, rstd [rows]
+// kept unless null.  Backward from the saved y and rstd: dx = rstd (dy - mean(dy) - y mean(dy y)), stored (pad
+// columns zeros) or, accumulate != 0, added onto dx (pad columns untouched); dx may alias dy.  Pitches: multiples
+// of 4 that are at least C, below 2^31; pointers 16-byte aligned
+hipError_t launch_layer_norm(const float* x, long ldx, long rows, int C, float eps, float* y, long ldy, float* rstd,
+                             hipStream_t s);
+hipError_t launch_layer_norm_bwd(const float* y, long ldy, const float* rstd, const float* dy, long lddy, long rows,
+                                 int C, float* dx, long lddx, int accumulate, hipStream_t s);
 // test hook: y = gelu(x), dy = gelu_grad(x), (y2, dy2) = gelu_and_grad(x) over n contiguous floats
 hipError_t launch_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, long n, hipStream_t s);
 // segmented copy: dst[seg.dst + i] = src[seg.src + i], i < seg.len (floats); reverse swaps the roles of

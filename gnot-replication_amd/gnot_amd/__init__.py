@@ -10,7 +10,8 @@ global-norm gradient clipping, `OneCycle`, `fit`), datasets, loaders and unit-Ga
 (`Normalizer`, `DeviceDataset`, `DeviceLoader`) in `gnot_amd.data`, and the multi-GPU glue in
 `gnot_amd.parallel`.  `GNOT(..., x_fourier=n, fn_fourier=n)` embeds x and the input functions in multi-scale
 Fourier features inside the model (`gnot_amd.fourier`: `fourier_features` is the same map in plain torch,
-`fourier_embed` the library's kernel).
+`fourier_embed` the library's kernel).  `GNOT(..., pre_norm=True)` normalises the inputs of every attention call
+with a parameter-free LayerNorm (`gnot_amd.norm` holds the two row kernels' wrappers).
 """
 from .model import GNOT, MLP, LinearAttention, HeterogeneousNormalizedAttentionBlock  # noqa: F401
 from . import _lib  # noqa: F401

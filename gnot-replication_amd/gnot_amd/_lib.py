@@ -36,7 +36,7 @@ EXPORTS = [
     "gnot_ema_update", "gnot_adamw_step_ema", "gnot_gather_rows", "gnot_debug_gelu",
     "gnot_channel_stats_work_floats", "gnot_channel_stats", "gnot_gather_rows_affine", "gnot_rel_l2_loss_affine",
     "gnot_mse_loss_affine", "gnot_plan_set_fourier", "gnot_fourier_embed", "gnot_fourier_embed_bwd",
-    "gnot_debug_kernel_forms",
+    "gnot_debug_kernel_forms", "gnot_plan_set_pre_norm", "gnot_layer_norm", "gnot_layer_norm_bwd",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -67,7 +67,7 @@ def build(jobs=8, quiet=True):
 # every file the library's code depends on (csrc/Makefile's SRCS, its headers and its flags)
 SOURCES = ["Makefile", "gnot_common.h", "gnot_kernels.h", "x6_core.h", "pack.hip", "linear.hip", "linear2.hip",
            "chain.hip", "chain2.hip", "chainw.hip", "wgrad.hip", "state.hip", "attn.hip", "attn_mfma.hip", "misc.hip",
-           "fourier.hip", "train.hip", "gather.hip", "stats.hip", "engine.cpp", "tuning.cpp"]
+           "fourier.hip", "norm.hip", "train.hip", "gather.hip", "stats.hip", "engine.cpp", "tuning.cpp"]
 
 
 def source_hash():
@@ -147,6 +147,9 @@ def _declare(lib):
     lib.gnot_plan_set_fourier.argtypes = [P, i32, i32]
     lib.gnot_fourier_embed.argtypes = [P, i64, i32, i32, P, i64, P]
     lib.gnot_fourier_embed_bwd.argtypes = [P, i64, P, i64, P, i64, i64, i32, i32, P, P]
+    lib.gnot_plan_set_pre_norm.argtypes = [P, i32, ctypes.c_float]
+    lib.gnot_layer_norm.argtypes = [P, i64, i64, i32, ctypes.c_float, P, i64, P, P]
+    lib.gnot_layer_norm_bwd.argtypes = [P, i64, P, P, i64, i64, i32, P, i64, i32, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p

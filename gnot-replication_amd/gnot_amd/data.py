@@ -335,7 +335,8 @@ class Normalizer:
 
     def fold(self, state_dict, n_mlp_num_layers, dtype=torch.float32):
         """A new state dict (the model and `state_dict` are left alone) whose network takes raw inputs and
-        returns physical outputs, with the reference's keys and nothing else:
+        returns physical outputs, with the keys of `state_dict` (the reference's; every entry the fold does not
+        name, such as a pre-norm model's `pre_norm_eps` buffer, is copied as it is):
           first Linear of each encoder, W' = W diag(r), b' = b - W' m, with (m, r) = (mean, rstd) of
             x.layers.0                     the x and theta blocks concatenated (the encoder's input is [x, theta])
             gating.layers.0                the x block

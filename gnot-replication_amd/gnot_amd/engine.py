@@ -17,11 +17,11 @@ def _ptr_array(ptrs):
 
 
 class Engine:
-    def __init__(self, cfg: dict, linears, fourier=(0, 0)):
+    def __init__(self, cfg: dict, linears, fourier=(0, 0), pre_norm=None):
         """cfg: the 12 constructor arguments (the gnot_config: with a Fourier embedding input_dim and
         input_func_dim are the embedded widths, the Linears'); linears: nn.Linear modules in state_dict order;
         fourier: the orders (x, input functions) of gnot_plan_set_fourier -- the caller's x, the input functions
-        and their gradients then have the raw widths."""
+        and their gradients then have the raw widths; pre_norm: the eps of gnot_plan_set_pre_norm (None: off)."""
         self.lib = _lib.load()
         c = _lib.GnotConfig(**cfg)
         plan = ctypes.c_void_p()
@@ -29,6 +29,9 @@ class Engine:
         self.plan = plan
         if any(fourier):           # the default model issues the calls it always did
             _lib.check(self.lib.gnot_plan_set_fourier(plan, int(fourier[0]), int(fourier[1])))
+        self.pre_norm = None if pre_norm is None else float(pre_norm)
+        if self.pre_norm is not None:
+            _lib.check(self.lib.gnot_plan_set_pre_norm(plan, 1, self.pre_norm))
         n = self.lib.gnot_plan_num_linears(plan)
         dims = (ctypes.c_int32 * (2 * n))()
         _lib.check(self.lib.gnot_plan_linear_dims(plan, dims))

@@ -144,13 +144,22 @@ class GNOT(nn.Module):
 
     def __init__(self, input_dim, theta_dim, input_func_dim, out_dim, n_attn_layers, n_attn_hidden_dim,
                  n_mlp_num_layers, n_mlp_hidden_dim, n_input_hidden_dim, n_expert, n_head, n_input_functions=0, *,
-                 x_fourier=0, fn_fourier=0):
+                 x_fourier=0, fn_fourier=0, pre_norm=False):
         """The reference's 12 arguments, then (keyword only, no reference counterpart) the orders of the
         Fourier embedding of x and of the input functions (gnot_amd.fourier; 0: none).  input_dim and
         input_func_dim stay the widths of the caller's tensors; with an order n the first Linears take
         4 n + 3 columns per channel, and the module is the reference GNOT of those embedded widths applied to
         fourier_features(x, x_fourier), the raw theta and fourier_features(fn_i, fn_fourier): its state_dict
-        has that model's keys, shapes and order and nothing else."""
+        has that model's keys, shapes and order and nothing else.
+        pre_norm (keyword only; the original GNOT code's LayerNorms, which the reference dropped): the attention
+        calls read F.layer_norm(h, (d,), eps=1e-5) of their inputs, without gamma / beta (in front of a Linear
+        they fold into it) --
+            query1 = query  + sum_e s_e ffn1_e(cross_attention(LN(query), [LN(enc_i)]))
+            query2 = query1 + sum_e s_e ffn2_e(self_attention(LN(query1)))
+        with the residual stream, gating, encoders and decoder unchanged (gnot_plan_set_pre_norm).  The
+        parameters are the reference's; the state_dict gains one buffer, `pre_norm_eps`, so that a pre-norm
+        checkpoint and a model without the option (or the reference) refuse each other on that key instead of
+        computing another function."""
         super().__init__()
         nx = check_order(x_fourier, "x_fourier")
         nf = check_order(fn_fourier, "fn_fourier")
@@ -175,6 +184,9 @@ class GNOT(nn.Module):
                          n_input_functions=n_input_functions)
         self._plan_cfg = dict(self._cfg, input_dim=input_dim, input_func_dim=input_func_dim)
         self.x_fourier, self.fn_fourier = nx, nf
+        self.pre_norm = bool(pre_norm)
+        if self.pre_norm:
+            self.register_buffer("pre_norm_eps", torch.tensor(1e-5, dtype=torch.float32))
         if nx or nf:
             # widths that do not fit the hidden width are refused here, with the engine's message (host only)
             _lib.probe_plan(self._plan_cfg, nx, nf)
@@ -198,7 +210,8 @@ class GNOT(nn.Module):
         return out + self.out.linears()
 
     def _new_engine(self):
-        e = Engine(self._plan_cfg, self.linears(), fourier=(self.x_fourier, self.fn_fourier))
+        e = Engine(self._plan_cfg, self.linears(), fourier=(self.x_fourier, self.fn_fourier),
+                   pre_norm=float(self.pre_norm_eps) if self.pre_norm else None)
         e.comm = self._comm
         e.grad_comm = self._grad_comm
         e.moe_recompute = self._moe_recompute

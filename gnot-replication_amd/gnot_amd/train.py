@@ -405,7 +405,8 @@ def save_checkpoint(model, path, normalizer=None):
     """torch.save(model.state_dict()) exactly as main.py:151 (reference-compatible keys/shapes).
     normalizer: the model was trained on normalised data; the statistics are folded into its first and last
     Linears (Normalizer.fold), so the file predicts physical outputs from raw inputs -- in gnot_amd.GNOT and in
-    the reference module alike -- and holds the reference's keys and nothing else.  Statistics of a block the
+    the reference module alike -- and holds the reference's keys and nothing else (a GNOT(pre_norm=True) adds its
+    one buffer, pre_norm_eps, which only a model with the option loads).  Statistics of a block the
     model embeds in Fourier features cannot be folded: ValueError unless that block is the identity (_foldable)."""
     sd = model.state_dict()
     torch.save(sd if normalizer is None else _foldable(model, normalizer).fold(sd, model._cfg["n_mlp_num_layers"]),

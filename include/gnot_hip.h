@@ -130,6 +130,24 @@ int gnot_plan_set_precision(gnot_plan* plan, int bf16);
  * (set_batch + bind again). */
 int gnot_plan_set_fourier(gnot_plan* plan, int nx, int nf);
 
+/* Parameter-free pre-norm of the attention inputs (the original GNOT code's LayerNorms ln1 .. ln5, which the
+ * replicated model.py dropped; no gamma / beta: in front of a Linear they fold into its W and b, so the
+ * parameter list, the gradient arena and every checkpoint key stay the reference's).  With on != 0 and
+ * LN(h) = (h - mean) / sqrtf(var + eps) over the n_attn_hidden_dim real features of a row (biased variance),
+ * a block (model.py:126-139) becomes
+ *     query1 = query  + sum_e s_e ffn1_e( cross_attention(LN(query),  [LN(enc_i)]) )
+ *     query2 = query1 + sum_e s_e ffn2_e( self_attention (LN(query1)) )
+ * Without input functions cross attention takes LN(query) as query and as key/value source (model.py:88-104).
+ * LN(enc_i) has no parameters and is computed once per input function for every block.  The residual stream,
+ * the gating, the encoders, the decoder and the softmaxed-q residual inside the attention are unchanged.  The
+ * backward pulls the projections' input gradients through the norm from the saved rows and their rstd (no
+ * statistics recomputed); every mode of the plan (sharding, MoE recompute, bf16 arithmetic -- the norm stays
+ * fp32 --, gradient accumulation, graph capture) works as without it.  gnot_debug_buffer names: "b{l}.n1",
+ * "b{l}.n2" [P, D], "fnn{i}" [Q_i, D], and in training "b{l}.r1", "b{l}.r2", "fnr{i}" (rstd per row), "dnorm".
+ * eps must be finite and positive (GNOT_E_INVALID otherwise; 1e-5 is torch's default).  Call after
+ * gnot_plan_create and before gnot_plan_set_batch; a change invalidates the batch (set_batch + bind again). */
+int gnot_plan_set_pre_norm(gnot_plan* plan, int on, float eps);
+
 /* Input gradients (off by default).  The reference's autograd also differentiates w.r.t. x, theta and
  * the input functions when they require grad (model.py:154-173: x feeds the gating MLP and, through
  * torch.cat with the broadcast theta, the query encoder; the input functions feed their encoder
@@ -195,6 +213,25 @@ int gnot_forward(gnot_plan* plan, const float* x, const float* theta, const floa
 int gnot_fourier_embed(const float* src, int64_t rows, int C, int n, float* dst, int64_t ld, void* stream);
 int gnot_fourier_embed_bwd(const float* emb, int64_t ld, const float* g, int64_t ldg, const float* g2, int64_t ldg2,
                            int64_t rows, int C, int n, float* dv, void* stream);
+
+/* The row kernels of gnot_plan_set_pre_norm on their own, for row-by-row tests (no plan; one launch on
+ * `stream`; fp32 device pointers; one wave per row, the row in registers, every row sum in one fixed order, so
+ * a row's bits do not depend on the call it is part of).
+ * gnot_layer_norm: y[r, :C] = (x[r, :C] - mean) * rstd, rstd = 1 / sqrtf(var + eps), var the biased variance
+ * summed from (x - mean)^2, the mean kept as two floats hi + lo with lo = mean(x - hi), so that a common offset
+ * of the row costs y and rstd nothing and a constant row gives exact zeros;
+ * columns C .. ldy - 1 of y are written as exact zeros, columns C .. ldx - 1 of x are ignored (not assumed
+ * zero); rstd [rows] is written unless null.
+ * gnot_layer_norm_bwd: dx = rstd (dy - mean_C(dy) - y mean_C(dy y)) from the y and rstd the forward wrote;
+ * accumulate == 0 stores it (columns C .. lddx - 1 as zeros), otherwise it is added onto dx, one rounded add
+ * per element (pad columns untouched).  dx may alias dy.
+ * GNOT_E_INVALID before any launch for a null pointer (rstd may be null in the forward), rows outside
+ * [1, 2^31), C outside [1, 1024], a row pitch below C, not a multiple of 4 or not below 2^31, a pointer that is
+ * not 16-byte aligned, or an eps that is not finite and positive. */
+int gnot_layer_norm(const float* x, int64_t ldx, int64_t rows, int C, float eps, float* y, int64_t ldy, float* rstd,
+                    void* stream);
+int gnot_layer_norm_bwd(const float* y, int64_t ldy, const float* rstd, const float* dy, int64_t lddy, int64_t rows,
+                        int C, float* dx, int64_t lddx, int accumulate, void* stream);
 
 /* Backward of the last gnot_forward: dout [P, out_dim] -> every parameter gradient, written
  * (overwritten) into the gradient arena.  The same as gnot_backward_ex(plan, dout, 0, stream). */

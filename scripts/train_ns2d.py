@@ -8,6 +8,7 @@ trains on K randomly chosen points of every mesh per step.  --normalize trains o
 targets (statistics of the training set, computed on the device) and writes a checkpoint that takes raw inputs.
 --x-fourier N / --fn-fourier N embed the coordinates / the input functions in multi-scale Fourier features of
 order N inside the model (the original GNOT code's horiz_fourier_dim), behind the normalisation.
+--pre-norm normalises the attention inputs (a parameter-free LayerNorm, the original GNOT code's ln1 .. ln5).
 
     python scripts/train_ns2d.py --train train.pkl --test test.pkl [--epochs 100 ...]
     python scripts/train_ns2d.py --synthetic 64 --epochs 2          # generated meshes, same format
@@ -79,6 +80,9 @@ def main():
                          "(4 N + 3 columns per channel, N up to 8; default 0: raw coordinates)")
     ap.add_argument("--fn-fourier", type=int, default=0, metavar="N",
                     help="the same embedding for every input function's channels (default 0)")
+    ap.add_argument("--pre-norm", action="store_true",
+                    help="LayerNorm (no gamma / beta, eps 1e-5) on the inputs of every attention call; the "
+                         "checkpoint then has one more key, pre_norm_eps, and loads only into GNOT(pre_norm=True)")
     args = ap.parse_args()
     norm = None if args.normalize is None else set(filter(None, args.normalize.split(",")))
     if norm is not None and (not norm or norm - {"x", "theta", "fns", "y"}):
@@ -99,7 +103,8 @@ def main():
     dev = torch.device("cuda", args.gpu_id)
     model = GNOT(x0.shape[1], len(np.atleast_1d(th0)), f0[0].shape[1], y0.shape[1], args.n_attn_layers,
                  args.n_attn_hidden_dim, args.n_mlp_num_layers, args.n_mlp_hidden_dim, args.n_input_hidden_dim,
-                 args.n_expert, args.n_head, len(f0), x_fourier=args.x_fourier, fn_fourier=args.fn_fourier).to(dev)
+                 args.n_expert, args.n_head, len(f0), x_fourier=args.x_fourier, fn_fourier=args.fn_fourier,
+                 pre_norm=args.pre_norm).to(dev)
     dl = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=args.batch, shuffle=sh,
                                                     collate_fn=data.collate_packed if args.packed
                                                     else data.collate_padded)
