@@ -250,6 +250,17 @@ __global__ void __launch_bounds__(256) pgemm_x6_kernel(const WgradJob* __restric
 //   MFMA:    wave (wr, wc) computes rows [128 wr, +128) x cols [64 wc, +64): 4 x 2 blocks, six order <= 2
 //            piece products each (smallest first), one accumulator per block.
 // Double-buffered fragment images: stage s+1 is split into the other buffer while stage s is multiplied.
+//   stagger: (TW = 256, NP = 3, the interleaved loops) every wave runs the same iteration between two barriers --
+//            row hand-over (counted wait, 16 ds_read_b32 of its raw slot, 4 LDS-DMAs), 8 MFMA groups with one
+//            point's staging after each, 6 LDS stores -- so the two waves of a SIMD (w and w + 4) would stand in
+//            the hand-over together with the matrix pipe idle, and reach the staging-heavy tail together.  Waves
+//            4 .. 7 take a second ordering of the same iteration: MFMA groups 0 .. kWStagger - 1 bare, then the
+//            hand-over, then the other groups with all eight points' staging.  One partner's hand-over then
+//            falls beside the other's MFMAs.  Same MFMAs and column-sum adds in the same order per accumulator,
+//            same vector-memory order per wave (every counted vmcnt keeps its number): the results are bit
+//            for bit those of the single ordering.  Neither loop holds a scratch instruction (the kernel's 38 /
+//            41 spilled registers are stored in front of the stage loops and reloaded behind them).
+//            Measured (profiles/LOG.md, "Wave stagger"): -2.2 .. -3.5 % per launch at configs[2]'s size.
 // Partials go to the same slab layout as the 128-tile kernel's.
 // TW = 128 (round 5): the same kernel at d <= 128 (configs[1]) with a 128 x 128 output per workgroup and 4
 // waves (one 64 x 64 quadrant each, 2 x 2 blocks), in place of the 128-tile kernel above, whose staging and
@@ -265,6 +276,24 @@ constexpr int kWRawSlots = 2;
 // LDS: two fragment buffers | waves x 2 raw slots (96 + 64 = 160 KiB at NP = 3, TW = 256; 48 + 32 at 128)
 constexpr size_t w_lds_bytes(int np, int tw = 256) {
   return (2 * (size_t)w_buf(np, tw) + (size_t)(tw / 32) * kWRawSlots * kWRawSlot) * 16;
+}
+
+// MFMA groups (of the 8 per stage) that the late waves of the TW = 256, NP = 3 kernel run before their row
+// hand-over (the kernel's header comment, `stagger`); a diagnostic build may move it (EXTRA=-DGNOT_WSTAGGER=k,
+// 1 <= k <= 7)
+#ifndef GNOT_WSTAGGER
+#define GNOT_WSTAGGER 4
+#endif
+constexpr int kWStagger = GNOT_WSTAGGER;
+static_assert(kWStagger >= 1 && kWStagger <= 7, "the late waves stage all 8 points in the groups that are left");
+
+// f(integral_constant<int, i>) for i = I .. N-1, in order: a loop whose index is a constant expression
+template <int I, int N, class F>
+GNOT_DEV void w_unroll(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    w_unroll<I + 1, N>(f);
+  }
 }
 
 // one dword of a wave-private raw slot (inline asm: the compiler does not order it against the LDS-DMA
@@ -468,7 +497,10 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
     int buf = 0;
     // MASK: columns past out / in exist (the fa / fb selects); jobs with out = in = 256 skip them
     // SC: scaled job, sc = the scales of the 8 points being staged (scale_load's register)
-    auto fused = [&](int b, auto GEL, auto MASK, auto SC, float sc) {
+    // LATE: the ordering of the SIMD partner waves NW/2 .. NW-1 (run() below); `head` is the iteration's
+    // row hand-over (counted wait, raw_read, scale request, raw_dma), issued here after MFMA group
+    // kWStagger - 1 instead of in front of fused()
+    auto fused = [&](int b, auto GEL, auto MASK, auto SC, auto LATE, float sc, auto&& head) {
       const u32x4* A = wl + b * w_buf(NP, TW);
       const u32x4* Bm = A + NP * kWPiece;
       u32x4 bf[2][NP], af[2][NP], pa[NP], pq[NP];
@@ -498,25 +530,35 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
           for (int q = 0; q < NP; ++q) asm volatile("" : "+v"(pa[q][k >> 1]), "+v"(pq[q][k >> 1]));
         }
       };
-      // 2 RB MFMA groups per stage and 8 points to stage: 8 / (2 RB) points after each group
-      constexpr int CPG = 8 / (2 * RB);
+      // NG = 2 RB MFMA groups per stage and 8 points to stage: 8 / NG points after each group; the late
+      // ordering leaves its first KS groups bare and spreads the 8 points over the other NG - KS
+      constexpr int NG = 2 * RB;
+      constexpr int KS = decltype(LATE)::value ? kWStagger : 0;
+      auto chunks = [&](auto G) __attribute__((always_inline)) {
+        constexpr int g = decltype(G)::value;
+        if constexpr (g >= KS) {
+          constexpr int k0 = 8 * (g - KS) / (NG - KS), k1 = 8 * (g - KS + 1) / (NG - KS);
 #pragma unroll
-      for (int ib = 0; ib < RB; ++ib) {
+          for (int k = k0; k < k1; ++k) chunk(k);
+        }
+      };
+      w_unroll<0, RB>([&](auto IB) __attribute__((always_inline)) {
+        constexpr int ib = decltype(IB)::value;
+        if constexpr (decltype(LATE)::value && 2 * ib == KS) head();
         if (ib + 1 < RB) {
 #pragma unroll
           for (int q = 0; q < NP; ++q) af[(ib + 1) & 1][q] = A[q * kWPiece + (wr * RB + ib + 1) * 64 + lane];
         }
         mfma_np<NP>(af[ib & 1], bf[0], acc[ib][0]);
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < CPG; ++k) chunk(CPG * 2 * ib + k);
+        chunks(std::integral_constant<int, 2 * ib>{});
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (decltype(LATE)::value && 2 * ib + 1 == KS) head();
         mfma_np<NP>(af[ib & 1], bf[1], acc[ib][1]);
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < CPG; ++k) chunk(CPG * (2 * ib + 1) + k);
+        chunks(std::integral_constant<int, 2 * ib + 1>{});
         __builtin_amdgcn_sched_barrier(0);
-      }
+      });
       u32x4* base = wl + (b ^ 1) * w_buf(NP, TW);
 #pragma unroll
       for (int q = 0; q < NP; ++q) {
@@ -530,22 +572,39 @@ __global__ void __launch_bounds__(w_threads(TW)) pgemm_x6w_kernel(const WgradJob
     // that leaves those four DMAs in flight retires them with stage s + 2's rows.  That wait stands at the END
     // of the iteration (the same place in time as the top of the next): it names the loaded register, so
     // whatever the compiler does with the value for the next iteration comes after it
+    // stagger: the late waves run the hand-over (`head`) after MFMA group kWStagger - 1 of the iteration, in
+    // the same order, so a wave's vector-memory ops keep their sequence (scales s + 2, rows s + 3) and every
+    // counted wait its number: the head's vmcnt(4) still leaves stage s + 2's four DMAs in flight, and the
+    // scaled form's end-of-iteration vmcnt(4), which names scn, still leaves stage s + 3's behind stage
+    // s + 2's scales (for a late wave those were requested half an iteration later than for an early one)
     auto run = [&](auto GEL, auto MASK, auto SC) {
       float scn = 0.f;
       if (decltype(SC)::value) {
         scn = scale_load(1);
         c2_wait_vm<4>();
       }
-      for (int s = 0; s + 1 < nst; ++s) {
-        const float sc = scn;
-        if (!decltype(SC)::value) c2_wait_vm<4>();
-        raw_read(s + 1);
-        if (decltype(SC)::value) scn = scale_issue(s + 2);
-        raw_dma(s + 3);
-        fused(buf, GEL, MASK, SC, sc);
-        lds_barrier();
-        buf ^= 1;
-        if (decltype(SC)::value) asm volatile("s_waitcnt vmcnt(4)" : "+v"(scn) :: "memory");
+      auto loop = [&](auto LATE) __attribute__((always_inline)) {
+        for (int s = 0; s + 1 < nst; ++s) {
+          const float sc = scn;
+          auto head = [&]() __attribute__((always_inline)) {
+            if (!decltype(SC)::value) c2_wait_vm<4>();
+            raw_read(s + 1);
+            if (decltype(SC)::value) scn = scale_issue(s + 2);
+            raw_dma(s + 3);
+          };
+          if (!decltype(LATE)::value) head();
+          fused(buf, GEL, MASK, SC, LATE, sc, head);
+          lds_barrier();
+          buf ^= 1;
+          if (decltype(SC)::value) asm volatile("s_waitcnt vmcnt(4)" : "+v"(scn) :: "memory");
+        }
+      };
+      // a scalar branch around two straight-line loops (wave is an SGPR)
+      if constexpr (TW == 256 && NP == 3) {
+        if (wave >= NW / 2) loop(std::true_type{});
+        else loop(std::false_type{});
+      } else {
+        loop(std::false_type{});
       }
     };
     // the interleaved form of scaled jobs: whole 256 x 256 gradients of a GELU'd input (a chain's last hidden
