@@ -2681,6 +2681,28 @@ extern "C" int gnot_mse_loss_affine(const float* pred, const float* tgt, const i
   return mse_loss(pred, tgt, off_dev, off_host, B, C, out_stats, work, loss, dpred, stream);
 }
 
+extern "C" size_t gnot_lp_loss_work_floats(const int64_t* off_host, int B, int C) {
+  return gnot_rel_l2_work_floats(off_host, B, C);      // the widest layout of the family: two norms per channel
+}
+
+extern "C" int gnot_lp_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
+                            int B, int C, int kind, const float* comp_weights, const float* out_stats, float* work,
+                            float* loss, float* terms, float* dpred, void* stream) {
+  static_assert(GNOT_LP_REL2 == 0 && GNOT_LP_REL1 == 1 && GNOT_LP_RELINF == 2 && GNOT_LP_MSE == 3 &&
+                GNOT_LP_L1 == 4 && GNOT_LP_LINF == 5, "launch_lp's kinds");
+  if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
+    return fail(GNOT_E_INVALID, "bad lp_loss arguments");
+  if (kind < GNOT_LP_REL2 || kind > GNOT_LP_LINF)
+    return fail(GNOT_E_INVALID, "lp_loss: unknown kind " + std::to_string(kind));
+  if (dpred && (kind == GNOT_LP_RELINF || kind == GNOT_LP_LINF))
+    return fail(GNOT_E_INVALID, "lp_loss: relinf and linf are metrics only: they have no gradient (dpred must be null)");
+  std::vector<long> off(off_host, off_host + B + 1);
+  if (int rc = check_loss_offsets(off, false)) return rc;
+  GNOT_CK(launch_lp(kind, pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
+                    comp_weights, out_stats, work, loss, terms, dpred, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
 extern "C" size_t gnot_grad_clip_work_floats(int64_t n) { return (size_t)grad_clip_partials(n); }
 
 extern "C" int gnot_grad_clip(const float* grad, int64_t n, const float* hyper, float max_norm, float* work,

@@ -357,6 +357,13 @@ hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_de
 // work: B*nsplit*C floats (nsplit = rel_l2_splits); every sample must have at least one row; stats as above
 hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
                       const float* stats, float* work, float* loss, float* dpred, hipStream_t s);
+// the Lp loss family (gnot_lp_loss): kind = GNOT_LP_* (0 rel2, 1 rel1, 2 relinf, 3 mse, 4 l1, 5 linf), checked by the
+// caller; w (C component weights), stats, terms ([B][C], the unweighted terms) and dpred may be null, dpred must be
+// for relinf / linf.  work: B*nsplit*2C + B*C floats (nsplit = rel_l2_splits); every sample has at least one row.
+// rel2 / mse without w and terms launch the kernels of launch_rel_l2 / launch_mse.
+hipError_t launch_lp(int kind, const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
+                     long rows, const float* w, const float* stats, float* work, float* loss, float* terms,
+                     float* dpred, hipStream_t s);
 // stage-1 partial sums of sum g^2 over n elements (a function of n alone); 0 for n < 1
 long grad_clip_partials(long n);
 // work: grad_clip_partials(n) floats; clip: 2 floats {norm, coefficient}

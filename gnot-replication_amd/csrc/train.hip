@@ -19,6 +19,9 @@
 //             (ema_update_kernel); w comes from device memory like the other hyper-parameters.
 //   affine    both losses on a normalised prediction: p' = pred * std[c] + mean[c] against the raw target, and
 //             the gradient scaled by std[c], inside the same passes (Stats of the partial and grad kernels).
+//   lp_*      the named losses of the original GNOT recipe (rel2, rel1, relinf, mse, l1, linf) with component
+//             weights and the per-(sample, channel) terms as an output, in the shape of the rel_l2 passes
+//             (gnot_lp_loss); rel2 / mse without weights are the arithmetic of rel_l2_* / mse_*.
 // adamw, its clipped and guarded forms and the fused average are one kernel, adamw_update_kernel<kEma>.
 #include "gnot_common.h"
 #include "gnot_kernels.h"
@@ -226,6 +229,185 @@ hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, 
                       const float* stats, float* work, float* loss, float* dpred, hipStream_t s) {
   return stats ? launch_mse_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s, stats)
                : launch_mse_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s);
+}
+
+// ---------------------------------------------------------------- Lp losses (gnot_lp_loss)
+// The loss family of the original GNOT recipe in the shape of the passes above: per (sample, channel) a term
+//   e[b, c] = ||d||_p / ||t||_p  (kRel: rel2, rel1, relinf)   or   sum |d|^p / N_b  (mse, l1),  max |d|  (linf),
+// d = p' - t with p' the prediction or its de-normalisation, p = kNorm (2, 1, or 0 for the maximum norm), and
+//   loss = (1/B) sum_b sum_c w^_c e[b, c],  w^_c = w_c / sum_c w_c  (1/C without weights).
+// Without weights the instantiations for rel2 and mse are the arithmetic of the rel_l2_* / mse_* kernels above,
+// operation for operation, so loss and gradient have their bits; the plain forms without weights and terms are
+// not instantiated at all (launch_lp runs the kernels above).  The maximum is taken so that a NaN stays one.
+__device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+// block_sum's tree with nan_max in place of the sum
+__device__ __forceinline__ float block_max(float x, float* red) {
+  red[threadIdx.x] = x;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] = nan_max(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  const float m = red[0];
+  __syncthreads();
+  return m;
+}
+
+// one more element v of a channel's norm: sum v^2, sum |v|, max |v|
+template <int kNorm>
+__device__ __forceinline__ float lp_accumulate(float v, float acc) {
+  if constexpr (kNorm == 2) return fmaf(v, v, acc);
+  else if constexpr (kNorm == 1) return acc + fabsf(v);
+  else return nan_max(acc, fabsf(v));
+}
+
+template <int kNorm>
+__device__ __forceinline__ float lp_block(float x, float* red) {
+  if constexpr (kNorm == 0) return block_max(x, red);
+  else return block_sum(x, red);
+}
+
+// partial[b][split][0..kW C), kW = kRel ? 2 : 1: the norm's sum (or maximum) of d [C] and, kRel, of t [C] over
+// the split's rows of sample b (an empty split: zeros)
+template <int kNorm, bool kRel, typename... Stats>
+__global__ void __launch_bounds__(256) lp_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                         const long* __restrict__ off, int C, int nsplit,
+                                                         float* __restrict__ partial, Stats... stats_arg) {
+  __shared__ float red[256];
+  constexpr int kW = kRel ? 2 : 1;
+  const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
+  const long r0 = off[b] + (long)split * kLossRows;
+  const long r1 = min(off[b + 1], r0 + kLossRows);
+  for (int c = 0; c < C; ++c) {
+    float num = 0.f, den = 0.f;
+    for (long r = r0 + threadIdx.x; r < r1; r += 256) {
+      const float t = tgt[r * C + c];
+      float d;
+      if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[r * C + c], (stats_arg, ...), C, c) - t;
+      else d = pred[r * C + c] - t;
+      num = lp_accumulate<kNorm>(d, num);
+      if constexpr (kRel) den = lp_accumulate<kNorm>(t, den);
+    }
+    num = lp_block<kNorm>(num, red);
+    if constexpr (kRel) den = lp_block<kNorm>(den, red);
+    if (threadIdx.x == 0) {
+      float* P = partial + ((long)b * nsplit + split) * kW * C;
+      P[c] = num;
+      if constexpr (kRel) P[C + c] = den;
+    }
+  }
+}
+
+// one workgroup: the norms per (b, c) in split order, the term e[b, c] (to terms, if asked for), the loss and
+// the per-(b, c) gradient scale s: d loss / d p' = s d (kNorm 2) or s sign(d) (kNorm 1).  w == nullptr: the
+// mean over (sample, channel) as rel_l2_finish_kernel / mse_finish_kernel take it; else w^_c from w[C], summed
+// in index order.
+template <int kNorm, bool kRel>
+__global__ void __launch_bounds__(256) lp_finish_kernel(const float* __restrict__ partial, const long* __restrict__ off,
+                                                        int B, int C, int nsplit, const float* __restrict__ w,
+                                                        float* __restrict__ scale, float* __restrict__ loss,
+                                                        float* __restrict__ terms) {
+  __shared__ float red[256];
+  constexpr int kW = kRel ? 2 : 1;
+  float wsum = 0.f;
+  if (w) for (int c = 0; c < C; ++c) wsum += w[c];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < B * C; i += 256) {
+    const int b = i / C, c = i % C;
+    float num = 0.f, den = 0.f;
+    for (int s = 0; s < nsplit; ++s) {
+      const float* P = partial + ((long)b * nsplit + s) * kW * C;
+      if constexpr (kNorm == 0) num = nan_max(num, P[c]); else num += P[c];
+      if constexpr (kRel) {
+        if constexpr (kNorm == 0) den = nan_max(den, P[C + c]); else den += P[C + c];
+      }
+    }
+    const float n = (float)(off[b + 1] - off[b]);
+    float e;
+    if constexpr (kRel) e = kNorm == 2 ? sqrtf(num / den) : num / den;
+    else e = kNorm == 0 ? num : num / n;
+    if (terms) terms[i] = e;
+    // the mean's factor: 1 / (B C), or w^_c / B
+    const float wc = w ? w[c] / wsum : 1.0f;
+    const float count = w ? (float)B : (float)(B * C);
+    if (w) acc += mul_rn(wc, e); else acc += e;
+    if constexpr (kNorm == 2 && kRel) scale[i] = wc / (count * den * e);
+    else if constexpr (kNorm == 1 && kRel) scale[i] = wc / (count * den);
+    else if constexpr (kNorm == 2) scale[i] = mul_rn(2.0f, wc) / (count * n);
+    else if constexpr (kNorm == 1) scale[i] = wc / (count * n);
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) *loss = acc / (w ? (float)B : (float)(B * C));
+}
+
+// d loss / d pred, elementwise; a channel of weight zero is written as zeros whatever d holds
+template <int kNorm, typename... Stats>
+__global__ void __launch_bounds__(256) lp_grad_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                      const long* __restrict__ off, int B, int C,
+                                                      const float* __restrict__ w, const float* __restrict__ scale,
+                                                      float* __restrict__ dpred, long rows, Stats... stats_arg) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * C) return;
+  const long r = i / C;
+  const int c = (int)(i % C);
+  if (w && w[c] == 0.f) { dpred[i] = 0.f; return; }
+  const float s = scale[sample_of_row(off, B, r) * C + c];
+  float d;
+  if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[i], (stats_arg, ...), C, c) - tgt[i];
+  else d = pred[i] - tgt[i];
+  float g;
+  if constexpr (kNorm == 2) g = d * s;
+  else g = d > 0.f ? s : d < 0.f ? -s : mul_rn(d, 0.f);      // sign(0) = 0; a NaN stays one
+  if constexpr (sizeof...(Stats) == 1) {
+    const float* __restrict__ stats = (stats_arg, ...);
+    dpred[i] = mul_rn(g, stats[C + c]);
+  } else {
+    dpred[i] = g;
+  }
+}
+
+template <int kNorm, bool kRel, typename... Stats>
+static hipError_t launch_lp_t(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
+                              long rows, const float* w, float* work, float* loss, float* terms, float* dpred,
+                              hipStream_t s, Stats... stats) {
+  float* partial = work;                                              // [B][nsplit][kW C]
+  float* scale = work + (size_t)B * nsplit * (kRel ? 2 : 1) * C;      // [B][C]
+  hipLaunchKernelGGL((lp_partial_kernel<kNorm, kRel, Stats...>), dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev,
+                     C, nsplit, partial, stats...);
+  hipLaunchKernelGGL((lp_finish_kernel<kNorm, kRel>), dim3(1), dim3(256), 0, s, (const float*)partial, off_dev, B, C,
+                     nsplit, w, scale, loss, terms);
+  if constexpr (kNorm != 0) {
+    if (dpred && rows > 0)
+      hipLaunchKernelGGL((lp_grad_kernel<kNorm, Stats...>), dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s,
+                         pred, tgt, off_dev, B, C, w, (const float*)scale, dpred, rows, stats...);
+  }
+  return hipGetLastError();
+}
+
+// kind: GNOT_LP_* (gnot_hip.h), checked by the caller, as is dpred == nullptr for the two maximum norms.
+// work: B*nsplit*2C + B*C floats (nsplit = rel_l2_splits); every sample has at least one row.  w, stats, terms,
+// dpred may be null.  rel2 and mse without w and terms: launch_rel_l2 / launch_mse, the same kernels.
+hipError_t launch_lp(int kind, const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
+                     long rows, const float* w, const float* stats, float* work, float* loss, float* terms,
+                     float* dpred, hipStream_t s) {
+  if (!w && !terms && kind == 0) return launch_rel_l2(pred, tgt, off_dev, B, C, nsplit, rows, stats, work, loss, dpred, s);
+  if (!w && !terms && kind == 3) return launch_mse(pred, tgt, off_dev, B, C, nsplit, rows, stats, work, loss, dpred, s);
+#define GNOT_LP_CASE(K, NORM, REL)                                                                                   \
+  case K:                                                                                                            \
+    return stats ? launch_lp_t<NORM, REL>(pred, tgt, off_dev, B, C, nsplit, rows, w, work, loss, terms, dpred, s,    \
+                                          stats)                                                                     \
+                 : launch_lp_t<NORM, REL>(pred, tgt, off_dev, B, C, nsplit, rows, w, work, loss, terms, dpred, s);
+  switch (kind) {
+    GNOT_LP_CASE(0, 2, true)
+    GNOT_LP_CASE(1, 1, true)
+    GNOT_LP_CASE(2, 0, true)
+    GNOT_LP_CASE(3, 2, false)
+    GNOT_LP_CASE(4, 1, false)
+    GNOT_LP_CASE(5, 0, false)
+  }
+#undef GNOT_LP_CASE
+  return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------- global gradient norm and clip coefficient

@@ -5,7 +5,8 @@
                  n_mlp_num_layers, n_mlp_hidden_dim, n_input_hidden_dim, n_expert, n_head,
                  n_input_functions).cuda()
 
-The training step around it lives in `gnot_amd.train` (`RelL2Loss`, `MSELoss`, `FlatAdamW` with optional
+The training step around it lives in `gnot_amd.train` (`RelL2Loss`, `MSELoss`, `LpLoss` -- the rel2 / rel1 / relinf /
+mse / l1 / linf family with component weights -- `evaluate_table` for per-sample errors, `FlatAdamW` with optional
 global-norm gradient clipping, `OneCycle`, `fit`), datasets, loaders and unit-Gaussian normalisation
 (`Normalizer`, `DeviceDataset`, `DeviceLoader`) in `gnot_amd.data`, and the multi-GPU glue in
 `gnot_amd.parallel`.  `GNOT(..., x_fourier=n, fn_fourier=n)` embeds x and the input functions in multi-scale
@@ -17,6 +18,7 @@ from .model import GNOT, MLP, LinearAttention, HeterogeneousNormalizedAttentionB
 from . import _lib  # noqa: F401
 from .data import Normalizer  # noqa: F401
 from .fourier import fourier_embed, fourier_features  # noqa: F401
+from .train import LpLoss, evaluate_table  # noqa: F401
 
 __all__ = ["GNOT", "MLP", "LinearAttention", "HeterogeneousNormalizedAttentionBlock", "Normalizer",
-           "fourier_features", "fourier_embed"]
+           "fourier_features", "fourier_embed", "LpLoss", "evaluate_table"]

@@ -37,6 +37,7 @@ EXPORTS = [
     "gnot_channel_stats_work_floats", "gnot_channel_stats", "gnot_gather_rows_affine", "gnot_rel_l2_loss_affine",
     "gnot_mse_loss_affine", "gnot_plan_set_fourier", "gnot_fourier_embed", "gnot_fourier_embed_bwd",
     "gnot_debug_kernel_forms", "gnot_plan_set_pre_norm", "gnot_layer_norm", "gnot_layer_norm_bwd",
+    "gnot_lp_loss_work_floats", "gnot_lp_loss",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -44,6 +45,9 @@ EXPORTS = [
 # gnot_backward_ex flags (include/gnot_hip.h)
 BWD_ACCUMULATE = 1
 BWD_SKIP_GRAD_COMM = 2
+
+# gnot_lp_loss kinds (include/gnot_hip.h GNOT_LP_*)
+LP_KINDS = {"rel2": 0, "rel1": 1, "relinf": 2, "mse": 3, "l1": 4, "linf": 5}
 
 # gnot_comm callbacks (include/gnot_hip.h)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
@@ -150,6 +154,9 @@ def _declare(lib):
     lib.gnot_plan_set_pre_norm.argtypes = [P, i32, ctypes.c_float]
     lib.gnot_layer_norm.argtypes = [P, i64, i64, i32, ctypes.c_float, P, i64, P, P]
     lib.gnot_layer_norm_bwd.argtypes = [P, i64, P, P, i64, i64, i32, P, i64, i32, P]
+    lib.gnot_lp_loss_work_floats.argtypes = [ctypes.POINTER(i64), i32, i32]
+    lib.gnot_lp_loss_work_floats.restype = sz
+    lib.gnot_lp_loss.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, i32, P, P, P, P, P, P, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p

@@ -28,6 +28,9 @@
   targets (data.Normalizer): the losses de-normalise the prediction inside their kernels
   (gnot_rel_l2_loss_affine / gnot_mse_loss_affine), the statistics travel in the state file, and the best
   checkpoint is written with them folded into its first and last Linears.
+* `LpLoss(kind, component_weights, normalizer)` -- the original GNOT code's named losses (rel2, rel1, relinf, mse,
+  l1, linf) with per-component weights through gnot_lp_loss, its `terms()` per (sample, channel),
+  `evaluate_table` (the per-sample error table of a test set) and `fit(log_components=True)`.
 """
 import contextlib
 import ctypes
@@ -81,9 +84,8 @@ class RelL2Loss(torch.nn.Module):
         self.normalizer = normalizer
         self._stats = None         # the normalizer's y block on the predictions' device
 
-    def forward(self, x_off, predictions, targets):
-        if not predictions.is_cuda:
-            raise RuntimeError(f"gnot_amd.{type(self).__name__} runs on a ROCm GPU only (libgnot_hip.so)")
+    def _geometry(self, x_off, predictions):
+        """(device offsets, work buffer, host offsets) of the packed geometry x_off, cached for the last one"""
         key = (tuple(int(v) for v in x_off), predictions.shape[1], predictions.device)
         if key not in self._cache:
             B = len(key[0]) - 1
@@ -95,16 +97,29 @@ class RelL2Loss(torch.nn.Module):
             self._cache = {key: (pinned.to(predictions.device, non_blocking=True),
                                  torch.empty(n, dtype=torch.float32, device=predictions.device), pinned)}
         off_dev, work, _ = self._cache[key]
+        return off_dev, work, key[0]
+
+    def _y_stats(self, predictions):
+        """the normalizer's y block on the predictions' device (None without a normalizer)"""
         if self.normalizer is None:
-            return _NativeLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0],
-                                     work, self._entry)
+            return None
         if self._stats is None or self._stats.device != predictions.device:
             self._stats = self.normalizer.y.to(predictions.device).contiguous()
         if self._stats.shape[1] != predictions.shape[1]:
             raise ValueError(f"{type(self).__name__}: the normalizer's y statistics hold {self._stats.shape[1]} "
                              f"channels, the prediction {predictions.shape[1]}")
-        return _NativeLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, key[0], work,
-                                 self._entry + "_affine", self._stats)
+        return self._stats
+
+    def forward(self, x_off, predictions, targets):
+        if not predictions.is_cuda:
+            raise RuntimeError(f"gnot_amd.{type(self).__name__} runs on a ROCm GPU only (libgnot_hip.so)")
+        off_dev, work, off_host = self._geometry(x_off, predictions)
+        stats = self._y_stats(predictions)
+        if stats is None:
+            return _NativeLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, off_host,
+                                     work, self._entry)
+        return _NativeLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, off_host, work,
+                                 self._entry + "_affine", stats)
 
 
 class MSELoss(RelL2Loss):
@@ -114,6 +129,102 @@ class MSELoss(RelL2Loss):
     A sample without points is refused (its mean is undefined)."""
 
     _entry, _work_floats = "gnot_mse_loss", "gnot_mse_work_floats"
+
+
+class _NativeLpLoss(torch.autograd.Function):
+    """gnot_lp_loss: the loss, d loss / d pred where pred needs it, and the unweighted terms into `terms`
+    ([B, C], or None) in the same pass"""
+
+    @staticmethod
+    def forward(ctx, pred, tgt, off_dev, off_host, work, kind, weights, stats, terms):
+        B = len(off_host) - 1
+        loss = torch.empty((), device=pred.device, dtype=torch.float32)
+        dpred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        oh = (ctypes.c_int64 * (B + 1))(*off_host)
+        s = ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(_lib.load().gnot_lp_loss(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, pred.shape[1],
+                                            _lib.LP_KINDS[kind], ptr(weights), ptr(stats), work.data_ptr(),
+                                            loss.data_ptr(), ptr(terms), ptr(dpred), s))
+        ctx.save_for_backward(dpred) if dpred is not None else None
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return (dpred * g,) + (None,) * 8
+
+
+class LpLoss(RelL2Loss):
+    """The loss family of the original GNOT recipe, `LpLoss(kind)(x_off, pred, tgt)` in RelL2Loss's call
+    convention, one native pass (gnot_lp_loss).  With d = pred - tgt over the N_b points of sample b, the term
+    of (sample b, channel c) is
+        rel2  sqrt(sum d^2 / sum t^2)    rel1  sum |d| / sum |t|    relinf  max |d| / max |t|
+        mse   sum d^2 / N_b              l1    sum |d| / N_b        linf    max |d|
+    and the loss (1/B) sum_b sum_c w_c e[b, c] / sum_c w_c.
+    component_weights: C non-negative numbers with a positive sum, one per output channel (ValueError for a
+    negative or non-finite one, a zero sum, or -- at the call -- another length than the prediction's
+    channels); a channel of weight zero gets a gradient of exact zeros.  None (default): every channel 1 / C,
+    and `rel2` / `mse` are then RelL2Loss / MSELoss bit for bit, loss and gradient.
+    relinf and linf are metrics: a prediction that requires grad is a ValueError.  A sample without points is
+    refused for every kind.  normalizer: as in RelL2Loss.
+    `terms(x_off, pred, tgt)` is the [B, C] table of the unweighted e[b, c] (a device tensor, no_grad);
+    `trajectory_name()` names kind and weights for fit's state file."""
+
+    _work_floats = "gnot_lp_loss_work_floats"
+
+    def __init__(self, kind="rel2", component_weights=None, normalizer=None):
+        if kind not in _lib.LP_KINDS:
+            raise ValueError(f"LpLoss: unknown kind {kind!r} (one of {', '.join(_lib.LP_KINDS)})")
+        if component_weights is not None:
+            component_weights = [float(v) for v in component_weights]
+            if not component_weights:
+                raise ValueError("LpLoss: component_weights is empty")
+            if not all(math.isfinite(v) for v in component_weights):
+                raise ValueError("LpLoss: component_weights must be finite")
+            if min(component_weights) < 0:
+                raise ValueError("LpLoss: component_weights must not be negative")
+            total = float(torch.tensor(component_weights, dtype=torch.float32).sum())
+            if not (total > 0 and math.isfinite(total)):
+                raise ValueError("LpLoss: component_weights need a positive (fp32-finite) sum")
+        super().__init__(normalizer)
+        self.kind, self.component_weights = kind, component_weights
+        self._w = None             # the weights on the predictions' device
+
+    def trajectory_name(self):
+        w = "" if self.component_weights is None else f", w={self.component_weights}"
+        return f"LpLoss({self.kind}{w})"
+
+    def _run(self, x_off, predictions, targets, want_terms):
+        """(loss, terms or None); every refusal the host can make comes before any GPU work"""
+        C = predictions.shape[1]
+        if self.kind in ("relinf", "linf") and predictions.requires_grad and torch.is_grad_enabled():
+            raise ValueError(f"LpLoss({self.kind}) is a metric only: it has no gradient, and this prediction requires "
+                             "one (call it under torch.no_grad() or on a detached prediction)")
+        if self.component_weights is not None and len(self.component_weights) != C:
+            raise ValueError(f"LpLoss: {len(self.component_weights)} component_weights, the prediction has {C} channels")
+        if not predictions.is_cuda:
+            raise RuntimeError("gnot_amd.LpLoss runs on a ROCm GPU only (libgnot_hip.so)")
+        off_dev, work, off_host = self._geometry(x_off, predictions)
+        stats = self._y_stats(predictions)
+        if self.component_weights is not None and (self._w is None or self._w.device != predictions.device):
+            self._w = torch.tensor(self.component_weights, dtype=torch.float32, device=predictions.device)
+        terms = torch.empty(len(off_host) - 1, C, dtype=torch.float32, device=predictions.device) if want_terms else None
+        loss = _NativeLpLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, off_host,
+                                   work, self.kind, self._w, stats, terms)
+        return loss, terms
+
+    def forward(self, x_off, predictions, targets):
+        return self._run(x_off, predictions, targets, False)[0]
+
+    def loss_and_terms(self, x_off, predictions, targets):
+        """(loss, terms [B, C]) of one pass; the loss is forward()'s, bit for bit, and differentiable like it"""
+        return self._run(x_off, predictions, targets, True)
+
+    def terms(self, x_off, predictions, targets):
+        """the unweighted e[b, c] as a [B, C] device tensor (no_grad; they do not depend on the weights)"""
+        with torch.no_grad():
+            return self._run(x_off, predictions, targets, True)[1]
 
 
 # ------------------------------------------------------------------ OneCycleLR (main.py:52)
@@ -588,16 +699,39 @@ def evaluate(model, loader, loss_fn=None, normalizer=None):
     return _evaluate(model, loader, loss_fn, _batch_encoder(loader, normalizer, "evaluate: the loader"))
 
 
-def _evaluate(model, loader, loss_fn, encoder):
-    """evaluate behind its checks; encoder: _batch_encoder's answer for this loader"""
+def _evaluate(model, loader, loss_fn, encoder, tables=None):
+    """evaluate behind its checks; encoder: _batch_encoder's answer for this loader.  tables (a list; loss_fn is
+    then an LpLoss): every batch's [B, C] terms are appended to it, device tensors from the same pass as its loss"""
     dev = next(model.parameters()).device
     vals = []
     with torch.no_grad():
         for batch in loader:
             pred, off, y = _forward_batch(model, batch, dev, encoder)
-            vals.append(loss_fn(off, pred, y))
+            if tables is None:
+                vals.append(loss_fn(off, pred, y))
+            else:
+                loss, terms = loss_fn.loss_and_terms(off, pred, y)
+                vals.append(loss)
+                tables.append(terms)
     vals = _read_back(vals)
     return sum(vals) / max(len(vals), 1)
+
+
+def evaluate_table(model, loader, kind="rel2", normalizer=None):
+    """The per-sample error table of a test set: a host tensor [S, C], row s the terms e[s, c] of LpLoss(kind)
+    for the s-th sample in loader order (batch after batch, samples in batch order), one column per output
+    channel -- which meshes and which fields are the bad ones.  no_grad; every batch's terms stay on the device
+    and the table is read once, behind the last batch.  normalizer: as in evaluate (the same checks; the errors
+    are in physical units)."""
+    loss_fn = LpLoss(kind, normalizer=normalizer)
+    encoder = _batch_encoder(loader, normalizer, "evaluate_table: the loader")
+    dev = next(model.parameters()).device
+    tables = []
+    with torch.no_grad():
+        for batch in loader:
+            pred, off, y = _forward_batch(model, batch, dev, encoder)
+            tables.append(loss_fn.terms(off, pred, y))
+    return torch.cat(tables).cpu() if tables else torch.empty(0, 0)
 
 
 def accum_groups(sizes, accum_steps):
@@ -649,14 +783,16 @@ def _accum_step(model, eng, opt, loss_fn, group, dev, encoder=None):
 
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
         log=print, loss_fn=None, max_grad_norm=None, accum_steps=1, skip_nonfinite=False, state_path=None,
-        resume=False, ema_decay=None, ema_warmup=True, normalizer=None):
+        resume=False, ema_decay=None, ema_warmup=True, normalizer=None, log_components=False):
     """The reference training loop (main.py:50-153): AdamW(lr) + OneCycleLR(max_lr=lr, steps_per_epoch,
     epochs), RelL2 loss, per-epoch test metric and best checkpoint.  With per_epoch_schedule=True the
     schedule is stepped once per epoch, as main.py:106 does.  The loaders decide the batch form:
     collate_padded batches run main.py's zero-padded semantics (pad rows in the attention sums),
     collate_packed batches the packed (per-sample exact) one.
-    loss_fn: the training loss, `RelL2Loss()` (default) or `MSELoss()` (main.py:97-98); the test metric is
-    RelL2 either way (main.py:143).  max_grad_norm: global-norm gradient clipping in front of every AdamW
+    loss_fn: the training loss, `RelL2Loss()` (default), `MSELoss()` (main.py:97-98) or an `LpLoss(kind,
+    component_weights)`; the test metric is RelL2 either way (main.py:143).  A loss with a `trajectory_name()`
+    (LpLoss: kind and weights) is stored under it in the state file, every other one under its class name, so a
+    run resumes only under the loss that wrote it.  max_grad_norm: global-norm gradient clipping in front of every AdamW
     step (FlatAdamW's max_grad_norm; None = off, the reference's loop).
     accum_steps: every accum_steps consecutive loader batches (micro-batches; the epoch's tail group may be
     shorter) form ONE optimizer step on the gradient of their concatenation (accum_groups): micro-batch i
@@ -698,6 +834,12 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     any GPU work (normalise that block in the dataset, or leave it out of the statistics); the state file takes
     any combination.
     None (default): raw data, every call what it was.
+    log_components: with a test loader, every epoch also logs "Epoch k, Test Metric per component: [...]", one
+    value per output channel: the MEAN OVER ALL TEST SAMPLES of the per-sample RelL2 terms (the column means of
+    evaluate_table's rel2 table), taken from the same forwards as the scalar metric -- the metric pass writes its
+    terms beside its loss (LpLoss.loss_and_terms), bit for bit the same loss.  The scalar metric stays main.py's
+    mean over BATCHES of the batch means; when the last batch is short the mean of the logged components is
+    therefore not the scalar metric.  The return value is unchanged.  False (default): nothing else happens.
     No step reads its loss back: every step's 0-d loss (with accum_steps, every micro-batch's) stays on the
     device and the epoch reads them all at its end, then does the host arithmetic above on those fp32 values;
     with a loader whose batches are on the device already (data.DeviceLoader) the host runs ahead of the GPU
@@ -718,7 +860,8 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     args = dict(epochs=int(epochs), lr=float(lr), steps_per_epoch=steps_per_epoch, accum_steps=accum_steps,
                 per_epoch_schedule=bool(per_epoch_schedule),
                 max_grad_norm=None if max_grad_norm is None else float(max_grad_norm),
-                loss=type(loss_fn).__name__, skip_nonfinite=bool(skip_nonfinite))
+                loss=loss_fn.trajectory_name() if hasattr(loss_fn, "trajectory_name") else type(loss_fn).__name__,
+                skip_nonfinite=bool(skip_nonfinite))
     # beside args, not in it: TRAJECTORY_ARGS is the raw trajectory, which the average does not touch
     ema_args = None if ema_decay is None else dict(ema_decay=float(ema_decay), ema_warmup=bool(ema_warmup))
     state = None
@@ -753,7 +896,11 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     eng = model.engine()
     prev = eng.param_grads
     eng.param_grads = False          # FlatAdamW reads the gradient arena; no .grad copies
-    metric = loss_fn if type(loss_fn) is RelL2Loss else RelL2Loss(normalizer)
+    log_components = bool(log_components) and test_loader is not None
+    if log_components:
+        metric = LpLoss("rel2", normalizer=normalizer)      # RelL2Loss's bits, and the terms in the same pass
+    else:
+        metric = loss_fn if type(loss_fn) is RelL2Loss else RelL2Loss(normalizer)
     best, hist_train, hist_test, first, skipped = float("inf"), [], [], 0, 0
     if state is not None:
         opt.load_state_dict(state["optimizer"])
@@ -796,9 +943,13 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             if test_loader is not None:
                 # with ema_decay the metric and the checkpoint see the averaged weights
                 with opt.ema.swapped() if opt.ema is not None else contextlib.nullcontext():
-                    res = _evaluate(model, test_loader, metric, enc_test)
+                    tables = [] if log_components else None
+                    res = _evaluate(model, test_loader, metric, enc_test, tables)
                     hist_test.append(res)
                     log(f"Epoch {epoch}, Test Metric: {res}")
+                    if tables:
+                        log(f"Epoch {epoch}, Test Metric per component: "
+                            f"{torch.cat(tables).cpu().double().mean(0).tolist()}")
                     if res < best and checkpoint:
                         best = res
                         save_checkpoint(model, checkpoint, normalizer)

@@ -457,7 +457,31 @@ int gnot_rel_l2_loss_affine(const float* pred, const float* tgt, const int64_t* 
 int gnot_mse_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B,
                          int C, const float* out_stats, float* work, float* loss, float* dpred, void* stream);
 
-/* Live kernel timing for the bench's roofline: while enabled, every launch of kernel class `kind`
+/* The Lp loss family with component weights and per-sample terms, over the packed arguments of gnot_rel_l2_loss.
+ * With d = p' - t (p' = pred, or pred * std[c] + mean[c] rounded as in the _affine entries when out_stats is not
+ * NULL) and n over the N_b rows of sample b, the term of (sample b, channel c) is
+ *   GNOT_LP_REL2    sqrt(sum d^2 / sum t^2)        GNOT_LP_MSE   sum d^2 / N_b
+ *   GNOT_LP_REL1    sum |d| / sum |t|              GNOT_LP_L1    sum |d| / N_b
+ *   GNOT_LP_RELINF  max |d| / max |t|              GNOT_LP_LINF  max |d|
+ * and *loss (device) = (1/B) sum_b sum_c w^_c e[b, c], w^_c = w_c / sum_c w_c from comp_weights (DEVICE array of C
+ * non-negative weights with a positive sum, normalised on the device in index order) or 1/C when it is NULL.
+ * terms, if not NULL: DEVICE [B, C], the unweighted e[b, c]; they do not depend on comp_weights.  dpred, if not
+ * NULL: d loss / d pred, (w^_c / B) d e / d p' -- sign(d) / sum |t| for rel1, sign(d) / N_b for l1, sign(0) = 0 --
+ * times std[c] as one more rounded product with out_stats; a channel of weight zero gets exact zeros.  relinf and
+ * linf are metrics only: a dpred with them is GNOT_E_INVALID, as are an unknown kind and a sample without rows
+ * ("empty sample"), all before any launch.  A relative kind with an all-zero target channel gives inf / NaN, like
+ * gnot_rel_l2_loss (no epsilon).  Without comp_weights, REL2 and MSE give the bits of gnot_rel_l2_loss(_affine) /
+ * gnot_mse_loss(_affine), loss and dpred alike (without terms too, they launch those entries' kernels).  work: device
+ * scratch of gnot_lp_loss_work_floats(off_host, B, C) floats.  Three launches at most (partial sums per 2048-row
+ * split, one finish workgroup, the elementwise gradient), fixed-order reductions, no atomics, no host
+ * synchronisation: deterministic and capturable. */
+enum { GNOT_LP_REL2 = 0, GNOT_LP_REL1 = 1, GNOT_LP_RELINF = 2, GNOT_LP_MSE = 3, GNOT_LP_L1 = 4, GNOT_LP_LINF = 5 };
+size_t gnot_lp_loss_work_floats(const int64_t* off_host, int B, int C);
+int gnot_lp_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B, int C,
+                 int kind, const float* comp_weights, const float* out_stats, float* work, float* loss, float* terms,
+                 float* dpred, void* stream);
+
+/* Live kernel timing for the bench's roofline:while enabled, every launch of kernel class `kind`
  * ("moe_fwd" fused expert chains forward, "moe_bwd" their backward, "wgrad" weight-gradient GEMMs;
  * "" disables) is bracketed by hipEvents on its stream.  gnot_profile_read synchronizes on those
  * events and returns the summed device time, the launch count and the algorithmic FLOPs of those

@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""What the Lp loss family costs beside the RelL2 entry: gnot_rel_l2_loss, gnot_lp_loss(rel2) and
+gnot_lp_loss(rel1, component weights), the last two with and without the per-sample terms, each with the gradient,
+on 262,144 packed rows (4 samples of 65,536) with C = 1 and C = 3 output channels.  --parent-lib names a
+libgnot_hip.so built from the parent commit, whose gnot_rel_l2_loss is then timed in the same process.
+Every variant is timed in blocks of --calls back-to-back calls between two device events (one call is a few
+microseconds of kernels: a single one would time the events); the blocks of all variants are interleaved, repetition
+after repetition, after a warm-up, and the medians per call are reported.  rel2 without weights and terms launches the
+kernels of gnot_rel_l2_loss, so the two should sit inside the spread of repeated blocks (us_min .. us_max).
+
+    python scripts/lp_loss_cost.py [--parent-lib PATH] [--reps 30] [--calls 200] [--out FILE]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gnot-replication_amd"))
+
+import torch  # noqa: E402
+
+from gnot_amd import _lib  # noqa: E402
+
+ROWS, B = 262144, 4
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", default=None, help="a libgnot_hip.so of the parent commit (its gnot_rel_l2_loss)")
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--calls", type=int, default=200, help="calls per timed block")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    parent = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib)
+        parent.gnot_rel_l2_loss.argtypes = lib.gnot_rel_l2_loss.argtypes
+    s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    P = lambda t: None if t is None else t.data_ptr()
+    off = [b * (ROWS // B) for b in range(B + 1)]
+    oh = (ctypes.c_int64 * (B + 1))(*off)
+    off_dev = torch.tensor(off, dtype=torch.int64, device=dev)
+    out = {"rows": ROWS, "samples": B, "reps": args.reps, "calls_per_block": args.calls}
+    for C in (1, 3):
+        gen = torch.Generator(device=dev).manual_seed(C)
+        pred = torch.randn(ROWS, C, device=dev, generator=gen)
+        tgt = torch.randn(ROWS, C, device=dev, generator=gen) + 0.5
+        w = torch.tensor([1.0, 0.0, 3.0][:C], device=dev)
+        work = torch.empty(lib.gnot_lp_loss_work_floats(oh, B, C), device=dev)
+        loss, terms, dpred = torch.empty((), device=dev), torch.empty(B, C, device=dev), torch.empty_like(pred)
+        head = (P(pred), P(tgt), P(off_dev), oh, B, C)
+        lp = lambda kind, wt, tm: (lambda: lib.gnot_lp_loss(*head, _lib.LP_KINDS[kind], P(wt), None, P(work), P(loss),
+                                                            P(tm), P(dpred), s))
+        runs = {}
+        if parent is not None:
+            runs["parent_rel_l2"] = lambda: parent.gnot_rel_l2_loss(*head, P(work), P(loss), P(dpred), s)
+        runs.update({"rel_l2": lambda: lib.gnot_rel_l2_loss(*head, P(work), P(loss), P(dpred), s),
+                     "lp_rel2": lp("rel2", None, None), "lp_rel2_terms": lp("rel2", None, terms),
+                     "lp_rel1_w": lp("rel1", w, None), "lp_rel1_w_terms": lp("rel1", w, terms)})
+        times = {k: [] for k in runs}
+        for rep in range(args.warmup + args.reps):
+            for k, fn in runs.items():               # interleaved: every repetition times a block of each
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.calls):
+                    if fn() != 0:
+                        raise RuntimeError(f"{k}: a call failed")
+                e1.record()
+                e1.synchronize()
+                if rep >= args.warmup:
+                    times[k].append(e0.elapsed_time(e1) * 1e3 / args.calls)
+        med = {k: statistics.median(t) for k, t in times.items()}
+        base = med.get("parent_rel_l2", med["rel_l2"])
+        out[f"C{C}"] = {"us_median": {k: round(x, 2) for k, x in med.items()},
+                        "us_min": {k: round(min(t), 2) for k, t in times.items()},
+                        "us_max": {k: round(max(t), 2) for k, t in times.items()},
+                        "over_" + ("parent_rel_l2" if parent is not None else "rel_l2"):
+                            {k: round(x / base, 3) for k, x in med.items()}}
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

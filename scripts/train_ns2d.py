@@ -9,6 +9,9 @@ targets (statistics of the training set, computed on the device) and writes a ch
 --x-fourier N / --fn-fourier N embed the coordinates / the input functions in multi-scale Fourier features of
 order N inside the model (the original GNOT code's horiz_fourier_dim), behind the normalisation.
 --pre-norm normalises the attention inputs (a parameter-free LayerNorm, the original GNOT code's ln1 .. ln5).
+--loss rel_l1 / l1 and --component-weights W0,W1,... train on the original GNOT code's other named losses and on
+weighted output components (train.LpLoss); --log-components logs the test metric per output component every epoch
+and prints the five worst test samples at the end (train.evaluate_table).
 
     python scripts/train_ns2d.py --train train.pkl --test test.pkl [--epochs 100 ...]
     python scripts/train_ns2d.py --synthetic 64 --epochs 2          # generated meshes, same format
@@ -26,7 +29,12 @@ import torch  # noqa: E402
 from gnot_amd import GNOT, data, train  # noqa: E402
 
 
-def main():
+LOSS_KINDS = {"rel_l2": "rel2", "mse": "mse", "rel_l1": "rel1", "l1": "l1"}       # --loss -> train.LpLoss's kind
+
+
+def parse_args(argv=None):
+    """The command line (argv: a list, default sys.argv[1:]) as a namespace; host only.  `normalize` becomes the
+    set of arrays to normalise (or None) and `component_weights` a list of floats (or None)."""
     ap = argparse.ArgumentParser(description="GNOT (MI355X)")
     ap.add_argument("--gpu_id", type=int, default=0)
     ap.add_argument("--n_attn_layers", type=int, default=4)
@@ -45,8 +53,15 @@ def main():
     ap.add_argument("--checkpoint", default="best_model.pth")
     ap.add_argument("--packed", action="store_true",
                     help="packed batches (per-sample exact); default: main.py's zero-padded batches")
-    ap.add_argument("--loss", choices=["rel_l2", "mse"], default="rel_l2",
-                    help="training loss: RelL2Loss (main.py:98) or MSELoss (main.py:97); the test metric stays RelL2")
+    ap.add_argument("--loss", choices=list(LOSS_KINDS), default="rel_l2",
+                    help="training loss: RelL2Loss (main.py:98), MSELoss (main.py:97), or the original GNOT code's "
+                         "relative L1 / L1 (train.LpLoss); the test metric stays RelL2")
+    ap.add_argument("--component-weights", default=None, metavar="W0,W1,...",
+                    help="one non-negative weight per output component in the training loss (normalised to sum 1; "
+                         "0 takes a component out of the loss).  Default: every component weighs the same")
+    ap.add_argument("--log-components", action="store_true",
+                    help="log the test metric per output component every epoch (mean over the test samples) and "
+                         "print the five worst test samples, with their per-component RelL2, after training")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="FLOAT",
                     help="clip the global gradient norm to this value before every AdamW step (default: off)")
     ap.add_argument("--accum-steps", type=int, default=1, metavar="N",
@@ -83,7 +98,13 @@ def main():
     ap.add_argument("--pre-norm", action="store_true",
                     help="LayerNorm (no gamma / beta, eps 1e-5) on the inputs of every attention call; the "
                          "checkpoint then has one more key, pre_norm_eps, and loads only into GNOT(pre_norm=True)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.component_weights is not None:
+        try:
+            args.component_weights = [float(v) for v in args.component_weights.split(",")]
+            train.LpLoss(LOSS_KINDS[args.loss], args.component_weights)      # the host checks of the weights
+        except ValueError as e:
+            ap.error(f"--component-weights takes comma-separated non-negative numbers with a positive sum ({e})")
     norm = None if args.normalize is None else set(filter(None, args.normalize.split(",")))
     if norm is not None and (not norm or norm - {"x", "theta", "fns", "y"}):
         ap.error("--normalize takes a comma-separated subset of x,theta,fns,y")
@@ -93,6 +114,21 @@ def main():
                      f"cannot be folded into the checkpoint; normalise {block} in the dataset itself or drop it "
                      "from --normalize")
     args.device_data = args.device_data or args.points_per_mesh is not None or norm is not None
+    args.normalize = norm
+    return args
+
+
+def training_loss(args, normalizer=None):
+    """The loss of --loss / --component-weights: RelL2Loss or MSELoss as before, an LpLoss for the new kinds and
+    for any weights"""
+    if args.component_weights is None and args.loss in ("rel_l2", "mse"):
+        return train.MSELoss(normalizer) if args.loss == "mse" else train.RelL2Loss(normalizer)
+    return train.LpLoss(LOSS_KINDS[args.loss], args.component_weights, normalizer)
+
+
+def main():
+    args = parse_args()
+    norm = args.normalize
     if args.synthetic:
         rng = np.random.default_rng(0)
         tr = data.NS2dData([data.synthetic_sample(rng, int(rng.integers(1000, 4000))) for _ in range(args.synthetic)])
@@ -120,11 +156,17 @@ def main():
         loaders = dl(tr, True), dl(te, False)
     _, test = train.fit(model, *loaders, epochs=args.epochs,
                         per_epoch_schedule=not args.per_batch_schedule, checkpoint=args.checkpoint,
-                        loss_fn=train.MSELoss(nz) if args.loss == "mse" else train.RelL2Loss(nz),
+                        loss_fn=training_loss(args, nz), log_components=args.log_components,
                         max_grad_norm=args.grad_clip, accum_steps=args.accum_steps,
                         skip_nonfinite=args.skip_nonfinite, state_path=args.state, resume=args.resume,
                         ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup, normalizer=nz)
     print(f"\nBest Test Metric: {min(test)}")
+    if args.log_components:      # of the final weights (the raw ones, also with --ema-decay)
+        table = train.evaluate_table(model, loaders[1], "rel2", nz)
+        worst = table.mean(1).argsort(descending=True)[:5].tolist()
+        print("Worst test samples (index, RelL2 per component):")
+        for i in worst:
+            print(f"  {i}: {table[i].tolist()}")
 
 
 if __name__ == "__main__":
