@@ -278,6 +278,81 @@ static void pre_norm() {
   CHECK(gnot_layer_norm_bwd(buf, 4, buf, buf, 4, 1, 4, buf + 4, 6, 0, nullptr) == GNOT_E_INVALID);
 }
 
+// dropout (gnot_plan_set_dropout): the option adds one small table (the samples' first points) and no buffer, also
+// for a sharded batch with an empty sample; on-then-off restores the plain layout; the launch-time switch leaves
+// the batch alone; bad arguments are refused.  (Its own generator, outside the layout digest, as above.)
+static void dropout() {
+  std::mt19937 rng(4242);
+  alignas(16) static uint32_t key[4];
+  alignas(16) static float buf[8];
+  static int64_t tab[2];
+  const int widths[][2] = {{64, 4}, {40, 2}, {256, 8}, {320, 5}};
+  for (const auto& wh : widths)
+    for (int I = 0; I <= 1; ++I) {
+      gnot_config c{};
+      c.input_dim = 2; c.theta_dim = 1; c.input_func_dim = 3; c.out_dim = 2; c.n_attn_layers = 1 + I;
+      c.n_attn_hidden_dim = c.n_mlp_hidden_dim = c.n_input_hidden_dim = wh[0];
+      c.n_mlp_num_layers = 2; c.n_expert = 3; c.n_head = wh[1]; c.n_input_functions = I;
+      gnot_plan* p = nullptr;
+      CHECK(gnot_plan_create(&c, &p) == GNOT_OK);
+      if (!p) continue;
+      CHECK(gnot_plan_set_dropout(p, 1.f, key) == GNOT_E_INVALID);
+      CHECK(gnot_plan_set_dropout(p, -0.1f, key) == GNOT_E_INVALID);
+      CHECK(gnot_plan_set_dropout(p, std::numeric_limits<float>::quiet_NaN(), key) == GNOT_E_INVALID);
+      CHECK(gnot_plan_set_dropout(p, 0.25f, nullptr) == GNOT_E_INVALID);
+      CHECK(gnot_plan_set_dropout_active(nullptr, 1) == GNOT_E_INVALID);
+      for (int trial = 0; trial < 3; ++trial) {
+        const int B = 2 + (int)(rng() % 4);
+        std::vector<int64_t> n(B), m(B);
+        for (int b = 0; b < B; ++b) {
+          n[b] = (trial == 1 && b == 1) ? 0 : 1 + (int64_t)(rng() % 2000);   // an empty sample once
+          m[b] = n[b] ? 1 + (int64_t)(rng() % 300) : 0;
+        }
+        const auto xo = offsets(n), fo = offsets(m);
+        for (int tr = 0; tr < 2; ++tr) {
+          CHECK(gnot_plan_set_dropout(p, 0.f, nullptr) == GNOT_OK);
+          CHECK(gnot_plan_set_batch(p, B, xo.data(), I ? fo.data() : nullptr, tr) == GNOT_OK);
+          const size_t plain = gnot_plan_workspace_bytes(p);
+          CHECK(gnot_plan_set_dropout(p, 0.25f, key) == GNOT_OK);
+          CHECK(gnot_plan_workspace_bytes(p) == 0);                  // batch invalidated
+          CHECK(gnot_plan_set_batch(p, B, xo.data(), I ? fo.data() : nullptr, tr) == GNOT_OK);
+          const size_t on = gnot_plan_workspace_bytes(p);
+          CHECK(on >= plain && on <= plain + 256);                   // one table of B offsets, no rows
+          CHECK(gnot_plan_set_dropout_active(p, 0) == GNOT_OK);
+          CHECK(gnot_plan_workspace_bytes(p) == on);                 // a launch-time switch
+          CHECK(gnot_plan_set_dropout(p, 0.f, nullptr) == GNOT_OK);
+          CHECK(gnot_plan_set_batch(p, B, xo.data(), I ? fo.data() : nullptr, tr) == GNOT_OK);
+          CHECK(gnot_plan_workspace_bytes(p) == plain);              // on, then off: the plain layout
+        }
+        gnot_comm comm{nullptr, fake_allreduce, fake_alltoallv};
+        CHECK(gnot_plan_set_dropout(p, 0.25f, key) == GNOT_OK);
+        for (int r = 0; r < 2; ++r) {
+          CHECK(gnot_plan_set_shard(p, r, 2, B, n.data(), &comm) == GNOT_OK);
+          std::vector<int64_t> loc(B);
+          for (int b = 0; b < B; ++b) {
+            int64_t lo, hi;
+            CHECK(gnot_shard_range(n[b], r, 2, &lo, &hi) == GNOT_OK);
+            loc[b] = hi - lo;
+          }
+          const auto lo = offsets(loc);
+          const int st = gnot_plan_set_batch(p, B, lo.data(), I ? fo.data() : nullptr, 1);
+          CHECK(st == GNOT_OK || lo.back() == 0);
+        }
+        CHECK(gnot_plan_set_shard(p, 0, 1, B, n.data(), nullptr) == GNOT_OK);
+      }
+      gnot_plan_destroy(p);
+    }
+  CHECK(gnot_dropout_rows(nullptr, 4, 1, 4, tab, tab, 1, key, 0, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf, 4, 0, 4, tab, tab, 1, key, 0, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf, 4, 1, 1025, tab, tab, 1, key, 0, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf, 2, 1, 2, tab, tab, 1, key, 0, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf + 1, 4, 1, 3, tab, tab, 1, key, 0, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf, 4, 1, 4, tab, tab, 0, key, 0, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf, 4, 1, 4, tab, tab, 1, nullptr, 0, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf, 4, 1, 4, tab, tab, 1, key, 1u << 24, 0.25f, nullptr) == GNOT_E_INVALID);
+  CHECK(gnot_dropout_rows(buf, 4, 1, 4, tab, tab, 1, key, 0, 1.f, nullptr) == GNOT_E_INVALID);
+}
+
 int main() {
   std::mt19937 rng(12345);
   // {width, heads}: 96 / 192 have head widths 12 / 24; 320 runs chainw.hip, 576 (internal width 640) the
@@ -351,6 +426,7 @@ int main() {
   }
   exchange(rng);
   pre_norm();
+  dropout();
   std::printf("layout digest: %016llx\n", (unsigned long long)g_digest);
   std::printf("asan_plan_check: %s (%d failed checks)\n", g_fail ? "FAILED" : "ok", g_fail);
   return g_fail ? 1 : 0;

@@ -136,6 +136,15 @@ struct gnot_plan {
   std::string norm_rstd(int l, bool cross) const { return "b" + std::to_string(l) + (cross ? ".r1" : ".r2"); }
   // the rows the key/value projections of input function i read (and their weight gradients)
   std::string fn_rows(int i) const { return (pre_norm ? "fnn" : "fnenc") + std::to_string(i); }
+  // keyed dropout on the attention outputs (gnot_plan_set_dropout, dropout.hip): "b{l}.a" / "b{l}.bb" right
+  // after fc_out in the forward, the rows' gradient ("dsum0" / "dsum1") right before fc_out's backward.
+  // drop_T = 0: off, no launch and no table
+  uint32_t drop_T = 0;
+  float drop_scale = 1.f;
+  const uint32_t* drop_key = nullptr;   // device {seed_lo, seed_hi, step, 0}, read when the kernels run
+  bool drop_active = true;              // gnot_plan_set_dropout_active: the next forward drops
+  bool drop_fwd = false;                // the last gnot_forward dropped: its backward masks the same elements
+  long* d_glo = nullptr;                // [B] global index of this rank's first point of every sample
   std::vector<int> lin_o, lin_i;   // out / in features per canonical Linear
   std::vector<const float*> W, b;
   bool params_bound = false;
@@ -1194,6 +1203,21 @@ struct TableWalk {
   void operator()(const std::vector<T>& v, T*& d) { d = static_cast<T*>(put(v.data(), v.size() * sizeof(T))); }
 };
 
+static void shard_range(long n, int rank, int world, long& lo, long& hi);
+
+// dropout's glo table: the global index of this rank's first point of every sample (0 unsharded), so that a
+// sharded run keys its rows as the unsharded one does; empty while dropout is off
+static std::vector<long> drop_first_points(const gnot_plan* p) {
+  std::vector<long> glo;
+  if (p->drop_T == 0) return glo;
+  glo.assign(p->B, 0);
+  for (int b = 0; b < p->B && p->sharded; ++b) {
+    long hi;
+    shard_range(p->nglob[b], p->rank, p->world, glo[b], hi);
+  }
+  return glo;
+}
+
 // every device table once: its host data and where its device pointer goes.  The job lists are (re)built
 // here from the current buffer pointers, after the chunk tables they point into
 static void walk_tables(gnot_plan* p, TableWalk& w) {
@@ -1243,6 +1267,7 @@ static void walk_tables(gnot_plan* p, TableWalk& w) {
     p->d_fnoff.assign(I, nullptr);
     for (int i = 0; i < I; ++i) p->d_fnoff[i] = at(p->d_xoff, (long)(p->B + 1) * (i + 1));
   }
+  w(drop_first_points(p), p->d_glo);         // (empty without dropout: no table)
   build_groups(p);
   for_each_group(p, [&](WgradGroup& G) {
     w(G.jobs, G.d_jobs);
@@ -1454,6 +1479,41 @@ extern "C" int gnot_plan_set_pre_norm(gnot_plan* p, int on, float eps) {
     p->batch_set = false;          // the workspace layout changes: set_batch + bind again
     p->ws_bound = false;
   }
+  return GNOT_OK;
+}
+
+// T = floor(p 2^32 + 0.5) and scale = fp32(2^32 / (2^32 - T)) of a drop probability (computed in double: the
+// expectation is exact for the probability actually used); false for a p outside [0, 1) or not finite
+static bool drop_threshold(float prob, uint32_t& T, float& scale) {
+  if (!std::isfinite(prob) || !(prob >= 0.f) || !(prob < 1.f)) return false;
+  const double t = std::floor((double)prob * 4294967296.0 + 0.5);   // <= 2^32 - 2^8: the largest float below 1
+  T = (uint32_t)t;
+  scale = (float)(4294967296.0 / (4294967296.0 - t));
+  return true;
+}
+
+extern "C" int gnot_plan_set_dropout(gnot_plan* p, float prob, const uint32_t* key_dev) {
+  if (!p) return fail(GNOT_E_INVALID, "null plan");
+  uint32_t T = 0;
+  float scale = 1.f;
+  if (!drop_threshold(prob, T, scale)) return fail(GNOT_E_INVALID, "dropout: p must be finite and in [0, 1)");
+  if (T > 0 && !key_dev) return fail(GNOT_E_INVALID, "dropout: a device key {seed_lo, seed_hi, step, 0} is required");
+  if (T > 0 && (reinterpret_cast<uintptr_t>(key_dev) & 3)) return fail(GNOT_E_INVALID, "dropout: the key must be 4-byte aligned");
+  if (T == 0) key_dev = nullptr;
+  if (p->drop_T != T || p->drop_key != key_dev) {
+    p->drop_T = T;
+    p->drop_scale = scale;
+    p->drop_key = key_dev;
+    p->drop_active = true;
+    p->batch_set = false;          // the tables gain or lose the samples' first points: set_batch + bind again
+    p->ws_bound = false;
+  }
+  return GNOT_OK;
+}
+
+extern "C" int gnot_plan_set_dropout_active(gnot_plan* p, int on) {
+  if (!p) return fail(GNOT_E_INVALID, "null plan");
+  p->drop_active = on != 0;        // a launch-time switch: the next gnot_forward reads it, the batch stays
   return GNOT_OK;
 }
 
@@ -2033,6 +2093,17 @@ AttnApplyArgs apply_args(const gnot_plan* p) {
   return ap;
 }
 
+// keyed dropout of one attention call's output rows (forward) or of their gradient (backward), in place on
+// this stream; site 2 l: block l's cross attention, 2 l + 1: its self attention.  Only when the last forward
+// dropped (gnot_plan_set_dropout + gnot_plan_set_dropout_active)
+int drop_rows(Ctx& c, float* rows, int l, bool cross) {
+  gnot_plan* p = c.p;
+  if (!p->drop_fwd) return GNOT_OK;
+  GNOT_CK(launch_dropout_rows(rows, p->D, p->P, p->Dr, p->d_xoff, p->d_glo, p->B, p->drop_key,
+                              (uint32_t)(2 * l + (cross ? 0 : 1)), p->drop_T, p->drop_scale, c.s));
+  return GNOT_OK;
+}
+
 // one LinearAttention call (model.py:53-107). q_in: the query rows [P, D].
 int attn_forward(Ctx& c, int l, bool cross, const float* q_in, float* res_out, float* out) {
   gnot_plan* p = c.p;
@@ -2062,6 +2133,7 @@ int attn_forward(Ctx& c, int l, bool cross, const float* q_in, float* res_out, f
   // fc_out over the scramble rows: Dr columns per token (the head-major apply output viewed as rows of
   // H * dh = Dr floats, model.py:81-83), read zero-filled to the padded width
   GNOT_RUN(run_linear(c, res_out, p->Dr, p->Dr, A.o, pbias + A.bo, out, D, D, P, EPI_STORE, 0));
+  GNOT_RUN(drop_rows(c, out, l, cross));     // everything downstream reads the dropped rows
   return GNOT_OK;
 }
 
@@ -2090,6 +2162,9 @@ int attn_backward(Ctx& c, int l, bool cross) {
     return GNOT_OK;
   };
   GNOT_RUN(guard_write(c, dqkv));
+  // dropout: the forward's mask again, regenerated from the key, before fc_out's backward-data and its weight
+  // gradients (a forked group reads the masked rows)
+  GNOT_RUN(drop_rows(c, dsum, l, cross));
   // fc_out backward-data: dres = dout W_o (token order); sharded: back to this rank's head-major rows
   GNOT_RUN(run_linear(c, dsum, D, D, p->T_img[lo], nullptr, dres, p->Dr, D, P, EPI_STORE, 0, p->Dr));
   if (p->sharded) {
@@ -2227,6 +2302,7 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   const long P = p->P;
   const int D = p->D;
   const bool tr = p->training;
+  p->drop_fwd = p->drop_T > 0 && p->drop_active;   // remembered: gnot_backward mirrors what this forward does
   // the input-function branch (encoders, every block's K/V projections and states) depends only on
   // the input functions: it runs on side2 while the query branch (gating, x encoder) runs here.  The
   // query branch is issued first (graph replay dispatches in capture order).
@@ -2875,6 +2951,26 @@ extern "C" int gnot_layer_norm_bwd(const float* y, int64_t ldy, const float* rst
   if (!e && (reinterpret_cast<uintptr_t>(rstd) & 15)) e = "pointers must be 16-byte aligned";
   if (e) return fail(GNOT_E_INVALID, std::string("layer_norm_bwd: ") + e);
   GNOT_CK(launch_layer_norm_bwd(y, ldy, rstd, dy, lddy, rows, C, dx, lddx, accumulate, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_dropout_rows(float* x, int64_t ld, int64_t rows, int C, const int64_t* off_dev,
+                                 const int64_t* glo_dev, int B, const uint32_t* key_dev, uint32_t site, float prob,
+                                 void* stream) {
+  if (!x || !off_dev || !glo_dev || !key_dev) return fail(GNOT_E_INVALID, "dropout_rows: null pointer");
+  const char* e = norm_shape_error(rows, C);
+  if (!e) e = norm_array_error(x, ld, C);
+  if (!e && B < 1) e = "B must be at least 1";
+  if (!e && ((reinterpret_cast<uintptr_t>(off_dev) | reinterpret_cast<uintptr_t>(glo_dev)) & 7)) e = "the offsets must be 8-byte aligned";
+  if (!e && (reinterpret_cast<uintptr_t>(key_dev) & 3)) e = "the key must be 4-byte aligned";
+  if (!e && site >= (1u << 24)) e = "site must be below 2^24";
+  uint32_t T = 0;
+  float scale = 1.f;
+  if (!e && !drop_threshold(prob, T, scale)) e = "p must be finite and in [0, 1)";
+  if (e) return fail(GNOT_E_INVALID, std::string("dropout_rows: ") + e);
+  GNOT_CK(launch_dropout_rows(x, ld, rows, C, reinterpret_cast<const long*>(off_dev),
+                              reinterpret_cast<const long*>(glo_dev), B, key_dev, site, T, scale,
+                              static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

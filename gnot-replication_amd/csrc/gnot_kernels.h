@@ -337,6 +337,12 @@ hipError_t launch_layer_norm(const float* x, long ldx, long rows, int C, float e
                              hipStream_t s);
 hipError_t launch_layer_norm_bwd(const float* y, long ldy, const float* rstd, const float* dy, long lddy, long rows,
                                  int C, float* dx, long lddx, int accumulate, hipStream_t s);
+// Keyed dropout in place on [rows, ld] rows of C <= 1024 real columns (dropout.hip), one wave per row: element
+// (r, c) is kept and scaled iff word c % 4 of Philox4x32-10((n, b, site << 8 | c / 4, key[2]), (key[0], key[1])) is
+// at least T, else +0; b the row's sample in off [B + 1], n = r - off[b] + glo[b]; key: 4 uint32 in device memory,
+// read when the kernel runs.  T = 0: no launch.  Columns C .. ld - 1 are untouched
+hipError_t launch_dropout_rows(float* x, long ld, long rows, int C, const long* off, const long* glo, int B,
+                               const uint32_t* key, uint32_t site, uint32_t T, float scale, hipStream_t s);
 // test hook: y = gelu(x), dy = gelu_grad(x), (y2, dy2) = gelu_and_grad(x) over n contiguous floats
 hipError_t launch_debug_gelu(const float* x, float* y, float* dy, float* y2, float* dy2, long n, hipStream_t s);
 // segmented copy: dst[seg.dst + i] = src[seg.src + i], i < seg.len (floats); reverse swaps the roles of

@@ -13,6 +13,8 @@ global-norm gradient clipping, `OneCycle`, `fit`), datasets, loaders and unit-Ga
 Fourier features inside the model (`gnot_amd.fourier`: `fourier_features` is the same map in plain torch,
 `fourier_embed` the library's kernel).  `GNOT(..., pre_norm=True)` normalises the inputs of every attention call
 with a parameter-free LayerNorm (`gnot_amd.norm` holds the two row kernels' wrappers).
+`GNOT(..., attn_dropout=p, dropout_seed=s)` drops the attention outputs in training mode with a keyed mask that is
+never stored (`gnot_amd.dropout` holds the threshold arithmetic and the row kernel's wrapper).
 """
 from .model import GNOT, MLP, LinearAttention, HeterogeneousNormalizedAttentionBlock  # noqa: F401
 from . import _lib  # noqa: F401

@@ -38,6 +38,7 @@ EXPORTS = [
     "gnot_mse_loss_affine", "gnot_plan_set_fourier", "gnot_fourier_embed", "gnot_fourier_embed_bwd",
     "gnot_debug_kernel_forms", "gnot_plan_set_pre_norm", "gnot_layer_norm", "gnot_layer_norm_bwd",
     "gnot_lp_loss_work_floats", "gnot_lp_loss",
+    "gnot_plan_set_dropout", "gnot_plan_set_dropout_active", "gnot_dropout_rows",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -71,7 +72,7 @@ def build(jobs=8, quiet=True):
 # every file the library's code depends on (csrc/Makefile's SRCS, its headers and its flags)
 SOURCES = ["Makefile", "gnot_common.h", "gnot_kernels.h", "x6_core.h", "pack.hip", "linear.hip", "linear2.hip",
            "chain.hip", "chain2.hip", "chainw.hip", "wgrad.hip", "state.hip", "attn.hip", "attn_mfma.hip", "misc.hip",
-           "fourier.hip", "norm.hip", "train.hip", "gather.hip", "stats.hip", "engine.cpp", "tuning.cpp"]
+           "fourier.hip", "norm.hip", "dropout.hip", "train.hip", "gather.hip", "stats.hip", "engine.cpp", "tuning.cpp"]
 
 
 def source_hash():
@@ -157,6 +158,9 @@ def _declare(lib):
     lib.gnot_lp_loss_work_floats.argtypes = [ctypes.POINTER(i64), i32, i32]
     lib.gnot_lp_loss_work_floats.restype = sz
     lib.gnot_lp_loss.argtypes = [P, P, P, ctypes.POINTER(i64), i32, i32, i32, P, P, P, P, P, P, P]
+    lib.gnot_plan_set_dropout.argtypes = [P, ctypes.c_float, P]
+    lib.gnot_plan_set_dropout_active.argtypes = [P, i32]
+    lib.gnot_dropout_rows.argtypes = [P, i64, i64, i32, P, P, i32, P, ctypes.c_uint32, ctypes.c_float, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p
@@ -191,8 +195,9 @@ def kernel_forms(plan):
     return dict(kv.split("=") for kv in text.value.decode().split())
 
 
-def probe_plan(cfg, nx=0, nf=0):
-    """Create and destroy a plan for `cfg` (the gnot_config as a dict) with the Fourier orders nx / nf: host
+def probe_plan(cfg, nx=0, nf=0, dropout=None):
+    """Create and destroy a plan for `cfg` (the gnot_config as a dict) with the Fourier orders nx / nf and, if
+    given, the dropout probability (gnot_plan_set_dropout with a placeholder key that nothing reads): host
     only.  ValueError with the library's message if it refuses the configuration."""
     lib = load()
     c = GnotConfig(**cfg)
@@ -200,6 +205,9 @@ def probe_plan(cfg, nx=0, nf=0):
     rc = lib.gnot_plan_create(ctypes.byref(c), ctypes.byref(plan))
     if rc == 0:
         rc = lib.gnot_plan_set_fourier(plan, nx, nf)
+        if rc == 0 and dropout is not None:
+            key = (ctypes.c_uint32 * 4)()
+            rc = lib.gnot_plan_set_dropout(plan, dropout, ctypes.addressof(key))
         msg = lib.gnot_last_error().decode() if rc != 0 else ""
         lib.gnot_plan_destroy(plan)
     else:

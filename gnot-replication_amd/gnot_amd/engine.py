@@ -10,6 +10,7 @@ import weakref
 import torch
 
 from . import _lib
+from . import dropout as dropout_mod
 
 
 def _ptr_array(ptrs):
@@ -17,11 +18,14 @@ def _ptr_array(ptrs):
 
 
 class Engine:
-    def __init__(self, cfg: dict, linears, fourier=(0, 0), pre_norm=None):
+    def __init__(self, cfg: dict, linears, fourier=(0, 0), pre_norm=None, dropout=0.0):
         """cfg: the 12 constructor arguments (the gnot_config: with a Fourier embedding input_dim and
         input_func_dim are the embedded widths, the Linears'); linears: nn.Linear modules in state_dict order;
         fourier: the orders (x, input functions) of gnot_plan_set_fourier -- the caller's x, the input functions
-        and their gradients then have the raw widths; pre_norm: the eps of gnot_plan_set_pre_norm (None: off)."""
+        and their gradients then have the raw widths; pre_norm: the eps of gnot_plan_set_pre_norm (None: off);
+        dropout: the probability of gnot_plan_set_dropout (a threshold of 0: off, no call) -- the engine owns
+        the device key {seed_lo, seed_hi, step, 0} its kernels read, so that the backward of a pending forward
+        regenerates that forward's mask whatever other engines have run since (write_dropout_key)."""
         self.lib = _lib.load()
         c = _lib.GnotConfig(**cfg)
         plan = ctypes.c_void_p()
@@ -32,6 +36,18 @@ class Engine:
         self.pre_norm = None if pre_norm is None else float(pre_norm)
         if self.pre_norm is not None:
             _lib.check(self.lib.gnot_plan_set_pre_norm(plan, 1, self.pre_norm))
+        self.dropout = float(dropout) if dropout_mod.threshold(dropout)[0] > 0 else 0.0
+        self.drop_key = None
+        self.drop_on = None        # what gnot_plan_set_dropout_active was last told
+        if self.dropout:
+            self.drop_key = torch.zeros(4, dtype=torch.int32, device=linears[0].weight.device)
+            # pinned staging ring of the key writes (FlatAdamW.prepare's pattern): the host may run steps ahead of
+            # the GPU; a slot is rewritten only after the copy that last read it has executed (its event)
+            self._key_ring = [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(4)] \
+                if self.drop_key.is_cuda else None
+            self._key_ev = [None] * 4
+            self._key_k = 0
+            _lib.check(self.lib.gnot_plan_set_dropout(plan, self.dropout, self.drop_key.data_ptr()))
         n = self.lib.gnot_plan_num_linears(plan)
         dims = (ctypes.c_int32 * (2 * n))()
         _lib.check(self.lib.gnot_plan_linear_dims(plan, dims))
@@ -213,6 +229,31 @@ class Engine:
             if c is not None:
                 c.ws = self.ws
                 c.arena = self.user_arena
+
+    def write_dropout_key(self, seed, step):
+        """{seed_lo, seed_hi, step, 0} into the device key, ordered on torch's current stream behind the kernels
+        that read the previous key (from pinned staging: no host wait).  Under stream capture nothing is
+        written: the caller sets the key before each replay (GNOT.set_dropout_step)."""
+        if not self.dropout or self._key_ring is None or torch.cuda.is_current_stream_capturing():
+            return
+        k = self._key_k = (self._key_k + 1) % len(self._key_ring)
+        if self._key_ev[k] is not None:
+            self._key_ev[k].synchronize()
+        h = self._key_ring[k]
+        for i, w in enumerate(dropout_mod.as_int32(dropout_mod.key_words(seed, step))):
+            h[i] = w
+        with torch.cuda.device(self.drop_key.device):
+            self.drop_key.copy_(h, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self._key_ev[k] = ev
+
+    def set_dropout_active(self, on):
+        """whether the next forward drops (gnot_plan_set_dropout_active; its backward mirrors it)"""
+        on = bool(on) and bool(self.dropout)
+        if self.dropout and on != self.drop_on:
+            _lib.check(self.lib.gnot_plan_set_dropout_active(self.plan, int(on)))
+            self.drop_on = on
 
     def forward(self, x, theta, fns, out):
         self._own_comms()

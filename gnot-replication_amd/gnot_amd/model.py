@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import dropout as dropout_mod
 from .engine import Engine
 from .fourier import check_order, width
 
@@ -144,7 +145,7 @@ class GNOT(nn.Module):
 
     def __init__(self, input_dim, theta_dim, input_func_dim, out_dim, n_attn_layers, n_attn_hidden_dim,
                  n_mlp_num_layers, n_mlp_hidden_dim, n_input_hidden_dim, n_expert, n_head, n_input_functions=0, *,
-                 x_fourier=0, fn_fourier=0, pre_norm=False):
+                 x_fourier=0, fn_fourier=0, pre_norm=False, attn_dropout=0.0, dropout_seed=0):
         """The reference's 12 arguments, then (keyword only, no reference counterpart) the orders of the
         Fourier embedding of x and of the input functions (gnot_amd.fourier; 0: none).  input_dim and
         input_func_dim stay the widths of the caller's tensors; with an order n the first Linears take
@@ -159,7 +160,16 @@ class GNOT(nn.Module):
         with the residual stream, gating, encoders and decoder unchanged (gnot_plan_set_pre_norm).  The
         parameters are the reference's; the state_dict gains one buffer, `pre_norm_eps`, so that a pre-norm
         checkpoint and a model without the option (or the reference) refuse each other on that key instead of
-        computing another function."""
+        computing another function.
+        attn_dropout, dropout_seed (keyword only; the original GNOT code's resid_drop1 / resid_drop2, which the
+        reference dropped): dropout with probability attn_dropout on the output of every attention call, the rows
+        the block's soft-MoE experts read (gnot_plan_set_dropout, gnot_amd.dropout).  Active iff
+        `self.training and attn_dropout > 0` -- the nn.Module flag, as with nn.Dropout; the grad mode does not
+        matter.  No mask is stored: every element is keyed on (dropout_seed, step, call site, sample, point,
+        column), so the backward regenerates it and a point-sharded run drops the unsharded run's elements.
+        Every active forward takes step = the model's counter and increments it (dropout_state /
+        load_dropout_state / set_dropout_step).  It adds no parameter and no buffer: the evaluated function and
+        the checkpoints are the reference's."""
         super().__init__()
         nx = check_order(x_fourier, "x_fourier")
         nf = check_order(fn_fourier, "fn_fourier")
@@ -187,6 +197,11 @@ class GNOT(nn.Module):
         self.pre_norm = bool(pre_norm)
         if self.pre_norm:
             self.register_buffer("pre_norm_eps", torch.tensor(1e-5, dtype=torch.float32))
+        T, _ = dropout_mod.threshold(attn_dropout)          # ValueError outside [0, 1)
+        dropout_mod.key_words(dropout_seed, 0)              # ValueError outside [0, 2^64)
+        self.attn_dropout = float(attn_dropout) if T > 0 else 0.0
+        self.dropout_seed = int(dropout_seed)
+        self._dropout_step = 0     # the step of the next active forward
         if nx or nf:
             # widths that do not fit the hidden width are refused here, with the engine's message (host only)
             _lib.probe_plan(self._plan_cfg, nx, nf)
@@ -211,7 +226,7 @@ class GNOT(nn.Module):
 
     def _new_engine(self):
         e = Engine(self._plan_cfg, self.linears(), fourier=(self.x_fourier, self.fn_fourier),
-                   pre_norm=float(self.pre_norm_eps) if self.pre_norm else None)
+                   pre_norm=float(self.pre_norm_eps) if self.pre_norm else None, dropout=self.attn_dropout)
         e.comm = self._comm
         e.grad_comm = self._grad_comm
         e.moe_recompute = self._moe_recompute
@@ -283,6 +298,32 @@ class GNOT(nn.Module):
         self._moe_recompute = bool(on)
         self.engine().moe_recompute = self._moe_recompute
         self._extra = []
+
+    def dropout_state(self):
+        """{p, seed, step} of the attention dropout: what a resumed run needs to drop the masks the
+        uninterrupted one would (step: the counter the next active forward takes)"""
+        return dict(p=self.attn_dropout, seed=self.dropout_seed, step=int(self._dropout_step))
+
+    def load_dropout_state(self, state):
+        """Restore the step counter of dropout_state(); a state written under another p or seed is a
+        ValueError (it belongs to another mask sequence)."""
+        for k, mine in (("p", self.attn_dropout), ("seed", self.dropout_seed)):
+            if state.get(k) != mine:
+                raise ValueError(f"load_dropout_state: the state has {k}={state.get(k)!r}, this model has {k}={mine!r}")
+        self.set_dropout_step(state["step"])
+
+    def set_dropout_step(self, k):
+        """The next active forward runs as step k.  The key {seed, k} is also written now (stream-ordered) to
+        every engine that has no backward pending -- a pending one keeps the key of its forward -- which is what
+        a captured training step reads: under capture the forward writes nothing, so call this before each
+        replay."""
+        if int(k) < 0:
+            raise ValueError("the dropout step must be >= 0")
+        self._dropout_step = int(k)
+        if self.attn_dropout and self._engine is not None:
+            for e in [self._engine] + self._extra:
+                if not e.busy():
+                    e.write_dropout_key(self.dropout_seed, self._dropout_step)
 
     def _apply(self, fn, *args, **kwargs):
         # moving / casting the module invalidates the bound parameter pointers
@@ -406,6 +447,13 @@ class GNOT(nn.Module):
         with torch.cuda.device(x.device):
             eng.prepare([int(v) for v in x_off], [[int(v) for v in o] for o in fn_offs], training, x.device,
                         n_global=None if n_global is None else [int(n) for n in n_global])
+            if self.attn_dropout:
+                # the nn.Module flag decides, as with nn.Dropout; an active forward takes the counter's step (its
+                # engine keeps that key until the forward's backward has run) and advances it
+                eng.set_dropout_active(self.training)
+                if self.training and not torch.cuda.is_current_stream_capturing():
+                    eng.write_dropout_key(self.dropout_seed, self._dropout_step)
+                    self._dropout_step += 1
             out = _GNOTFunction.apply(eng, self._cfg["out_dim"], len(fns), x, theta, *fns, *params)
         # the engine's activations now belong to this autograd node until its backward runs or the graph is
         # freed (the node is only weakly referenced)

@@ -594,15 +594,17 @@ def restore_rng_state(state, train_loader=None):
 
 
 def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, hist_test, args, train_loader=None,
-                        ema_args=None, normalizer=None):
+                        ema_args=None, normalizer=None, dropout=None):
     """Everything fit needs to continue a run bit for bit, in one torch.save of tensors (on the host) and plain
     Python values, readable with weights_only=True: the model state_dict (reference keys), the optimizer's
     and the schedule's state_dict(), the next epoch, the best metric, both histories, the host random state
     (rng_state) and the trajectory arguments `args` (TRAJECTORY_ARGS); with a weight average also `ema_args`
     (fit's ema_decay / ema_warmup; the average itself travels in the optimizer's state, the model entry holds
     the raw weights); with a normalizer its statistics ("normalizer": Normalizer.state_dict(); the model
-    entry holds the unfolded weights, which take normalised inputs).  Written under a temporary name in
-    the same directory and moved into place with os.replace: a kill in mid-write leaves the previous file."""
+    entry holds the unfolded weights, which take normalised inputs); with attention dropout its {p, seed, step}
+    ("dropout": GNOT.dropout_state(), the step counter the next training forward takes).  Written under a
+    temporary name in the same directory and moved into place with os.replace: a kill in mid-write leaves the
+    previous file."""
     state = {"model": _cpu(model.state_dict()), "optimizer": _cpu(opt.state_dict()), "schedule": sched.state_dict(),
              "next_epoch": int(next_epoch), "best": float(best), "hist_train": [float(v) for v in hist_train],
              "hist_test": [float(v) for v in hist_test], "rng": rng_state(train_loader), "args": dict(args)}
@@ -610,6 +612,8 @@ def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, h
         state["ema_args"] = dict(ema_args)
     if normalizer is not None:
         state["normalizer"] = normalizer.state_dict()
+    if dropout is not None:
+        state["dropout"] = dict(dropout)
     tmp = f"{path}.tmp{os.getpid()}"
     try:
         torch.save(state, tmp)
@@ -655,6 +659,22 @@ def _forward_batch(model, batch, dev, encoder=None):
     return model.forward_packed(x, x_off, theta, fns, fn_offs), x_off, y
 
 
+@contextlib.contextmanager
+def _eval_mode(model):
+    """the model in eval mode (no attention dropout, as nn.Dropout), its `training` flag restored on exit"""
+    was = model.training
+    model.eval()
+    try:
+        yield model
+    finally:
+        model.train(was)
+
+
+def _dropout_state(model):
+    """GNOT.dropout_state() of a model that drops (attn_dropout > 0), else None"""
+    return model.dropout_state() if getattr(model, "attn_dropout", 0.0) else None
+
+
 def _read_back(losses):
     """the 0-d device losses of many steps as Python floats (each exactly float(loss)): one device read"""
     return torch.stack(losses).tolist() if losses else []
@@ -688,7 +708,8 @@ def _batch_encoder(loader, normalizer, who):
 
 
 def evaluate(model, loader, loss_fn=None, normalizer=None):
-    """main.py:108-147: mean RelL2 over the test batches, no_grad (no activations kept).  Batches from
+    """main.py:108-147: mean RelL2 over the test batches, no_grad (no activations kept), the model in eval mode
+    (no attention dropout; its `training` flag is restored afterwards).  Batches from
     collate_padded reproduce main.py's padded evaluation; collate_packed batches the unpadded one.
     The batch losses stay on the device and are read once, behind the last batch.
     normalizer: the model takes normalised inputs and returns normalised predictions (fit's normalizer); the
@@ -704,7 +725,7 @@ def _evaluate(model, loader, loss_fn, encoder, tables=None):
     then an LpLoss): every batch's [B, C] terms are appended to it, device tensors from the same pass as its loss"""
     dev = next(model.parameters()).device
     vals = []
-    with torch.no_grad():
+    with torch.no_grad(), _eval_mode(model):
         for batch in loader:
             pred, off, y = _forward_batch(model, batch, dev, encoder)
             if tables is None:
@@ -727,7 +748,7 @@ def evaluate_table(model, loader, kind="rel2", normalizer=None):
     encoder = _batch_encoder(loader, normalizer, "evaluate_table: the loader")
     dev = next(model.parameters()).device
     tables = []
-    with torch.no_grad():
+    with torch.no_grad(), _eval_mode(model):
         for batch in loader:
             pred, off, y = _forward_batch(model, batch, dev, encoder)
             tables.append(loss_fn.terms(off, pred, y))
@@ -834,6 +855,10 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     any GPU work (normalise that block in the dataset, or leave it out of the statistics); the state file takes
     any combination.
     None (default): raw data, every call what it was.
+    A model with attention dropout (GNOT(attn_dropout=p)) drops in the training forwards only: the test pass runs
+    in eval mode and restores the flag.  The state file names {p, seed, step} in an entry of its own, "dropout";
+    resume restores the step counter and refuses a file whose p or seed differ, one that has the entry when the
+    model does not drop, and one that lacks it when the model does.
     log_components: with a test loader, every epoch also logs "Epoch k, Test Metric per component: [...]", one
     value per output channel: the MEAN OVER ALL TEST SAMPLES of the per-sample RelL2 terms (the column means of
     evaluate_table's rel2 table), taken from the same forwards as the scalar metric -- the metric pass writes its
@@ -876,6 +901,11 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             if stored.get(k) != (ema_args or {}).get(k):
                 raise ValueError(f"fit(resume=True): {state_path} was written with {k}={stored.get(k)!r}, "
                                  f"this call has {k}={(ema_args or {}).get(k)!r}")
+        stored, mine = state.get("dropout"), _dropout_state(model)
+        for k in ("p", "seed"):
+            if (stored or {}).get(k) != (mine or {}).get(k):
+                raise ValueError(f"fit(resume=True): {state_path} was written with dropout {k}={(stored or {}).get(k)!r}, "
+                                 f"this call's model has {k}={(mine or {}).get(k)!r}")
         stored = state.get("normalizer")
         if (stored is None) != (normalizer is None):
             raise ValueError(f"fit(resume=True): {state_path} "
@@ -908,6 +938,8 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
         best, hist_train, hist_test = state["best"], list(state["hist_train"]), list(state["hist_test"])
         first, skipped = state["next_epoch"], int(state["optimizer"]["skipped"])
         restore_rng_state(state["rng"], train_loader)
+        if state.get("dropout") is not None:
+            model.load_dropout_state(state["dropout"])
     try:
         for epoch in range(first, epochs):
             losses = []
@@ -955,7 +987,7 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                         save_checkpoint(model, checkpoint, normalizer)
             if state_path:       # outside the swap: the raw weights, the average inside the optimizer state
                 save_training_state(state_path, model, opt, sched, epoch + 1, best, hist_train, hist_test, args,
-                                    train_loader, ema_args, normalizer)
+                                    train_loader, ema_args, normalizer, _dropout_state(model))
     finally:
         eng.param_grads = prev       # ordinary autograd use after fit() gets .grad again
         if accum_steps > 1:

@@ -148,6 +148,26 @@ int gnot_plan_set_fourier(gnot_plan* plan, int nx, int nf);
  * gnot_plan_create and before gnot_plan_set_batch; a change invalidates the batch (set_batch + bind again). */
 int gnot_plan_set_pre_norm(gnot_plan* plan, int on, float eps);
 
+/* Keyed dropout on the attention outputs (off by default; the original GNOT code's resid_drop1 / resid_drop2,
+ * which the replicated model.py dropped).  With p > 0 every attention call's output rows -- fc_out's result, the
+ * input of the block's soft-MoE experts; gnot_debug_buffer "b{l}.a" (cross) and "b{l}.bb" (self) -- are masked in
+ * place right after fc_out, and in the backward the gradient of those rows is masked with the same mask right
+ * before fc_out's backward.  No mask is stored: element (point n of sample b, column c) of call site
+ * s = 2 l (cross attention of block l) or 2 l + 1 (self attention) is kept iff word c % 4 of
+ *     Philox4x32-10( counter = (n, b, s << 8 | c / 4, step), key = (seed_lo, seed_hi) )
+ * is at least T = floor(p 2^32 + 0.5) (computed in double), and then multiplied by fp32(2^32 / (2^32 - T));
+ * a dropped element becomes +0 whatever it held (a select, not a product).  n counts within the WHOLE sample,
+ * so a point-sharded run drops exactly the elements of the unsharded one.  key_dev: 4 uint32 in DEVICE memory,
+ * {seed_lo, seed_hi, step, 0}, read when the kernels run (a captured graph drops a fresh mask on every replay
+ * once the caller has rewritten it); a backward needs the key its forward ran with.  It must be non-null when
+ * T > 0.  p must be finite and in [0, 1) (GNOT_E_INVALID otherwise); T = 0 is off: no launch, no table, the
+ * launch sequence of a plan without the call.  Training and inference plans alike.  Call after gnot_plan_create
+ * and before gnot_plan_set_batch; a change invalidates the batch (set_batch + bind again).
+ * gnot_plan_set_dropout_active: a launch-time switch (it does not invalidate the batch; on once a p is set):
+ * gnot_forward drops only while it is on, and gnot_backward mirrors what the last gnot_forward did. */
+int gnot_plan_set_dropout(gnot_plan* plan, float p, const uint32_t* key_dev);
+int gnot_plan_set_dropout_active(gnot_plan* plan, int on);
+
 /* Input gradients (off by default).  The reference's autograd also differentiates w.r.t. x, theta and
  * the input functions when they require grad (model.py:154-173: x feeds the gating MLP and, through
  * torch.cat with the broadcast theta, the query encoder; the input functions feed their encoder
@@ -232,6 +252,15 @@ int gnot_layer_norm(const float* x, int64_t ldx, int64_t rows, int C, float eps,
                     void* stream);
 int gnot_layer_norm_bwd(const float* y, int64_t ldy, const float* rstd, const float* dy, int64_t lddy, int64_t rows,
                         int C, float* dx, int64_t lddx, int accumulate, void* stream);
+
+/* The row kernel of gnot_plan_set_dropout on its own, for bit-level tests (no plan; one launch on `stream`):
+ * x [rows, ld] fp32 in place, columns C .. ld - 1 untouched; off_dev [B + 1] the samples' row offsets and
+ * glo_dev [B] the global index of the first row of every sample (int64, device); key_dev and site as above.
+ * p = 0 (T = 0) launches nothing.  GNOT_E_INVALID before any launch for a null pointer, rows outside [1, 2^31),
+ * C outside [1, 1024], a row pitch below C, not a multiple of 4 or not below 2^31, an x that is not 16-byte
+ * aligned, B < 1, site >= 2^24, or a p outside [0, 1). */
+int gnot_dropout_rows(float* x, int64_t ld, int64_t rows, int C, const int64_t* off_dev, const int64_t* glo_dev, int B,
+                      const uint32_t* key_dev, uint32_t site, float p, void* stream);
 
 /* Backward of the last gnot_forward: dout [P, out_dim] -> every parameter gradient, written
  * (overwritten) into the gradient arena.  The same as gnot_backward_ex(plan, dout, 0, stream). */

@@ -98,7 +98,16 @@ def parse_args(argv=None):
     ap.add_argument("--pre-norm", action="store_true",
                     help="LayerNorm (no gamma / beta, eps 1e-5) on the inputs of every attention call; the "
                          "checkpoint then has one more key, pre_norm_eps, and loads only into GNOT(pre_norm=True)")
+    ap.add_argument("--attn-dropout", type=float, default=0.0, metavar="P",
+                    help="dropout with probability P in [0, 1) on the output of every attention call, in the training "
+                         "forwards only (default 0: off); the state file carries its step counter")
+    ap.add_argument("--dropout-seed", type=int, default=0, metavar="S",
+                    help="the seed of the dropout masks (default 0); a run resumes only under the seed that wrote it")
     args = ap.parse_args(argv)
+    if not (0.0 <= args.attn_dropout < 1.0):
+        ap.error("--attn-dropout takes a probability in [0, 1)")
+    if not (0 <= args.dropout_seed < 1 << 64):
+        ap.error("--dropout-seed takes an integer in [0, 2^64)")
     if args.component_weights is not None:
         try:
             args.component_weights = [float(v) for v in args.component_weights.split(",")]
@@ -140,7 +149,7 @@ def main():
     model = GNOT(x0.shape[1], len(np.atleast_1d(th0)), f0[0].shape[1], y0.shape[1], args.n_attn_layers,
                  args.n_attn_hidden_dim, args.n_mlp_num_layers, args.n_mlp_hidden_dim, args.n_input_hidden_dim,
                  args.n_expert, args.n_head, len(f0), x_fourier=args.x_fourier, fn_fourier=args.fn_fourier,
-                 pre_norm=args.pre_norm).to(dev)
+                 pre_norm=args.pre_norm, attn_dropout=args.attn_dropout, dropout_seed=args.dropout_seed).to(dev)
     dl = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=args.batch, shuffle=sh,
                                                     collate_fn=data.collate_packed if args.packed
                                                     else data.collate_padded)
