@@ -359,6 +359,20 @@ struct gnot_plan {
   int lin_f2(int l, int e, int j) const { return lin_sq(l) + 4 + E * NL + e * NL + j; }
   int lin_out(int j) const { return blk0() + L * per_block() + j; }
   int n_lin() const { return lin_out(NL - 1) + 1; }
+  // gnot_plan_set_trainable: one byte per canonical Linear; empty: all trainable.  A frozen Linear has no
+  // weight-gradient job (build_groups), so its arena ranges are never written.
+  std::vector<uint8_t> trainable;
+  bool frozen(int li) const { return !trainable.empty() && !trainable[li]; }
+  // the stage of a Linear: -1 the encoders (x MLP, gating, input-function encoders), l block l, L the decoder
+  int stage_of(int li) const { return li < blk0() ? -1 : li >= lin_out(0) ? L : (li - blk0()) / per_block(); }
+  // the lowest stage the backward enters (canonical order ascends through the stages): -1 .. L as stage_of,
+  // L + 1: nothing to do.  Input gradients come out of the encoders' chain backwards.
+  int lowest_stage() const {
+    if (input_grads) return -1;
+    for (int li = 0; li < n_lin(); ++li)
+      if (!frozen(li)) return stage_of(li);
+    return L + 1;
+  }
 
   std::string final_query() const {
     return L > 0 ? "b" + std::to_string(L - 1) + ".query2" : std::string("query0");
@@ -925,6 +939,7 @@ static void build_groups(gnot_plan* p) {
 
   auto lin_job = [&](WgradGroup& G, int li, const float* dz, long lddz, const float* x, long ldx, int gelu,
                      long rows) {
+    if (p->frozen(li)) return;
     WgradJob J{};
     J.dz = dz; J.lddz = lddz; J.x = x; J.ldx = ldx; J.x_gelu = gelu;
     J.out = p->lin_o[li]; J.in = p->lin_i[li];
@@ -937,6 +952,7 @@ static void build_groups(gnot_plan* p) {
   // a q / k / v projection's gradients: dz in heads of dh; padded heads: one job per head (its dhr real
   // rows of the canonical dW / db)
   auto lin_job_heads = [&](WgradGroup& G, int li, const float* dz, long lddz, const float* x, long ldx, long rows) {
+    if (p->frozen(li)) return;
     if (!p->head_padded()) {
       lin_job(G, li, dz, lddz, x, ldx, 0, rows);
       return;
@@ -969,6 +985,7 @@ static void build_groups(gnot_plan* p) {
         if (j == 0) {
           lin_job(C.wg, C.firsts[c] + j, dzp, D, x0.p, x0.ld, 0, rows);
         } else if (direct && j == NL - 1) {
+          if (p->frozen(C.firsts[c] + j)) continue;      // no job whose scale to set
           lin_job(C.wg, C.firsts[c] + j, p->P_("dquery"), D, at(save, ((long)c * NL + j - 1) * rows * D), D, 1, rows);
           C.wg.jobs.back().scale = at(sc.p, (long)c);
           C.wg.jobs.back().ldscale = (int)sc.ld;
@@ -1527,6 +1544,36 @@ extern "C" int gnot_plan_set_moe_recompute(gnot_plan* p, int on) {
   return GNOT_OK;
 }
 
+extern "C" int gnot_plan_set_trainable(gnot_plan* p, const uint8_t* mask) {
+  if (!p) return fail(GNOT_E_INVALID, "null plan");
+  std::vector<uint8_t> t;
+  if (mask) {
+    t.assign(mask, mask + p->n_lin());
+    for (auto& b : t) b = b ? 1 : 0;
+    if (std::find(t.begin(), t.end(), (uint8_t)0) == t.end()) t.clear();     // all trainable: the default
+  }
+  if (t != p->trainable) {
+    p->trainable.swap(t);
+    p->batch_set = false;          // the weight-gradient job lists change: set_batch + bind again
+    p->ws_bound = false;
+  }
+  return GNOT_OK;
+}
+
+extern "C" int gnot_debug_backward_plan(const gnot_plan* p, int* wgrad_jobs, int* lowest_stage) {
+  if (!p || !wgrad_jobs || !lowest_stage) return fail(GNOT_E_INVALID, "null argument");
+  if (!p->batch_set) return fail(GNOT_E_STATE, "set_batch first");
+  int jobs = 0;
+  if (p->training) {
+    for (const Chain& C : p->chains) jobs += (int)C.wg.jobs.size();
+    for (int l = 0; l < p->L; ++l) jobs += (int)(p->wg_self[l].jobs.size() + p->wg_cross[l].jobs.size());
+    jobs += (int)p->wg_fnkv.jobs.size();
+  }
+  *wgrad_jobs = jobs;
+  *lowest_stage = p->lowest_stage();
+  return GNOT_OK;
+}
+
 extern "C" int gnot_plan_set_input_grads(gnot_plan* p, int on) {
   if (!p) return fail(GNOT_E_INVALID, "null plan");
   if (p->input_grads != (on != 0)) {
@@ -1783,8 +1830,20 @@ extern "C" int gnot_plan_bind_workspace_async(gnot_plan* p, void* workspace, siz
   // a padded width: the pad columns of rows that kernels write per head only (the attention backward's
   // dq / dk / dv, du) are read as exact zeros by the next backward-data products: clear the activation
   // part of the workspace once per bind (the tables follow it, uploaded after this on the same stream)
-  if (p->padded())
-    GNOT_CK(hipMemsetAsync(p->ws, 0, p->bufs["__tables"].off, static_cast<hipStream_t>(stream)));
+  // The ranges of frozen Linears in a workspace arena are left out: nothing writes them (gnot_plan_set_trainable)
+  if (p->padded()) {
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    size_t from = 0;
+    if (!p->user_grads && p->training)
+      for (int li = 0; li < p->n_lin(); ++li) {
+        if (!p->frozen(li)) continue;
+        const size_t lo = p->bufs["grads"].off + (size_t)p->grad_off[2 * li] * 4;
+        const size_t hi = p->bufs["grads"].off + ((size_t)p->grad_off[2 * li + 1] + p->lin_o[li]) * 4;
+        if (lo > from) GNOT_CK(hipMemsetAsync(p->ws + from, 0, lo - from, s));
+        from = hi;
+      }
+    GNOT_CK(hipMemsetAsync(p->ws + from, 0, p->bufs["__tables"].off - from, s));
+  }
   if (!p->side2) GNOT_CK(hipStreamCreateWithFlags(&p->side2, hipStreamNonBlocking));
   if (!p->side) {
     // same priority as the caller's stream: measured on MI355X, a low- (or high-) priority side
@@ -2408,6 +2467,14 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
   const int D = p->D, E = p->E, NL = p->NL;
   float* dquery = p->P_("dquery");
   float* stage = p->P_("stage");
+  // the lowest stage that holds a trainable Linear (gnot_plan_set_trainable): the backward runs from the decoder
+  // down to it and issues no kernel of the stages below; nothing trainable and no input gradients: nothing at all
+  const int stop = p->lowest_stage();
+  if (stop > p->L) {
+    p->bwd_done = true;
+    p->ig_reduced = false;
+    return GNOT_OK;
+  }
   p->readers.clear();
   p->deferred.clear();
   if (p->grad_comm_live) {                   // the comm stream joins here (a first-level fork of the caller's)
@@ -2459,7 +2526,7 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
     ChainArgs a = bwd_args(p->ch_out(), p->P_("dout"), p->bufs["dout"].ld, "dquery");
     GNOT_RUN(chain_bwd(c, p->ch_out(), a, "chain_bwd"));
   }
-  for (int l = p->L - 1; l >= 0; --l) {
+  for (int l = p->L - 1; l >= std::max(stop, 0); --l) {
     // ffn2 experts: query2 = query1 + sum_e s_e ffn2_e(bb)   (model.py:134-137)
     for (int m = 2; m >= 1; --m) {
       const bool m1 = (m == 1);
@@ -2486,8 +2553,12 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
       GNOT_RUN(attn_backward(c, l, m1));
     }
   }
-  // the input-function branch again runs on side2, concurrently with the query encoder and gating
-  const bool br = p->I > 0;
+  // the input-function branch again runs on side2, concurrently with the query encoder and gating.  A backward
+  // that stops above the encoders (stop >= 0) enters it only for the key/value weight gradients of the blocks it
+  // ran, and only when one of them is trainable.
+  const bool enc = stop < 0;
+  const bool kv = p->I > 0 && p->L > 0 && (enc || !p->wg_fnkv.jobs.empty());
+  const bool br = p->I > 0 && (enc || kv);
   Ctx cf{p, br ? p->side2 : c.s};
   // ranks issue their gradient collectives in one host order whatever serial_wgrad() says (it is chosen
   // per rank from the local point count): a forked rank still holds the last attention call's groups
@@ -2499,42 +2570,44 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
     GNOT_CK(hipStreamWaitEvent(cf.s, fork, 0));
   }
   // dK, dV of every (block, input function), the encodings' gradient and the key/value weight
-  // gradients, batched over blocks
-  if (p->I > 0 && p->L > 0) {
-    GNOT_CK(launch_attn_kv_bwd(p->kv_bwd_batch, nullptr, p->d_kvbwd_jobs, (int)p->kvbwd_jobs.size(),
+  // gradients, batched over blocks (the jobs are in block order: those of the blocks that ran are a suffix)
+  if (kv) {
+    const int l0 = std::max(stop, 0);
+    GNOT_CK(launch_attn_kv_bwd(p->kv_bwd_batch, nullptr, p->d_kvbwd_jobs + (long)l0 * p->I, (p->L - l0) * p->I,
                                p->kv_batch_maxchunks, p->H, p->dh, cf.s));
-    for (size_t k = 0; k < p->d_dfn_jobs.size(); ++k)
-      GNOT_CK(launch_linear_batch(p->d_dfn_jobs[k], p->I, (int)p->Qmax(), D, D > 512 ? D / 2 : D, p->dh, cf.s));
+    if (enc)
+      for (size_t k = 0; k < p->d_dfn_jobs.size(); ++k)
+        GNOT_CK(launch_linear_batch(p->d_dfn_jobs[k], p->I, (int)p->Qmax(), D, D > 512 ? D / 2 : D, p->dh, cf.s));
     GNOT_RUN(run_wgrad_side(cf, p->wg_fnkv, {}));
     // pre-norm: dfn{i} is so far the gradient of the normalised encodings; pulled through the norm in place
     // (a row is read whole before it is written) before the encoder's chain backward reads it
-    if (p->pre_norm)
+    if (enc && p->pre_norm)
       for (int i = 0; i < p->I; ++i) {
         const std::string si = std::to_string(i);
         float* dfn = p->P_("dfn" + si);
         GNOT_CK(launch_layer_norm_bwd(p->P_("fnn" + si), D, p->P_("fnr" + si), dfn, D, p->Q[i], p->Dr, dfn, D, 0, cf.s));
       }
   }
-  if (p->I > 0 && p->L == 0)   // encodings unused by the output: zero gradients
-    for (int i = 0; i < p->I; ++i)
-      GNOT_CK(hipMemsetAsync(p->P_("dfn" + std::to_string(i)), 0, p->Q[i] * D * 4, cf.s));
-  // input-function encoders (their inputs need no gradient)
-  for (int i = 0; i < p->I; ++i) {
-    const std::string si = std::to_string(i);
-    ChainArgs a = bwd_args(p->ch_fn(i), p->P_("dfn" + si), D, p->input_grads ? "dfnin" + si : std::string());
-    GNOT_RUN(chain_bwd(cf, p->ch_fn(i), a, "chain_bwd"));
-  }
-  // query encoder
-  {
-    ChainArgs a = bwd_args(p->ch_x(), dquery, D, p->input_grads ? "dxin" : "");
-    GNOT_RUN(chain_bwd(c, p->ch_x(), a, "chain_bwd"));
-  }
-  // gating: d scores accumulated over every MoE above -> softmax backward -> chain.  With the weight
-  // gradients forked and an input-function branch, the gating's own group runs HERE after the branch has
-  // joined, on the branch's slab (free by then): forked, it queued behind the query encoder's group on the
-  // side stream and ended the step ~45 us later (configs[1] trace); its all-reduce keeps its place, last
-  const bool gate_here = br && !p->serial_wgrad();
-  {
+  const bool gate_here = enc && br && !p->serial_wgrad();
+  if (enc) {
+    if (p->I > 0 && p->L == 0)   // encodings unused by the output: zero gradients
+      for (int i = 0; i < p->I; ++i)
+        GNOT_CK(hipMemsetAsync(p->P_("dfn" + std::to_string(i)), 0, p->Q[i] * D * 4, cf.s));
+    // input-function encoders (their inputs need no gradient)
+    for (int i = 0; i < p->I; ++i) {
+      const std::string si = std::to_string(i);
+      ChainArgs a = bwd_args(p->ch_fn(i), p->P_("dfn" + si), D, p->input_grads ? "dfnin" + si : std::string());
+      GNOT_RUN(chain_bwd(cf, p->ch_fn(i), a, "chain_bwd"));
+    }
+    // query encoder
+    {
+      ChainArgs a = bwd_args(p->ch_x(), dquery, D, p->input_grads ? "dxin" : "");
+      GNOT_RUN(chain_bwd(c, p->ch_x(), a, "chain_bwd"));
+    }
+    // gating: d scores accumulated over every MoE above -> softmax backward -> chain.  With the weight
+    // gradients forked and an input-function branch, the gating's own group runs HERE after the branch has
+    // joined, on the branch's slab (free by then): forked, it queued behind the query encoder's group on the
+    // side stream and ended the step ~45 us later (configs[1] trace); its all-reduce keeps its place, last
     // (its incoming gradient is dscore, no dY)
     ChainArgs a = bwd_args(p->ch_gate(), nullptr, 0, p->input_grads ? "dxg" : "");
     // gate_here: the launch alone (its flush is the query encoder's group: side launch after this kernel)
@@ -2833,6 +2906,69 @@ extern "C" int gnot_adamw_step_ema(float* param, const float* grad, float* exp_a
   GNOT_CK(launch_adamw_update(param, grad, exp_avg, exp_avg_sq, ema, n, hyper, clip, guard,
                               static_cast<hipStream_t>(stream)));
   return GNOT_OK;
+}
+
+// the host copy of a slice table {begin, len, group}: rows sorted and disjoint inside [0, n), 1 <= len <= 8192,
+// 0 <= group < G (G < 0: the caller does not read the group column, it is not checked); one workgroup per row,
+// so fewer than 2^24 rows as for gnot_grad_clip's partials
+static int check_slices(const char* who, const int64_t* slices_host, int64_t nslices, int64_t n, int64_t G) {
+  if (!slices_host) return fail(GNOT_E_INVALID, std::string(who) + ": null slices_host");
+  if (nslices < 1 || nslices >= (1L << 24)) return fail(GNOT_E_INVALID, std::string(who) + ": nslices out of range");
+  // every step of a training loop walks the table here: integer compares alone, the message only on a refusal
+  int64_t end = 0;
+  for (int64_t k = 0; k < nslices; ++k) {
+    const int64_t begin = slices_host[3 * k], len = slices_host[3 * k + 1], group = slices_host[3 * k + 2];
+    const char* bad = (len < 1 || len > 8192) ? " has a length outside [1, 8192]"
+                      : begin < end           ? " is not sorted behind and disjoint from the one before it"
+                      : begin > n - len       ? " does not lie inside [0, n)"
+                      : (G >= 0 && (group < 0 || group >= G)) ? " names a group outside [0, G)" : nullptr;
+    if (bad) return fail(GNOT_E_INVALID, std::string(who) + ": slice " + std::to_string(k) + bad);
+    end = begin + len;
+  }
+  return GNOT_OK;
+}
+
+extern "C" int gnot_adamw_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema,
+                                      int64_t n, const float* hyper, const float* ghyper, int G,
+                                      const int64_t* slices_dev, const int64_t* slices_host, int64_t nslices,
+                                      const float* clip, int32_t* guard, void* stream) {
+  if (!adamw_pointers(param, grad, exp_avg, exp_avg_sq, hyper) || !ghyper || !slices_dev || n < 1 || G < 1)
+    return fail(GNOT_E_INVALID, "bad adamw_step_groups arguments");
+  if (guard && !clip) return fail(GNOT_E_INVALID, "adamw_step_groups: a guard needs a clip");
+  if (ema && ema == param) return fail(GNOT_E_INVALID, "adamw_step_groups: ema must not alias param");
+  if (int rc = check_slices("adamw_step_groups", slices_host, nslices, n, G)) return rc;
+  GNOT_CK(launch_adamw_groups(param, grad, exp_avg, exp_avg_sq, ema, hyper, ghyper,
+                              reinterpret_cast<const long*>(slices_dev), nslices, clip, guard,
+                              static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+// gnot_grad_norm_groups (norm_only) and gnot_grad_clip_groups; the group column is not read by the norm
+static int grad_norm_groups(const char* who, const float* grad, int64_t n, const float* hyper, float max_norm,
+                            int norm_only, const int64_t* slices_dev, const int64_t* slices_host, int64_t nslices,
+                            float* work, float* clip, void* stream) {
+  if (!grad || !hyper || !slices_dev || !work || !clip || n < 1)
+    return fail(GNOT_E_INVALID, std::string("bad ") + who + " arguments");
+  if (int rc = check_slices(who, slices_host, nslices, n, -1)) return rc;
+  GNOT_CK(launch_grad_norm_slices(grad, reinterpret_cast<const long*>(slices_dev), nslices, hyper, max_norm, norm_only,
+                                  work, clip, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" int gnot_grad_norm_groups(const float* grad, int64_t n, const float* hyper, const int64_t* slices_dev,
+                                     const int64_t* slices_host, int64_t nslices, float* work, float* clip,
+                                     void* stream) {
+  return grad_norm_groups("grad_norm_groups", grad, n, hyper, 1.0f, 1, slices_dev, slices_host, nslices, work, clip,
+                          stream);
+}
+
+extern "C" int gnot_grad_clip_groups(const float* grad, int64_t n, const float* hyper, float max_norm,
+                                     const int64_t* slices_dev, const int64_t* slices_host, int64_t nslices,
+                                     float* work, float* clip, void* stream) {
+  if (!(max_norm > 0.f) || !std::isfinite(max_norm))
+    return fail(GNOT_E_INVALID, "grad_clip_groups: max_norm must be positive and finite");
+  return grad_norm_groups("grad_clip_groups", grad, n, hyper, max_norm, 0, slices_dev, slices_host, nslices, work, clip,
+                          stream);
 }
 
 // gnot_gather_rows (stats == nullptr) and gnot_gather_rows_affine

@@ -385,6 +385,17 @@ hipError_t launch_ema_update(float* ema, const float* param, long n, const float
 // stored parameter fused in; hyper then has 9 floats, hyper[8] the EMA weight.  n <= 0 launches nothing.
 hipError_t launch_adamw_update(float* param, const float* grad, float* m, float* v, float* ema, long n,
                                const float* hyper, const float* clip, int* guard, hipStream_t s);
+// The slice-table forms (gnot_adamw_step_groups, gnot_grad_norm_groups, gnot_grad_clip_groups).  slices: device
+// rows of three longs {begin, len, group}, 1 <= len <= 8192, validated by the caller; nslices >= 1, one workgroup
+// per row; nothing outside the rows is read or written.
+// The norm stages over the rows' elements: work nslices floats, clip as above; norm_only: no max_norm, clip[1] = 1
+hipError_t launch_grad_norm_slices(const float* grad, const long* slices, long nslices, const float* hyper,
+                                   float max_norm, int norm_only, float* work, float* clip, hipStream_t s);
+// launch_adamw_update's element expression with lr = hyper[0] * ghyper[group][0] and weight_decay =
+// ghyper[group][1] (ghyper: device, two floats per group)
+hipError_t launch_adamw_groups(float* param, const float* grad, float* m, float* v, float* ema, const float* hyper,
+                               const float* ghyper, const long* slices, long nslices, const float* clip, int* guard,
+                               hipStream_t s);
 
 
 // ------------------------------------------------------------------ batch assembly (gather.hip)

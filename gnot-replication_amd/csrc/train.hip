@@ -419,12 +419,9 @@ constexpr long kClipSlice = 8192;   // elements per stage-1 workgroup: 8 float4 
 
 long grad_clip_partials(long n) { return n < 1 ? 0 : (n + kClipSlice - 1) / kClipSlice; }
 
-__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ grad, long n,
-                                                         float* __restrict__ partial) {
-  __shared__ float red[256];
-  const long s0 = (long)blockIdx.x * kClipSlice;
-  const int len = (int)min(kClipSlice, n - s0);
-  const float* p = grad + s0;
+// sum g^2 over p[0, len), 1 <= len <= kClipSlice, by the 256 threads of a workgroup in a fixed order (every thread
+// returns the sum)
+__device__ __forceinline__ float slice_sumsq(const float* __restrict__ p, int len, float* red) {
   // 16-byte loads over the aligned body of the slice; the (up to 3) elements before and after it one by one
   const int head = min(len, (int)((4 - (((uintptr_t)p >> 2) & 3)) & 3));
   const int body4 = (len - head) >> 2;
@@ -447,7 +444,27 @@ __global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict
     const float g = p[head + 4 * body4 + threadIdx.x];
     a1 = fmaf(g, g, a1);
   }
-  const float sum = block_sum((a0 + a1) + (a2 + a3), red);
+  return block_sum((a0 + a1) + (a2 + a3), red);
+}
+
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ grad, long n,
+                                                         float* __restrict__ partial) {
+  __shared__ float red[256];
+  const long s0 = (long)blockIdx.x * kClipSlice;
+  const float sum = slice_sumsq(grad + s0, (int)min(kClipSlice, n - s0), red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+// The same stage 1 over a slice table (gnot_grad_norm_groups / gnot_grad_clip_groups): workgroup k sums g^2 over
+// [begin, begin + len) of row k = {begin, len, group}, so an element outside every row is never read.
+constexpr int kSliceCols = 3;
+
+__global__ void __launch_bounds__(256) grad_sumsq_slices_kernel(const float* __restrict__ grad,
+                                                                const long* __restrict__ slices,
+                                                                float* __restrict__ partial) {
+  __shared__ float red[256];
+  const long* S = slices + (long)blockIdx.x * kSliceCols;
+  const float sum = slice_sumsq(grad + S[0], (int)S[1], red);
   if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
@@ -475,6 +492,15 @@ static hipError_t launch_grad_norm_stages(const float* grad, long n, const float
   const long nparts = grad_clip_partials(n);
   hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nparts), dim3(256), 0, s, grad, n, work);
   hipLaunchKernelGGL(grad_clip_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)work, nparts, hyper, max_norm,
+                     norm_only, clip);
+  return hipGetLastError();
+}
+
+// work: nslices floats; the table's rows are validated by the caller
+hipError_t launch_grad_norm_slices(const float* grad, const long* slices, long nslices, const float* hyper,
+                                   float max_norm, int norm_only, float* work, float* clip, hipStream_t s) {
+  hipLaunchKernelGGL(grad_sumsq_slices_kernel, dim3((unsigned)nslices), dim3(256), 0, s, grad, slices, work);
+  hipLaunchKernelGGL(grad_clip_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)work, nslices, hyper, max_norm,
                      norm_only, clip);
   return hipGetLastError();
 }
@@ -561,6 +587,74 @@ hipError_t launch_adamw_update(float* param, const float* grad, float* m, float*
   else
     hipLaunchKernelGGL(adamw_update_kernel<false>, dim3(flat_grid(n)), dim3(256), 0, s, param, grad, m, v, ema, n,
                        hyper, clip, guard);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- AdamW per slice, with group constants
+// adamw_update_kernel's element expression over a slice table instead of [0, n): workgroup k updates the elements
+// [begin, begin + len) of row k = {begin, len, group} (len <= kClipSlice) with lr = hyper[0] * ghyper[group][0],
+// the product rounded to fp32 once, and weight_decay = ghyper[group][1]; hyper[4] is not read.  An element outside
+// every row is neither read nor written, in any array.  The moment's inner term is always the rounded-product
+// form fmaf(gi, coef, -mi) of the clipped update (coef = 1.0f without a clip): with one group {1, hyper[4]} whose
+// rows cover [0, n) the results are adamw_update_kernel's bit for bit, for the plain update when hyper[7] is a
+// power of two.  guard: as there, written by thread 0 of workgroup 0 (at least one row).
+template <bool kEma>
+__global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           float* __restrict__ ema, const float* __restrict__ hyper,
+                                                           const float* __restrict__ ghyper,
+                                                           const long* __restrict__ slices,
+                                                           const float* __restrict__ clip, int* __restrict__ guard) {
+#pragma clang fp contract(off)
+  if (guard) {
+    const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (!finite) guard[0] = guard[0] + 1;
+      guard[1] = finite ? 0 : 1;
+    }
+    if (!finite) return;
+  }
+  const long* S = slices + (long)blockIdx.x * kSliceCols;
+  const long begin = S[0];
+  const int len = (int)S[1];
+  const float* gh = ghyper + 2 * S[2];
+  const float lr = hyper[0] * gh[0], wd = gh[1];
+  const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3];
+  const float bc1 = hyper[5], bc2 = hyper[6], gs = hyper[7];
+  const float step_size = lr / bc1;
+  const float bc2_sqrt = sqrtf(bc2);
+  const float decay = fmaf(-lr, wd, 1.0f);               // decoupled weight decay
+  const float coef = clip ? clip[1] : 1.0f;
+  const float w = kEma ? hyper[8] : 0.f;
+  for (int j = threadIdx.x; j < len; j += 256) {
+    const long i = begin + j;
+    const float gi = grad[i] * gs;
+    const float g = gi * coef;
+    float mi = m[i];
+    mi = fmaf(1.0f - b1, fmaf(gi, coef, -mi), mi);
+    const float vi = fmaf(g, (1.0f - b2) * g, v[i] * b2);
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    const float p = fmaf(decay, param[i], -(step_size * (mi / denom)));
+    param[i] = p;
+    m[i] = mi;
+    v[i] = vi;
+    if (kEma) {
+      const float e = ema[i];
+      ema[i] = fmaf(w, p - e, e);
+    }
+  }
+}
+
+// nslices >= 1; the table's rows are validated by the caller.  ema, clip, guard as in launch_adamw_update.
+hipError_t launch_adamw_groups(float* param, const float* grad, float* m, float* v, float* ema, const float* hyper,
+                               const float* ghyper, const long* slices, long nslices, const float* clip, int* guard,
+                               hipStream_t s) {
+  if (ema)
+    hipLaunchKernelGGL(adamw_groups_kernel<true>, dim3((unsigned)nslices), dim3(256), 0, s, param, grad, m, v, ema,
+                       hyper, ghyper, slices, clip, guard);
+  else
+    hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3((unsigned)nslices), dim3(256), 0, s, param, grad, m, v, ema,
+                       hyper, ghyper, slices, clip, guard);
   return hipGetLastError();
 }
 

@@ -39,6 +39,8 @@ EXPORTS = [
     "gnot_debug_kernel_forms", "gnot_plan_set_pre_norm", "gnot_layer_norm", "gnot_layer_norm_bwd",
     "gnot_lp_loss_work_floats", "gnot_lp_loss",
     "gnot_plan_set_dropout", "gnot_plan_set_dropout_active", "gnot_dropout_rows",
+    "gnot_adamw_step_groups", "gnot_grad_norm_groups", "gnot_grad_clip_groups",
+    "gnot_plan_set_trainable", "gnot_debug_backward_plan",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -161,6 +163,11 @@ def _declare(lib):
     lib.gnot_plan_set_dropout.argtypes = [P, ctypes.c_float, P]
     lib.gnot_plan_set_dropout_active.argtypes = [P, i32]
     lib.gnot_dropout_rows.argtypes = [P, i64, i64, i32, P, P, i32, P, ctypes.c_uint32, ctypes.c_float, P]
+    lib.gnot_adamw_step_groups.argtypes = [P, P, P, P, P, i64, P, P, i32, P, ctypes.POINTER(i64), i64, P, P, P]
+    lib.gnot_grad_norm_groups.argtypes = [P, i64, P, P, ctypes.POINTER(i64), i64, P, P, P]
+    lib.gnot_grad_clip_groups.argtypes = [P, i64, P, ctypes.c_float, P, ctypes.POINTER(i64), i64, P, P, P]
+    lib.gnot_plan_set_trainable.argtypes = [P, P]
+    lib.gnot_debug_backward_plan.argtypes = [P, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p
@@ -193,6 +200,14 @@ def kernel_forms(plan):
     text = ctypes.create_string_buffer(512)
     check(load().gnot_debug_kernel_forms(plan, text, len(text)))
     return dict(kv.split("=") for kv in text.value.decode().split())
+
+
+def backward_plan(plan):
+    """gnot_debug_backward_plan of a plan whose batch is set: (weight-gradient jobs over all groups, the lowest
+    stage the backward enters: -1 encoders, l block l, L the decoder alone, L + 1 nothing).  Host only."""
+    jobs, stage = ctypes.c_int(), ctypes.c_int()
+    check(load().gnot_debug_backward_plan(plan, ctypes.byref(jobs), ctypes.byref(stage)))
+    return jobs.value, stage.value
 
 
 def probe_plan(cfg, nx=0, nf=0, dropout=None):

@@ -72,6 +72,8 @@ class Engine:
         self.bf16 = False          # bf16 arithmetic mode of the MFMA kernels up to d = 256 (gnot_plan_set_precision)
         self.input_grads = False   # also differentiate x, theta, input functions (gnot_plan_set_input_grads)
         self.user_arena = None     # caller-owned flat fp32 gradient arena (GNOT.set_grad_arena); None: the workspace's
+        self.trainable = None      # one bool per Linear (gnot_plan_set_trainable); None: all trainable, no call
+        self._mask_sent = False    # the plan has been given a mask (a later None must take it back)
         # options of the next backward(s), shared by the engines of one module (GNOT.backward_options)
         self.bwd_opts = {"accumulate": False, "reduce": True}
         self.fwd_token = 0
@@ -124,7 +126,8 @@ class Engine:
         geom = (tuple(x_off), tuple(tuple(o) for o in fn_offs), bool(training),
                 tuple(n_global) if n_global is not None else None, bool(self.moe_recompute), bool(self.bf16),
                 bool(self.input_grads) and bool(training), id(self.grad_comm),
-                None if self.user_arena is None else (self.user_arena.data_ptr(), self.user_arena.numel()))
+                None if self.user_arena is None else (self.user_arena.data_ptr(), self.user_arena.numel()),
+                None if self.trainable is None else tuple(bool(t) for t in self.trainable))
         if geom == self.geom:
             return
         B = len(x_off) - 1
@@ -146,6 +149,12 @@ class Engine:
             _lib.check(self.lib.gnot_plan_set_grad_arena(self.plan, self.user_arena.data_ptr(), self.user_arena.numel()))
         else:
             _lib.check(self.lib.gnot_plan_set_grad_arena(self.plan, None, 0))
+        if self.trainable is not None or self._mask_sent:     # the default model issues the calls it always did
+            if self.trainable is not None and len(self.trainable) != len(self.dims):
+                raise ValueError(f"the trainable mask has {len(self.trainable)} entries, the plan {len(self.dims)} Linears")
+            mask = None if self.trainable is None else (ctypes.c_uint8 * len(self.dims))(*[int(bool(t)) for t in self.trainable])
+            _lib.check(self.lib.gnot_plan_set_trainable(self.plan, mask))
+            self._mask_sent = self.trainable is not None
         xo = (ctypes.c_int64 * (B + 1))(*x_off)
         flat = [v for o in fn_offs for v in o]
         fo = (ctypes.c_int64 * max(1, len(flat)))(*flat) if flat else None
@@ -188,6 +197,11 @@ class Engine:
             self.grad_layout = layout          # offsets relative to the arena start
             last_o = self.dims[-1][0]
             self.grad_arena = wsf[base // 4: base // 4 + offs[2 * n - 1] + last_o]
+
+    def backward_plan(self):
+        """(weight-gradient jobs, lowest stage the backward enters) of the current batch (gnot_debug_backward_plan):
+        -1 the encoders, l block l, L the decoder alone, L + 1 nothing.  Needs no GPU."""
+        return _lib.backward_plan(self.plan)
 
     def kernel_forms(self):
         """The kernel forms the plan chose for the current batch geometry (gnot_debug_kernel_forms) as a dict,

@@ -103,6 +103,7 @@ class _GNOTFunction(torch.autograd.Function):
         ctx.nfn = nfn
         ctx.in_shapes = (tuple(x.shape), tuple(theta.shape), [tuple(f.shape) for f in fns])
         ctx.nparams = len(rest) - nfn
+        ctx.live = engine.trainable       # the mask of the plan this forward ran on
         return out
 
     @staticmethod
@@ -133,9 +134,11 @@ class _GNOTFunction(torch.autograd.Function):
         flat = eng.grad_arena.clone()
         eng.grad_flat = flat        # the step's gradient buffer (sample-DP all-reduces it in place)
         ws, bs = [], []
-        for off_w, off_b, shape_w, nb in eng.grad_layout:
-            ws.append(flat[off_w:off_w + shape_w[0] * shape_w[1]].view(shape_w))
-            bs.append(flat[off_b:off_b + nb])
+        live = ctx.live or [True] * len(eng.grad_layout)
+        for (off_w, off_b, shape_w, nb), on in zip(eng.grad_layout, live):
+            # a frozen Linear's arena ranges are never written: no gradient (torch's None)
+            ws.append(flat[off_w:off_w + shape_w[0] * shape_w[1]].view(shape_w) if on else None)
+            bs.append(flat[off_b:off_b + nb] if on else None)
         # params were passed as (all weights..., all biases...)
         return head + (*ws, *bs)
 
@@ -214,6 +217,7 @@ class GNOT(nn.Module):
         self._bf16 = False
         self._grad_arena = None    # caller-owned gradient arena (set_grad_arena); survives engine rebuilds
         self._bwd_opts = {"accumulate": False, "reduce": True}   # backward_options; one dict for every engine
+        self._trainable = None     # the mask the engines hold (trainable_mask); None: every Linear trainable
 
     # canonical Linear order == named_parameters() order of the reference module
     def linears(self):
@@ -233,6 +237,7 @@ class GNOT(nn.Module):
         e.bf16 = self._bf16
         e.user_arena = self._grad_arena
         e.bwd_opts = self._bwd_opts
+        e.trainable = self._trainable
         return e
 
     def engine(self):
@@ -270,6 +275,16 @@ class GNOT(nn.Module):
         e.grad_hook = prim.grad_hook
         self._extra.append(e)
         return e
+
+    def trainable_mask(self):
+        """One bool per Linear in canonical order -- trainable when its weight or its bias requires grad (the
+        Linear is the engine's unit: dW and db come out of one job) -- or None when every Linear is.  Frozen
+        Linears get no weight-gradient job, their ranges of the gradient arena are never written, their
+        parameters receive no .grad, and the backward stops at the lowest stage that holds a trainable Linear
+        (gnot_plan_set_trainable).  forward_packed hands it to every engine; a changed flag re-plans at the
+        next forward, as set_precision does."""
+        mask = tuple(bool(l.weight.requires_grad or l.bias.requires_grad) for l in self.linears())
+        return None if all(mask) else mask
 
     def set_precision(self, dtype):
         """'fp32' (default: the reference's fp32 arithmetic, bf16x6-exact on the MFMA) or 'bf16' (BASELINE
@@ -441,6 +456,12 @@ class GNOT(nn.Module):
         grad = torch.is_grad_enabled()
         inputs_grad = grad and (x.requires_grad or theta.requires_grad or any(f.requires_grad for f in fns))
         training = grad and (inputs_grad or any(p.requires_grad for p in params))
+        mask = self.trainable_mask() if training else self._trainable
+        if mask != self._trainable:
+            self._trainable = mask
+            if self._engine is not None:
+                self._engine.trainable = mask
+            self._extra = []           # settings changed: spare engines are rebuilt on demand
         eng = self._engine_for(training)
         eng.input_grads = inputs_grad
         # every launch (and the plan's side streams) on x's device, whatever device is current

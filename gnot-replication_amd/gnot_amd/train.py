@@ -31,9 +31,14 @@
 * `LpLoss(kind, component_weights, normalizer)` -- the original GNOT code's named losses (rel2, rel1, relinf, mse,
   l1, linf) with per-component weights through gnot_lp_loss, its `terms()` per (sample, channel),
   `evaluate_table` (the per-sample error table of a test set) and `fit(log_components=True)`.
+* `param_groups` / `FlatAdamW(groups=, layout=)` / `fit(freeze=, no_decay=, lr_scale=)` -- fine-tuning: fnmatch
+  patterns over the state_dict names resolve to frozen tensors and AdamW parameter groups, and the norm and the
+  update run over a slice table of the trainable tensors (gnot_grad_norm_groups / gnot_grad_clip_groups,
+  gnot_adamw_step_groups), so a frozen tensor is neither read nor written.
 """
 import contextlib
 import ctypes
+import fnmatch
 import math
 import os
 
@@ -300,6 +305,83 @@ def flatten_parameters(model):
     return flat
 
 
+# ------------------------------------------------------------------ frozen tensors and AdamW parameter groups
+SLICE = 8192        # elements per row of a slice table: kClipSlice of csrc/train.hip, the bound gnot_hip.h states
+
+
+def arena_layout(model):
+    """[(state_dict name, numel)] of the 2 L tensors of the flat arena in its order (W0, b0, W1, b1, ...: the
+    engine's gradient arena, flatten_parameters' buffer).  Host only."""
+    names = {id(p): n for n, p in model.named_parameters()}
+    return [(names[id(p)], p.numel()) for l in model.linears() for p in (l.weight, l.bias)]
+
+
+def _matching(patterns, names, what):
+    """the names any of the fnmatch patterns matches; a pattern that matches none of them is a ValueError"""
+    hit = set()
+    for pat in patterns:
+        if not isinstance(pat, str):
+            raise ValueError(f"param_groups: {what} takes fnmatch patterns (strings), got {pat!r}")
+        found = [n for n in names if fnmatch.fnmatchcase(n, pat)]
+        if not found:
+            raise ValueError(f"param_groups: the {what} pattern {pat!r} matches no parameter (names look like "
+                             f"{names[0]!r}, {names[-1]!r})")
+        hit.update(found)
+    return hit
+
+
+def param_groups(model, freeze=(), no_decay=(), lr_scale=None, weight_decay=1e-2):
+    """The AdamW parameter groups of a fine-tuning run over the 2 L arena tensors (arena_layout), for
+    FlatAdamW(groups=).  freeze / no_decay: lists of fnmatch patterns (case-sensitive) over the state_dict names
+    -- "blocks.0.*", "*.bias", "out.*".  A frozen tensor is never read or written by the optimizer: no update,
+    no weight decay, no moments, and its gradient stays out of the norm.  A no_decay tensor has weight_decay 0,
+    every other trainable one `weight_decay`.  lr_scale: {pattern: s}, the first matching pattern (in the dict's
+    order) gives a tensor's learning rate lr * s at every step of the schedule, s > 0 and finite; no match: 1.
+    A pattern of any of the three that matches no name is a ValueError, as is a string in place of a list.
+    Returns a list of {"tensors": [names in arena order], "lr_scale", "weight_decay", "frozen"}: the frozen
+    tensors (if any) in one entry with lr_scale 0.0 and weight_decay 0.0, the trainable ones grouped by their
+    (lr_scale, weight_decay) in order of first appearance.  Host only; the model is not changed."""
+    for what, v in (("freeze", freeze), ("no_decay", no_decay)):
+        if isinstance(v, str):
+            raise ValueError(f"param_groups: {what} is a list of patterns, not one string")
+    weight_decay = float(weight_decay)
+    if not (weight_decay >= 0 and math.isfinite(weight_decay)):
+        raise ValueError("param_groups: weight_decay must be finite and not negative")
+    names = [n for n, _ in arena_layout(model)]
+    frozen = _matching(freeze, names, "freeze")
+    plain = _matching(no_decay, names, "no_decay")
+    scales = []
+    for pat, s in (lr_scale or {}).items():
+        s = float(s)
+        if not (s > 0 and math.isfinite(s)):
+            raise ValueError(f"param_groups: lr_scale[{pat!r}] = {s!r} must be positive and finite")
+        scales.append((_matching([pat], names, "lr_scale"), s))
+    groups, index = [], {}
+    for n in names:
+        if n in frozen:
+            key = (True, 0.0, 0.0)
+        else:
+            key = (False, next((s for hit, s in scales if n in hit), 1.0), 0.0 if n in plain else weight_decay)
+        if key not in index:
+            index[key] = len(groups)
+            groups.append({"tensors": [], "lr_scale": key[1], "weight_decay": key[2], "frozen": key[0]})
+        groups[index[key]]["tensors"].append(n)
+    return groups
+
+
+def slice_table(numels, group_of):
+    """The slice table of gnot_adamw_step_groups / gnot_grad_norm_groups for an arena of consecutive tensors of
+    numels[i] elements: every tensor whose group_of[i] is not None cut into rows [begin, len, group_of[i]] of at
+    most SLICE elements (all but a tensor's last row full), in arena order; a tensor with None has no row.  Rows
+    start at tensor boundaries, so the table depends on the layout and the groups alone."""
+    rows, begin = [], 0
+    for n, g in zip(numels, group_of):
+        if g is not None:
+            rows += [[begin + o, min(SLICE, n - o), int(g)] for o in range(0, n, SLICE)]
+        begin += n
+    return rows
+
+
 class WeightEMA:
     """An exponential moving average of a flat parameter arena: ema += w_t (flat - ema) after optimizer step t,
     w_t = 1 - decay_t.  `ema` starts as a copy of `flat`.
@@ -392,10 +474,31 @@ class FlatAdamW:
     computes the same parameters and moments bit for bit and moves the average in the same pass; the weight
     w_t of step t is a ninth hyper-parameter `prepare()` writes, so `launch()` stays capturable.  A step the
     guard skips leaves the average alone.  None (default): no average, the kernels and the 8-float hyper
-    above."""
+    above.
+
+    groups, layout: fine-tuning -- frozen tensors and torch.optim.AdamW's parameter groups.  groups: the list
+    param_groups(model, freeze, no_decay, lr_scale) returns; layout: arena_layout(model), the names and sizes
+    the entries' "tensors" refer to (every tensor of the layout in exactly one entry; at least one not
+    frozen).  The norm and the update then run over a slice table of the trainable tensors
+    (gnot_grad_norm_groups / gnot_grad_clip_groups and gnot_adamw_step_groups, one launch each as above): a
+    tensor of entry k steps with lr * lr_scale_k -- of the schedule's lr at every step -- and weight_decay_k,
+    the constructor's weight_decay is not used, and a frozen tensor is neither read nor written: its
+    parameters, moments (zeros) and average (the weight itself) keep their bits, and a NaN in its gradient
+    changes nothing.  `grad_norm` is the norm of the trainable gradient, which is also what max_grad_norm
+    clips by and skip_nonfinite tests.  max_grad_norm, skip_nonfinite and ema_decay combine as above and
+    `launch()` stays capturable.  One group of lr_scale 1 over every tensor computes the update above bit for
+    bit (with a power-of-two gradient scale; the norm's bits differ, its slices start at tensor boundaries).
+    state_dict() names the groups and load_state_dict refuses a state written under other ones.  None
+    (default): the entries above, nothing else."""
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, schedule=None,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, groups=None, layout=None):
+        self.groups = None
+        nparts = None
+        if groups is not None:
+            nparts = self._init_groups(flat, groups, layout)
+        elif layout is not None:
+            raise ValueError("FlatAdamW: a layout without groups")
         self.ema = None if ema_decay is None else WeightEMA(flat, ema_decay, ema_warmup)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -404,8 +507,8 @@ class FlatAdamW:
             raise ValueError("max_grad_norm must be positive and finite")
         if self.max_grad_norm is not None or self.skip_nonfinite:
             self._clip = torch.zeros(2, dtype=torch.float32, device=flat.device)       # {norm, coefficient}
-            self._clip_work = torch.empty(_lib.load().gnot_grad_clip_work_floats(flat.numel()),
-                                          dtype=torch.float32, device=flat.device)
+            self._clip_work = torch.empty(_lib.load().gnot_grad_clip_work_floats(flat.numel()) if nparts is None
+                                          else nparts, dtype=torch.float32, device=flat.device)
             self.grad_norm = self._clip[0]
         if self.skip_nonfinite:
             self._guard = torch.zeros(2, dtype=torch.int32, device=flat.device)        # {skipped, skipped now}
@@ -422,6 +525,46 @@ class FlatAdamW:
         # after the copy that last read it has executed (its event)
         self._ring = [torch.zeros(nh, dtype=torch.float32).pin_memory() for _ in range(4)]
         self._ev = [None] * 4
+
+    def _init_groups(self, flat, groups, layout):
+        """Check `groups` against `layout`, keep a plain copy in self.groups and upload the slice table and the
+        group constants; returns the number of slices.  Host checks first, then two small copies."""
+        if layout is None:
+            raise ValueError("FlatAdamW: groups need the layout they name (arena_layout(model))")
+        layout = [(str(n), int(k)) for n, k in layout]
+        if sum(k for _, k in layout) != flat.numel():
+            raise ValueError(f"FlatAdamW: the layout holds {sum(k for _, k in layout)} elements, the arena "
+                             f"{flat.numel()}")
+        spec, owner, ghyper = [], {}, []
+        for g in groups:
+            e = {"tensors": [str(n) for n in g["tensors"]], "lr_scale": float(g["lr_scale"]),
+                 "weight_decay": float(g["weight_decay"]), "frozen": bool(g["frozen"])}
+            if not e["frozen"]:
+                if not (e["lr_scale"] > 0 and math.isfinite(e["lr_scale"])):
+                    raise ValueError(f"FlatAdamW: lr_scale {e['lr_scale']!r} of a group must be positive and finite")
+                if not (e["weight_decay"] >= 0 and math.isfinite(e["weight_decay"])):
+                    raise ValueError(f"FlatAdamW: weight_decay {e['weight_decay']!r} of a group must be finite and "
+                                     "not negative")
+            for n in e["tensors"]:
+                if n in owner:
+                    raise ValueError(f"FlatAdamW: {n!r} is in more than one group")
+                owner[n] = None if e["frozen"] else len(ghyper)
+            if not e["frozen"]:
+                ghyper.append([e["lr_scale"], e["weight_decay"]])
+            spec.append(e)
+        names = [n for n, _ in layout]
+        if set(owner) != set(names) or len(set(names)) != len(names):
+            odd = sorted(set(owner) ^ set(names))
+            raise ValueError(f"FlatAdamW: the groups and the layout name different tensors ({odd[:4]})")
+        rows = slice_table([k for _, k in layout], [owner[n] for n in names])
+        if not rows:
+            raise ValueError("FlatAdamW: every tensor is frozen, there is nothing to optimise")
+        self.groups = spec
+        self._ngroups = len(ghyper)
+        self._slices_host = (ctypes.c_int64 * (3 * len(rows)))(*[v for r in rows for v in r])
+        self._slices = torch.tensor(rows, dtype=torch.int64).to(flat.device)
+        self._ghyper = torch.tensor(ghyper, dtype=torch.float32).to(flat.device)
+        return len(rows)
 
     def prepare(self):
         """Advance the step count and write this step's hyper-parameters to the device array."""
@@ -450,6 +593,8 @@ class FlatAdamW:
         s = ctypes.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)
         lib, n, hyper = _lib.load(), self.flat.numel(), self.hyper.data_ptr()
         clip = guard = None
+        if self.groups is not None:
+            return self._launch_groups(grad, lib, n, hyper, s)
         # at most one norm step ...
         if self.grad_norm is not None:
             clip = self._clip.data_ptr()
@@ -472,6 +617,25 @@ class FlatAdamW:
             rc = lib.gnot_adamw_step(*arrays, n, hyper, s)
         _lib.check(rc)
 
+    def _launch_groups(self, grad, lib, n, hyper, s):
+        """launch() with groups: the same sequence through the slice-table entries"""
+        clip = guard = None
+        table = (self._slices.data_ptr(), self._slices_host, self._slices.shape[0])
+        if self.grad_norm is not None:
+            clip = self._clip.data_ptr()
+            if self.max_grad_norm is not None:
+                _lib.check(lib.gnot_grad_clip_groups(grad.data_ptr(), n, hyper, self.max_grad_norm, *table,
+                                                     self._clip_work.data_ptr(), clip, s))
+            else:
+                _lib.check(lib.gnot_grad_norm_groups(grad.data_ptr(), n, hyper, *table, self._clip_work.data_ptr(),
+                                                     clip, s))
+        if self.skip_nonfinite:
+            guard = self._guard.data_ptr()
+        _lib.check(lib.gnot_adamw_step_groups(
+            self.flat.data_ptr(), grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+            None if self.ema is None else self.ema.ema.data_ptr(), n, hyper, self._ghyper.data_ptr(), self._ngroups,
+            *table, clip, guard, s))
+
     def step(self, grad):
         self.prepare()
         self.launch(grad)
@@ -486,6 +650,8 @@ class FlatAdamW:
                  "weight_decay": self.wd, "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
         if self.ema is not None:
             state["ema"] = self.ema.state_dict()       # only with ema_decay: the keys above are the rest
+        if self.groups is not None:
+            state["groups"] = [dict(g, tensors=list(g["tensors"])) for g in self.groups]      # only with groups
         return state
 
     def load_state_dict(self, state):
@@ -500,6 +666,10 @@ class FlatAdamW:
             raise ValueError("FlatAdamW.load_state_dict: the stored state "
                              + ("holds no weight average (ema_decay is set here)" if self.ema is not None
                                 else "holds a weight average (ema_decay is not set here)"))
+        if state.get("groups") != self.groups:
+            raise ValueError("FlatAdamW.load_state_dict: the stored state was written under "
+                             + ("no parameter groups" if state.get("groups") is None else "other parameter groups")
+                             + (", this optimizer has none" if self.groups is None else " than this optimizer's"))
         if self.ema is not None:
             self.ema.load_state_dict(state["ema"])
         self.m.copy_(state["exp_avg"].reshape(-1))
@@ -594,7 +764,7 @@ def restore_rng_state(state, train_loader=None):
 
 
 def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, hist_test, args, train_loader=None,
-                        ema_args=None, normalizer=None, dropout=None):
+                        ema_args=None, normalizer=None, dropout=None, param_groups=None):
     """Everything fit needs to continue a run bit for bit, in one torch.save of tensors (on the host) and plain
     Python values, readable with weights_only=True: the model state_dict (reference keys), the optimizer's
     and the schedule's state_dict(), the next epoch, the best metric, both histories, the host random state
@@ -602,7 +772,9 @@ def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, h
     (fit's ema_decay / ema_warmup; the average itself travels in the optimizer's state, the model entry holds
     the raw weights); with a normalizer its statistics ("normalizer": Normalizer.state_dict(); the model
     entry holds the unfolded weights, which take normalised inputs); with attention dropout its {p, seed, step}
-    ("dropout": GNOT.dropout_state(), the step counter the next training forward takes).  Written under a
+    ("dropout": GNOT.dropout_state(), the step counter the next training forward takes); with frozen tensors or
+    parameter groups fit's three arguments ("param_groups": {freeze, no_decay, lr_scale}; the groups they resolve
+    to travel in the optimizer's state).  Written under a
     temporary name in the same directory and moved into place with os.replace: a kill in mid-write leaves the
     previous file."""
     state = {"model": _cpu(model.state_dict()), "optimizer": _cpu(opt.state_dict()), "schedule": sched.state_dict(),
@@ -614,6 +786,8 @@ def save_training_state(path, model, opt, sched, next_epoch, best, hist_train, h
         state["normalizer"] = normalizer.state_dict()
     if dropout is not None:
         state["dropout"] = dict(dropout)
+    if param_groups is not None:
+        state["param_groups"] = dict(param_groups)
     tmp = f"{path}.tmp{os.getpid()}"
     try:
         torch.save(state, tmp)
@@ -804,7 +978,8 @@ def _accum_step(model, eng, opt, loss_fn, group, dev, encoder=None):
 
 def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_schedule=True, checkpoint=None,
         log=print, loss_fn=None, max_grad_norm=None, accum_steps=1, skip_nonfinite=False, state_path=None,
-        resume=False, ema_decay=None, ema_warmup=True, normalizer=None, log_components=False):
+        resume=False, ema_decay=None, ema_warmup=True, normalizer=None, log_components=False, freeze=None,
+        no_decay=None, lr_scale=None):
     """The reference training loop (main.py:50-153): AdamW(lr) + OneCycleLR(max_lr=lr, steps_per_epoch,
     epochs), RelL2 loss, per-epoch test metric and best checkpoint.  With per_epoch_schedule=True the
     schedule is stepped once per epoch, as main.py:106 does.  The loaders decide the batch form:
@@ -865,6 +1040,19 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
     terms beside its loss (LpLoss.loss_and_terms), bit for bit the same loss.  The scalar metric stays main.py's
     mean over BATCHES of the batch means; when the last batch is short the mean of the logged components is
     therefore not the scalar metric.  The return value is unchanged.  False (default): nothing else happens.
+    freeze, no_decay, lr_scale: fine-tuning a trained model (load_checkpoint first) -- param_groups' arguments:
+    lists of fnmatch patterns over the state_dict names and a {pattern: s} dict.  With any of them given, fit
+    sets the requires_grad of every Linear's weight and bias for the duration of the call (False on the `freeze`
+    matches, True on the rest; the caller's flags are put back on return, like the engine's other settings), so
+    the engine plans no weight-gradient job for a Linear whose weight and bias are both frozen and its backward
+    stops at the lowest stage that still trains (GNOT.trainable_mask), and the optimizer runs per group
+    (FlatAdamW(groups=)): a frozen tensor keeps its bits --
+    no update, no weight decay, and with ema_decay its average stays equal to the weight --, a no_decay tensor
+    has weight_decay 0, a tensor matching lr_scale follows the schedule at s times its rate, and max_grad_norm
+    / skip_nonfinite see the norm of the trainable gradient only.  A pattern that matches nothing is a
+    ValueError before any GPU work.  The state file names the three arguments in an entry of its
+    own, "param_groups"; resume refuses a file whose entry differs from this call's in any of them, an absent
+    one included.  All None (default): one group, the plain kernels, every call what it was.
     No step reads its loss back: every step's 0-d loss (with accum_steps, every micro-batch's) stays on the
     device and the epoch reads them all at its end, then does the host arithmetic above on those fp32 values;
     with a loader whose batches are on the device already (data.DeviceLoader) the host runs ahead of the GPU
@@ -889,6 +1077,13 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                 skip_nonfinite=bool(skip_nonfinite))
     # beside args, not in it: TRAJECTORY_ARGS is the raw trajectory, which the average does not touch
     ema_args = None if ema_decay is None else dict(ema_decay=float(ema_decay), ema_warmup=bool(ema_warmup))
+    group_args = groups = None
+    if freeze is not None or no_decay is not None or lr_scale is not None:
+        groups = param_groups(model, freeze or (), no_decay or (), lr_scale)      # refuses before any GPU work
+        if all(g["frozen"] for g in groups):
+            raise ValueError("fit: freeze matches every parameter, there is nothing to train")
+        group_args = dict(freeze=[str(v) for v in freeze or ()], no_decay=[str(v) for v in no_decay or ()],
+                          lr_scale={str(k): float(v) for k, v in (lr_scale or {}).items()})
     state = None
     if resume and os.path.exists(state_path):
         state = load_training_state(state_path)
@@ -901,6 +1096,11 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             if stored.get(k) != (ema_args or {}).get(k):
                 raise ValueError(f"fit(resume=True): {state_path} was written with {k}={stored.get(k)!r}, "
                                  f"this call has {k}={(ema_args or {}).get(k)!r}")
+        stored = state.get("param_groups") or {}
+        for k in ("freeze", "no_decay", "lr_scale"):
+            if stored.get(k) != (group_args or {}).get(k):
+                raise ValueError(f"fit(resume=True): {state_path} was written with {k}={stored.get(k)!r}, "
+                                 f"this call has {k}={(group_args or {}).get(k)!r}")
         stored, mine = state.get("dropout"), _dropout_state(model)
         for k in ("p", "seed"):
             if (stored or {}).get(k) != (mine or {}).get(k):
@@ -915,10 +1115,18 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             raise ValueError(f"fit(resume=True): {state_path} was written with other statistics in its normalizer "
                              f"entry ({normalizer.mismatch(stored)!r} differs from this call's)")
         model.load_state_dict(state["model"])       # before the parameters move into the flat arena
+    layout, flags = None, None
+    if groups is not None:
+        layout = arena_layout(model)
+        frozen = {n for g in groups if g["frozen"] for n in g["tensors"]}
+        names = {id(p): n for n, p in model.named_parameters()}
+        flags = [(p, p.requires_grad) for l in model.linears() for p in (l.weight, l.bias)]
+        for p, _ in flags:
+            p.requires_grad_(names[id(p)] not in frozen)
     flat = flatten_parameters(model)
     sched = OneCycle(lr, epochs, steps_per_epoch)
     opt = FlatAdamW(flat, lr=lr, schedule=sched, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                    ema_decay=ema_decay, ema_warmup=ema_warmup)
+                    ema_decay=ema_decay, ema_warmup=ema_warmup, groups=groups, layout=layout)
     dev = flat.device
     prev_arena = model._grad_arena
     if accum_steps > 1:
@@ -987,9 +1195,11 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
                         save_checkpoint(model, checkpoint, normalizer)
             if state_path:       # outside the swap: the raw weights, the average inside the optimizer state
                 save_training_state(state_path, model, opt, sched, epoch + 1, best, hist_train, hist_test, args,
-                                    train_loader, ema_args, normalizer, _dropout_state(model))
+                                    train_loader, ema_args, normalizer, _dropout_state(model), group_args)
     finally:
         eng.param_grads = prev       # ordinary autograd use after fit() gets .grad again
+        for p, was in flags or ():   # ... and the caller's requires_grad flags
+            p.requires_grad_(was)
         if accum_steps > 1:
             model.set_grad_arena(prev_arena)
     return hist_train, hist_test

@@ -422,6 +422,65 @@ int gnot_ema_update(float* ema, const float* param, int64_t n, const float* weig
 int gnot_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                         const float* hyper, const float* clip, int32_t* guard, void* stream);
 
+/* Frozen Linears (fine-tuning).  mask: one byte per Linear in gnot_plan_num_linears order, non-zero = trainable;
+ * NULL (the default): all trainable.  A Linear is the unit -- its dW and db come out of one weight-gradient job.
+ * Call after gnot_plan_create and before gnot_plan_set_batch; a change invalidates the batch, like the other
+ * setters.  Training plans only; the forward and the saved activations do not change, and the workspace keeps
+ * their size (its split-K slab and job tables shrink with the jobs; freeing the saves below the cut is the
+ * known follow-up).
+ *   - No weight-gradient job is planned for a frozen Linear.  A group left without a job launches nothing, takes
+ *     no split-K slab, records no profile scope and issues no gradient collective; with gnot_plan_set_grad_comm a
+ *     group reduces only the arena ranges of its trainable Linears, one call per contiguous run.
+ *   - The arena ranges of a frozen Linear are never written: not by the backward (with or without
+ *     GNOT_BWD_ACCUMULATE), not by bind (the clear of padded widths goes around them), in the workspace arena
+ *     and in a caller's arena alike.
+ *   - Removing jobs changes a group's split counts and balanced ranges, so the remaining gradients equal the
+ *     unfrozen run's to rounding, not bit for bit.
+ *   - Early stop.  Stages: the encoders (the x MLP, gating, every input-function encoder), blocks 0 .. L-1, the
+ *     decoder.  With c the lowest stage that holds a trainable Linear (the encoders when
+ *     gnot_plan_set_input_grads is on), gnot_backward runs from the decoder down to stage c and issues no kernel
+ *     of the stages below it; inside block c everything runs as before.  Of the batched key/value backward of
+ *     the input functions only the jobs of the blocks that ran are launched, and only when one of their
+ *     key/value Linears is trainable.  Everything frozen and no input gradients: the backward launches nothing
+ *     and returns GNOT_OK.  Every side stream a shortened backward forks is joined before it returns.
+ * gnot_debug_backward_plan (host only, needs gnot_plan_set_batch): *wgrad_jobs = the weight-gradient jobs over all
+ * groups, *lowest_stage = the lowest stage the backward enters: -1 the encoders, l block l, L the decoder alone,
+ * L + 1 nothing. */
+int gnot_plan_set_trainable(gnot_plan* plan, const uint8_t* mask);
+int gnot_debug_backward_plan(const gnot_plan* plan, int* wgrad_jobs, int* lowest_stage);
+
+/* The update and the norm over PARTS of an arena with per-group constants: frozen tensors and AdamW parameter
+ * groups (fine-tuning).  One slice table serves both: `nslices` rows of three int64 {begin, len, group}, built on
+ * the host -- every trainable tensor of the arena cut into slices of at most 8192 elements, a frozen tensor
+ * has no row -- and uploaded once (slices_dev on the device, slices_host the same on the host, for validation).
+ * Rows must be sorted and disjoint, lie inside [0, n), have 1 <= len <= 8192 and 0 <= group < G, 1 <= nslices
+ * < 2^24; anything else is GNOT_E_INVALID before any launch.  One workgroup per row.  An element outside every
+ * row is neither read nor written, in param, grad, exp_avg, exp_avg_sq and ema alike (a NaN in a frozen range of
+ * grad is never seen).
+ *
+ * gnot_adamw_step_groups: the element expression of gnot_adamw_step with lr = hyper[0] * ghyper[group][0], the
+ * product rounded to fp32 once, and weight_decay = ghyper[group][1]; ghyper: DEVICE array of G pairs {lr_scale,
+ * weight_decay}; hyper[4] is not read.  ema, clip and guard may be NULL in the combinations gnot_adamw_step_ema
+ * accepts (a guard needs a clip); with ema, hyper has 9 floats.  With one group {1, hyper[4]} whose rows cover
+ * [0, n) the results are bit for bit those of gnot_adamw_step_clipped, _guarded and _ema for the same inputs, a
+ * guarded skip that writes nothing but guard included; with clip == NULL and ema == NULL they are
+ * gnot_adamw_step's bit for bit when hyper[7] is a power of two (the limit gnot_adamw_step_clipped states).
+ * One kernel launch, stream-ordered, nothing read back: capturable.
+ *
+ * gnot_grad_norm_groups / gnot_grad_clip_groups: gnot_grad_norm / gnot_grad_clip over the rows' elements only,
+ * the norm of the trainable gradient.  Stage 1 sums g^2 per row in a fixed order, stage 2 the partials in row
+ * order; work: nslices floats.  No atomics: the same arguments give the same bits on every run and device.  The
+ * bits differ from the plain entries' for the same gradient, because the rows start at tensor boundaries and not
+ * at multiples of 8192.  The group column is neither read nor checked. */
+int gnot_adamw_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                           const float* hyper, const float* ghyper, int G, const int64_t* slices_dev,
+                           const int64_t* slices_host, int64_t nslices, const float* clip, int32_t* guard,
+                           void* stream);
+int gnot_grad_norm_groups(const float* grad, int64_t n, const float* hyper, const int64_t* slices_dev,
+                          const int64_t* slices_host, int64_t nslices, float* work, float* clip, void* stream);
+int gnot_grad_clip_groups(const float* grad, int64_t n, const float* hyper, float max_norm, const int64_t* slices_dev,
+                          const int64_t* slices_host, int64_t nslices, float* work, float* clip, void* stream);
+
 /* Batch assembly from a dataset that lives in device memory (no reference counterpart: main.py:57-58 batches
  * on the host).  src [rows, C] and dst [sum k, C] are fp32; the table has one row of six int64 per segment b,
  * {src_row0, n, dst_row0, k, key_lo, key_hi} (table_dev on the device, table_host the same on the host, for

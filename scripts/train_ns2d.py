@@ -12,6 +12,9 @@ order N inside the model (the original GNOT code's horiz_fourier_dim), behind th
 --loss rel_l1 / l1 and --component-weights W0,W1,... train on the original GNOT code's other named losses and on
 weighted output components (train.LpLoss); --log-components logs the test metric per output component every epoch
 and prints the five worst test samples at the end (train.evaluate_table).
+--init CHECKPOINT starts from a trained model's weights (fine-tuning); --freeze P1,P2 keeps the parameters matching
+those fnmatch patterns (state_dict names: "blocks.0.*", "x.*") as they are, --no-decay P1,P2 takes them out of
+the weight decay ("*.bias") and --lr-scale PATTERN=S[,...] trains them at S times the schedule's rate.
 
     python scripts/train_ns2d.py --train train.pkl --test test.pkl [--epochs 100 ...]
     python scripts/train_ns2d.py --synthetic 64 --epochs 2          # generated meshes, same format
@@ -103,7 +106,37 @@ def parse_args(argv=None):
                          "forwards only (default 0: off); the state file carries its step counter")
     ap.add_argument("--dropout-seed", type=int, default=0, metavar="S",
                     help="the seed of the dropout masks (default 0); a run resumes only under the seed that wrote it")
+    ap.add_argument("--init", default=None, metavar="CHECKPOINT",
+                    help="load this state_dict checkpoint (train.load_checkpoint) before training: fine-tuning a "
+                         "trained model.  Unlike --resume it starts a new run: step 0 of a fresh schedule")
+    ap.add_argument("--freeze", default=None, metavar="P1,P2",
+                    help="fnmatch patterns over the state_dict names (\"blocks.0.*\", \"x.*\"): the matching "
+                         "parameters are not trained -- no update and no weight decay")
+    ap.add_argument("--no-decay", default=None, metavar="P1,P2",
+                    help="patterns of the parameters that take no weight decay (\"*.bias\")")
+    ap.add_argument("--lr-scale", default=None, metavar="PATTERN=S[,...]",
+                    help="train the parameters matching PATTERN at S times the schedule's learning rate, S > 0; the "
+                         "first matching pattern counts (\"blocks.*=0.1\")")
     args = ap.parse_args(argv)
+    for name in ("freeze", "no_decay"):
+        v = getattr(args, name)
+        if v is not None:
+            setattr(args, name, [p for p in v.split(",") if p])
+            if not getattr(args, name):
+                ap.error(f"--{name.replace('_', '-')} takes comma-separated patterns")
+    if args.lr_scale is not None:
+        scales = {}
+        for item in filter(None, args.lr_scale.split(",")):
+            pat, sep, val = item.rpartition("=")
+            try:
+                scales[pat] = float(val)
+            except ValueError:
+                sep = ""
+            if not sep or not pat or not (scales[pat] > 0 and scales[pat] < float("inf")):
+                ap.error("--lr-scale takes PATTERN=S[,PATTERN=S...] with positive finite S")
+        if not scales:
+            ap.error("--lr-scale takes PATTERN=S[,PATTERN=S...] with positive finite S")
+        args.lr_scale = scales
     if not (0.0 <= args.attn_dropout < 1.0):
         ap.error("--attn-dropout takes a probability in [0, 1)")
     if not (0 <= args.dropout_seed < 1 << 64):
@@ -150,6 +183,8 @@ def main():
                  args.n_attn_hidden_dim, args.n_mlp_num_layers, args.n_mlp_hidden_dim, args.n_input_hidden_dim,
                  args.n_expert, args.n_head, len(f0), x_fourier=args.x_fourier, fn_fourier=args.fn_fourier,
                  pre_norm=args.pre_norm, attn_dropout=args.attn_dropout, dropout_seed=args.dropout_seed).to(dev)
+    if args.init:
+        train.load_checkpoint(model, args.init)
     dl = lambda ds, sh: torch.utils.data.DataLoader(ds, batch_size=args.batch, shuffle=sh,
                                                     collate_fn=data.collate_packed if args.packed
                                                     else data.collate_padded)
@@ -168,7 +203,8 @@ def main():
                         loss_fn=training_loss(args, nz), log_components=args.log_components,
                         max_grad_norm=args.grad_clip, accum_steps=args.accum_steps,
                         skip_nonfinite=args.skip_nonfinite, state_path=args.state, resume=args.resume,
-                        ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup, normalizer=nz)
+                        ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup, normalizer=nz,
+                        freeze=args.freeze, no_decay=args.no_decay, lr_scale=args.lr_scale)
     print(f"\nBest Test Metric: {min(test)}")
     if args.log_components:      # of the final weights (the raw ones, also with --ema-decay)
         table = train.evaluate_table(model, loaders[1], "rel2", nz)
