@@ -2761,34 +2761,76 @@ static bool adamw_pointers(const float* param, const float* grad, const float* e
   return param && grad && exp_avg && exp_avg_sq && hyper;
 }
 
+// work of the relative kinds: [B][nsplit][2C] partial norms and the [B][C] gradient scales
 extern "C" size_t gnot_rel_l2_work_floats(const int64_t* off_host, int B, int C) {
   if (!off_host || B <= 0 || C <= 0) return 0;
   std::vector<long> off(off_host, off_host + B + 1);
   return (size_t)B * rel_l2_splits(off.data(), B) * 2 * C + (size_t)B * C;
 }
 
-// gnot_rel_l2_loss (stats == nullptr) and gnot_rel_l2_loss_affine
-static int rel_l2_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B,
-                       int C, const float* stats, float* work, float* loss, float* dpred, void* stream) {
-  if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
-    return fail(GNOT_E_INVALID, "bad rel_l2 arguments");
+// ... and of the others: [B][nsplit][C] and the same scales
+extern "C" size_t gnot_mse_work_floats(const int64_t* off_host, int B, int C) {
+  if (!off_host || B <= 0 || C <= 0) return 0;
   std::vector<long> off(off_host, off_host + B + 1);
-  if (int rc = check_loss_offsets(off, true)) return rc;
-  GNOT_CK(launch_rel_l2(pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B),
-                        off[B], stats, work, loss, dpred, static_cast<hipStream_t>(stream)));
+  return (size_t)B * rel_l2_splits(off.data(), B) * C + (size_t)B * C;
+}
+
+extern "C" size_t gnot_lp_loss_work_floats(const int64_t* off_host, int B, int C) {
+  return gnot_rel_l2_work_floats(off_host, B, C);      // the widest layout of the family: two norms per channel
+}
+
+// Every loss entry: `name` is the caller's in messages; allow_empty: a sample may have no rows.
+static int loss_entry(const char* name, int kind, bool allow_empty, const float* pred, const float* tgt,
+                      const int64_t* off_dev, const int64_t* off_host, int B, int C, const float* comp_weights,
+                      const float* stats, float* work, float* loss, float* terms, float* dpred, void* stream) {
+  static_assert(GNOT_LP_REL2 == 0 && GNOT_LP_REL1 == 1 && GNOT_LP_RELINF == 2 && GNOT_LP_MSE == 3 &&
+                GNOT_LP_L1 == 4 && GNOT_LP_LINF == 5, "launch_lp's kinds");
+  if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
+    return fail(GNOT_E_INVALID, std::string("bad ") + name + " arguments");
+  if (kind < GNOT_LP_REL2 || kind > GNOT_LP_LINF)      // gnot_lp_loss alone passes a caller's number on
+    return fail(GNOT_E_INVALID, "lp_loss: unknown kind " + std::to_string(kind));
+  if (dpred && (kind == GNOT_LP_RELINF || kind == GNOT_LP_LINF))
+    return fail(GNOT_E_INVALID, "lp_loss: relinf and linf are metrics only: they have no gradient (dpred must be null)");
+  std::vector<long> off(off_host, off_host + B + 1);
+  if (int rc = check_loss_offsets(off, allow_empty)) return rc;
+  GNOT_CK(launch_lp(kind, pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
+                    comp_weights, stats, work, loss, terms, dpred, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 
 extern "C" int gnot_rel_l2_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
                                 int B, int C, float* work, float* loss, float* dpred, void* stream) {
-  return rel_l2_loss(pred, tgt, off_dev, off_host, B, C, nullptr, work, loss, dpred, stream);
+  return loss_entry("rel_l2", GNOT_LP_REL2, true, pred, tgt, off_dev, off_host, B, C, nullptr, nullptr, work, loss,
+                    nullptr, dpred, stream);
 }
 
 extern "C" int gnot_rel_l2_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev,
                                        const int64_t* off_host, int B, int C, const float* out_stats, float* work,
                                        float* loss, float* dpred, void* stream) {
   if (!out_stats) return fail(GNOT_E_INVALID, "rel_l2_loss_affine: null out_stats");
-  return rel_l2_loss(pred, tgt, off_dev, off_host, B, C, out_stats, work, loss, dpred, stream);
+  return loss_entry("rel_l2", GNOT_LP_REL2, true, pred, tgt, off_dev, off_host, B, C, nullptr, out_stats, work, loss,
+                    nullptr, dpred, stream);
+}
+
+extern "C" int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
+                             int B, int C, float* work, float* loss, float* dpred, void* stream) {
+  return loss_entry("mse", GNOT_LP_MSE, false, pred, tgt, off_dev, off_host, B, C, nullptr, nullptr, work, loss,
+                    nullptr, dpred, stream);
+}
+
+extern "C" int gnot_mse_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev,
+                                    const int64_t* off_host, int B, int C, const float* out_stats, float* work,
+                                    float* loss, float* dpred, void* stream) {
+  if (!out_stats) return fail(GNOT_E_INVALID, "mse_loss_affine: null out_stats");
+  return loss_entry("mse", GNOT_LP_MSE, false, pred, tgt, off_dev, off_host, B, C, nullptr, out_stats, work, loss,
+                    nullptr, dpred, stream);
+}
+
+extern "C" int gnot_lp_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
+                            int B, int C, int kind, const float* comp_weights, const float* out_stats, float* work,
+                            float* loss, float* terms, float* dpred, void* stream) {
+  return loss_entry("lp_loss", kind, false, pred, tgt, off_dev, off_host, B, C, comp_weights, out_stats, work, loss,
+                    terms, dpred, stream);
 }
 
 extern "C" int gnot_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
@@ -2797,58 +2839,6 @@ extern "C" int gnot_adamw_step(float* param, const float* grad, float* exp_avg, 
     return fail(GNOT_E_INVALID, "bad adamw arguments");
   GNOT_CK(launch_adamw_update(param, grad, exp_avg, exp_avg_sq, nullptr, n, hyper, nullptr, nullptr,
                               static_cast<hipStream_t>(stream)));
-  return GNOT_OK;
-}
-
-extern "C" size_t gnot_mse_work_floats(const int64_t* off_host, int B, int C) {
-  if (!off_host || B <= 0 || C <= 0) return 0;
-  std::vector<long> off(off_host, off_host + B + 1);
-  return (size_t)B * rel_l2_splits(off.data(), B) * C;
-}
-
-// gnot_mse_loss (stats == nullptr) and gnot_mse_loss_affine
-static int mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B, int C,
-                    const float* stats, float* work, float* loss, float* dpred, void* stream) {
-  if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
-    return fail(GNOT_E_INVALID, "bad mse arguments");
-  std::vector<long> off(off_host, off_host + B + 1);
-  if (int rc = check_loss_offsets(off, false)) return rc;
-  GNOT_CK(launch_mse(pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
-                     stats, work, loss, dpred, static_cast<hipStream_t>(stream)));
-  return GNOT_OK;
-}
-
-extern "C" int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
-                             int B, int C, float* work, float* loss, float* dpred, void* stream) {
-  return mse_loss(pred, tgt, off_dev, off_host, B, C, nullptr, work, loss, dpred, stream);
-}
-
-extern "C" int gnot_mse_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev,
-                                    const int64_t* off_host, int B, int C, const float* out_stats, float* work,
-                                    float* loss, float* dpred, void* stream) {
-  if (!out_stats) return fail(GNOT_E_INVALID, "mse_loss_affine: null out_stats");
-  return mse_loss(pred, tgt, off_dev, off_host, B, C, out_stats, work, loss, dpred, stream);
-}
-
-extern "C" size_t gnot_lp_loss_work_floats(const int64_t* off_host, int B, int C) {
-  return gnot_rel_l2_work_floats(off_host, B, C);      // the widest layout of the family: two norms per channel
-}
-
-extern "C" int gnot_lp_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
-                            int B, int C, int kind, const float* comp_weights, const float* out_stats, float* work,
-                            float* loss, float* terms, float* dpred, void* stream) {
-  static_assert(GNOT_LP_REL2 == 0 && GNOT_LP_REL1 == 1 && GNOT_LP_RELINF == 2 && GNOT_LP_MSE == 3 &&
-                GNOT_LP_L1 == 4 && GNOT_LP_LINF == 5, "launch_lp's kinds");
-  if (!pred || !tgt || !off_dev || !off_host || B <= 0 || C <= 0 || !work || !loss)
-    return fail(GNOT_E_INVALID, "bad lp_loss arguments");
-  if (kind < GNOT_LP_REL2 || kind > GNOT_LP_LINF)
-    return fail(GNOT_E_INVALID, "lp_loss: unknown kind " + std::to_string(kind));
-  if (dpred && (kind == GNOT_LP_RELINF || kind == GNOT_LP_LINF))
-    return fail(GNOT_E_INVALID, "lp_loss: relinf and linf are metrics only: they have no gradient (dpred must be null)");
-  std::vector<long> off(off_host, off_host + B + 1);
-  if (int rc = check_loss_offsets(off, false)) return rc;
-  GNOT_CK(launch_lp(kind, pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
-                    comp_weights, out_stats, work, loss, terms, dpred, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

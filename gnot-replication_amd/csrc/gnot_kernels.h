@@ -355,18 +355,14 @@ hipError_t launch_segcopy(const CopySeg* segs, const int* prefix, int nseg, int 
                           bool reverse, hipStream_t s, int unit = 4);
 
 // ------------------------------------------------------------------ training step (train.hip)
+// the 2048-row splits of the longest sample (at least 1)
 int rel_l2_splits(const long* off_host, int B);
-// work: B*nsplit*2C + B*C floats.  stats != nullptr (a stats block {mean[C], std[C], rstd[C]}, stats.hip): the
-// loss of pred * std[c] + mean[c] and its gradient times std[c]; nullptr: the plain loss
-hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                         long rows, const float* stats, float* work, float* loss, float* dpred, hipStream_t s);
-// work: B*nsplit*C floats (nsplit = rel_l2_splits); every sample must have at least one row; stats as above
-hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
-                      const float* stats, float* work, float* loss, float* dpred, hipStream_t s);
-// the Lp loss family (gnot_lp_loss): kind = GNOT_LP_* (0 rel2, 1 rel1, 2 relinf, 3 mse, 4 l1, 5 linf), checked by the
-// caller; w (C component weights), stats, terms ([B][C], the unweighted terms) and dpred may be null, dpred must be
-// for relinf / linf.  work: B*nsplit*2C + B*C floats (nsplit = rel_l2_splits); every sample has at least one row.
-// rel2 / mse without w and terms launch the kernels of launch_rel_l2 / launch_mse.
+// every loss, one kernel family: kind = GNOT_LP_* (0 rel2, 1 rel1, 2 relinf, 3 mse, 4 l1, 5 linf), checked by the
+// caller; gnot_rel_l2_loss / gnot_mse_loss are kinds 0 / 3 with w == terms == nullptr.  w (C component weights),
+// terms ([B][C], the unweighted terms) and dpred may be null, dpred must be for relinf / linf.  stats != nullptr
+// (a stats block {mean[C], std[C], rstd[C]}, stats.hip): the loss of pred * std[c] + mean[c] and its gradient
+// times std[c]; nullptr: the plain loss.  work: B*nsplit*kW*C + B*C floats (nsplit = rel_l2_splits; kW = 2 for
+// the relative kinds 0-2, else 1).  A sample without rows makes sense for rel2 alone (its term is a NaN).
 hipError_t launch_lp(int kind, const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
                      long rows, const float* w, const float* stats, float* work, float* loss, float* terms,
                      float* dpred, hipStream_t s);

@@ -1,15 +1,19 @@
 // The training step on either side of the GNOT path, on the GPU:
 //
-//   rel_l2_*  RelL2Loss (reference loss.py:14-23) over packed predictions: per-sample segment sums
-//             of (p - t)^2 and t^2 (the dgl SumPooling of loss.py:20-21), loss = mean over (sample,
-//             channel) of sqrt(num / den), and d loss / d pred in the same pass.  Deterministic:
-//             per-split partial sums reduced in a fixed order, no atomics.
+//   lp_*      every loss, over packed predictions: per-sample segment norms of d = p - t and, for the relative
+//             kinds, of t (the dgl SumPooling / AvgPooling of reference loss.py), the mean over (sample, channel)
+//             of the per-(sample, channel) terms, and d loss / d pred in the same pass.  One kernel family,
+//             lp_{partial,finish,grad}_kernel<kNorm, kRel>, for the six named losses of the original GNOT recipe
+//             (rel2, rel1, relinf, mse, l1, linf), with component weights and the terms as an output
+//             (gnot_lp_loss).  RelL2Loss (loss.py:14-23; gnot_rel_l2_loss) and MSELoss (loss.py:4-12;
+//             gnot_mse_loss) are its kinds 0 and 3 with w == terms == nullptr.  Deterministic: per-split partial
+//             sums reduced in a fixed order, no atomics.
+//   affine    a loss on a normalised prediction: p' = pred * std[c] + mean[c] against the raw target, and the
+//             gradient scaled by std[c], inside the same passes (Stats of the partial and grad kernels).
 //   adamw     torch.optim.AdamW's update (main.py:51; decoupled weight decay, bias-corrected moments)
 //             over ONE flat fp32 arena of parameters / gradients / moments, in torch's op order.
 //             Hyper-parameters come from a small device array so a captured hipGraph replays
 //             whatever the host's schedule (OneCycleLR, main.py:52/106) wrote there.
-//   mse_*     MSELoss (reference loss.py:4-12): per-sample means of (p - t)^2 (dgl AvgPooling), in the
-//             shape of the rel_l2 passes.
 //   grad_clip global L2 norm of the flat gradient and torch.nn.utils.clip_grad_norm_'s coefficient, on
 //             the device (two fixed-order stages), consumed by the update through its clip argument.
 //   guarded   the clipped update behind a device-side test of that norm: a NaN or infinite norm leaves
@@ -17,12 +21,8 @@
 //   ema       an exponential moving average of the parameters, ema += w (param - ema), as one more stream of
 //             the update (adamw_update_kernel<true>: plain, clipped or guarded) or as a pass of its own
 //             (ema_update_kernel); w comes from device memory like the other hyper-parameters.
-//   affine    both losses on a normalised prediction: p' = pred * std[c] + mean[c] against the raw target, and
-//             the gradient scaled by std[c], inside the same passes (Stats of the partial and grad kernels).
-//   lp_*      the named losses of the original GNOT recipe (rel2, rel1, relinf, mse, l1, linf) with component
-//             weights and the per-(sample, channel) terms as an output, in the shape of the rel_l2 passes
-//             (gnot_lp_loss); rel2 / mse without weights are the arithmetic of rel_l2_* / mse_*.
-// adamw, its clipped and guarded forms and the fused average are one kernel, adamw_update_kernel<kEma>.
+// adamw, its clipped and guarded forms and the fused average are one kernel, adamw_update_kernel<kEma>; the
+// slice-table form adamw_groups_kernel<kEma> runs the same guard and the same element update (adamw_element).
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
@@ -43,202 +43,30 @@ __device__ __forceinline__ int sample_of_row(const long* __restrict__ off, int B
 // the grid of an elementwise grid-stride kernel over n >= 1 elements, 256 threads a workgroup
 static unsigned flat_grid(long n) { return (unsigned)std::min<long>((n + 255) / 256, 2048); }
 
-// The _affine losses (gnot_rel_l2_loss_affine, gnot_mse_loss_affine): pred is a normalised prediction and the
-// loss that of p' = pred * std[c] + mean[c] against the raw target, stats = {mean[C], std[C], rstd[C]}
-// (stats.hip).  The product and the sum are each rounded -- torch's pred * std + mean, bit for bit -- and
-// d loss / d pred = (d loss / d p') * std[c] is one more rounded product.  The partial and the gradient kernels
-// take the block as a template parameter pack, Stats: empty -- kernel<>, the plain loss, with the argument list
-// and so the code it had before there was anything else -- or one const float*.
+// A loss with a stats block (gnot_rel_l2_loss_affine, gnot_mse_loss_affine, gnot_lp_loss with out_stats): pred is
+// a normalised prediction and the loss that of p' = pred * std[c] + mean[c] against the raw target, stats =
+// {mean[C], std[C], rstd[C]} (stats.hip).  The product and the sum are each rounded -- torch's pred * std + mean,
+// bit for bit -- and d loss / d pred = (d loss / d p') * std[c] is one more rounded product.  The partial and the
+// gradient kernels take the block as a template parameter pack, Stats: empty -- kernel<>, the plain loss, whose
+// argument list and code know nothing of it -- or one const float*.
 __device__ __forceinline__ float denormalised(float p, const float* __restrict__ stats, int C, int c) {
   return __fadd_rn(mul_rn(p, stats[C + c]), stats[c]);
 }
 
-// partial[b][split][0..2C) = (sum (p-t)^2 [C], sum t^2 [C]) over the split's rows of sample b
-template <typename... Stats>
-__global__ void __launch_bounds__(256) rel_l2_partial_kernel(const float* __restrict__ pred,
-                                                             const float* __restrict__ tgt,
-                                                             const long* __restrict__ off, int C, int nsplit,
-                                                             float* __restrict__ partial, Stats... stats_arg) {
-  __shared__ float red[256];
-  const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
-  const long r0 = off[b] + (long)split * kLossRows;
-  const long r1 = min(off[b + 1], r0 + kLossRows);
-  for (int c = 0; c < C; ++c) {
-    float num = 0.f, den = 0.f;
-    for (long r = r0 + threadIdx.x; r < r1; r += 256) {
-      const float t = tgt[r * C + c];
-      float d;
-      if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[r * C + c], (stats_arg, ...), C, c) - t;
-      else d = pred[r * C + c] - t;
-      num = fmaf(d, d, num);
-      den = fmaf(t, t, den);
-    }
-    num = block_sum(num, red);
-    den = block_sum(den, red);
-    if (threadIdx.x == 0) {
-      float* P = partial + ((long)b * nsplit + split) * 2 * C;
-      P[c] = num;
-      P[C + c] = den;
-    }
-  }
-}
-
-// one workgroup: num/den per (b, c) in split order, loss = mean sqrt(num/den), and the per-(b, c)
-// gradient scale d loss / d pred = (p - t) / (B C den sqrt(num/den))
-__global__ void __launch_bounds__(256) rel_l2_finish_kernel(const float* __restrict__ partial, int B, int C,
-                                                            int nsplit, float* __restrict__ scale,
-                                                            float* __restrict__ loss) {
-  __shared__ float red[256];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < B * C; i += 256) {
-    const int b = i / C, c = i % C;
-    float num = 0.f, den = 0.f;
-    for (int s = 0; s < nsplit; ++s) {
-      const float* P = partial + ((long)b * nsplit + s) * 2 * C;
-      num += P[c];
-      den += P[C + c];
-    }
-    const float r = sqrtf(num / den);
-    acc += r;
-    scale[i] = 1.0f / ((float)(B * C) * den * r);
-  }
-  acc = block_sum(acc, red);
-  if (threadIdx.x == 0) *loss = acc / (float)(B * C);
-}
-
-template <typename... Stats>
-__global__ void __launch_bounds__(256) rel_l2_grad_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                          const long* __restrict__ off, int B, int C,
-                                                          const float* __restrict__ scale, float* __restrict__ dpred,
-                                                          long rows, Stats... stats_arg) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows * C) return;
-  const long r = i / C;
-  const int c = (int)(i % C);
-  if constexpr (sizeof...(Stats) == 1) {
-    const float* __restrict__ stats = (stats_arg, ...);
-    const float g = (denormalised(pred[i], stats, C, c) - tgt[i]) * scale[sample_of_row(off, B, r) * C + c];
-    dpred[i] = mul_rn(g, stats[C + c]);
-  } else {
-    dpred[i] = (pred[i] - tgt[i]) * scale[sample_of_row(off, B, r) * C + c];
-  }
-}
-
+// the 2048-row splits of the longest sample: partial sums per (sample, split), at least one split
 int rel_l2_splits(const long* off_host, int B) {
   long mx = 1;
   for (int b = 0; b < B; ++b) mx = std::max(mx, off_host[b + 1] - off_host[b]);
   return (int)((mx + kLossRows - 1) / kLossRows);
 }
 
-template <typename... Stats>
-static hipError_t launch_rel_l2_t(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                                  long rows, float* work, float* loss, float* dpred, hipStream_t s, Stats... stats) {
-  float* partial = work;                                  // [B][nsplit][2C]
-  float* scale = work + (size_t)B * nsplit * 2 * C;       // [B][C]
-  hipLaunchKernelGGL(rel_l2_partial_kernel<Stats...>, dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev, C, nsplit,
-                     partial, stats...);
-  hipLaunchKernelGGL(rel_l2_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)partial, B, C, nsplit, scale, loss);
-  if (dpred && rows > 0)
-    hipLaunchKernelGGL(rel_l2_grad_kernel<Stats...>, dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s, pred,
-                       tgt, off_dev, B, C, (const float*)scale, dpred, rows, stats...);
-  return hipGetLastError();
-}
-
-// stats == nullptr: the plain loss
-hipError_t launch_rel_l2(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                         long rows, const float* stats, float* work, float* loss, float* dpred, hipStream_t s) {
-  return stats ? launch_rel_l2_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s, stats)
-               : launch_rel_l2_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s);
-}
-
-// ---------------------------------------------------------------- MSELoss (reference loss.py:4-12)
-// dgl AvgPooling of (p - t)^2 = per-sample mean over points, then the mean over (sample, channel); the
-// passes have the shape of the RelL2 ones above (which stay as they are, bit for bit).
-// partial[b][split][0..C) = sum (p-t)^2 over the split's rows of sample b
-template <typename... Stats>
-__global__ void __launch_bounds__(256) mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                          const long* __restrict__ off, int C, int nsplit,
-                                                          float* __restrict__ partial, Stats... stats_arg) {
-  __shared__ float red[256];
-  const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
-  const long r0 = off[b] + (long)split * kLossRows;
-  const long r1 = min(off[b + 1], r0 + kLossRows);
-  for (int c = 0; c < C; ++c) {
-    float num = 0.f;
-    for (long r = r0 + threadIdx.x; r < r1; r += 256) {
-      float d;
-      if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[r * C + c], (stats_arg, ...), C, c) - tgt[r * C + c];
-      else d = pred[r * C + c] - tgt[r * C + c];
-      num = fmaf(d, d, num);
-    }
-    num = block_sum(num, red);
-    if (threadIdx.x == 0) partial[((long)b * nsplit + split) * C + c] = num;
-  }
-}
-
-// one workgroup: sum per (b, c) in split order, loss = 1/(B C) sum_b sum_c num / N_b
-__global__ void __launch_bounds__(256) mse_finish_kernel(const float* __restrict__ partial,
-                                                         const long* __restrict__ off, int B, int C, int nsplit,
-                                                         float* __restrict__ loss) {
-  __shared__ float red[256];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < B * C; i += 256) {
-    const int b = i / C, c = i % C;
-    float num = 0.f;
-    for (int s = 0; s < nsplit; ++s) num += partial[((long)b * nsplit + s) * C + c];
-    acc += num / (float)(off[b + 1] - off[b]);
-  }
-  acc = block_sum(acc, red);
-  if (threadIdx.x == 0) *loss = acc / (float)(B * C);
-}
-
-// d loss / d pred = 2 (p - t) / (B C N_b)
-template <typename... Stats>
-__global__ void __launch_bounds__(256) mse_grad_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                       const long* __restrict__ off, int B, int C,
-                                                       float* __restrict__ dpred, long rows, Stats... stats_arg) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows * C) return;
-  const int b = sample_of_row(off, B, i / C);
-  if constexpr (sizeof...(Stats) == 1) {
-    const float* __restrict__ stats = (stats_arg, ...);
-    const int c = (int)(i % C);
-    const float g = (denormalised(pred[i], stats, C, c) - tgt[i]) *
-                    (2.0f / ((float)(B * C) * (float)(off[b + 1] - off[b])));
-    dpred[i] = mul_rn(g, stats[C + c]);
-  } else {
-    dpred[i] = (pred[i] - tgt[i]) * (2.0f / ((float)(B * C) * (float)(off[b + 1] - off[b])));
-  }
-}
-
-// work: B*nsplit*C floats
-template <typename... Stats>
-static hipError_t launch_mse_t(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                               long rows, float* work, float* loss, float* dpred, hipStream_t s, Stats... stats) {
-  hipLaunchKernelGGL(mse_partial_kernel<Stats...>, dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev, C, nsplit,
-                     work, stats...);
-  hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)work, off_dev, B, C, nsplit, loss);
-  if (dpred && rows > 0)
-    hipLaunchKernelGGL(mse_grad_kernel<Stats...>, dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s, pred, tgt,
-                       off_dev, B, C, dpred, rows, stats...);
-  return hipGetLastError();
-}
-
-// stats == nullptr: the plain loss
-hipError_t launch_mse(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit, long rows,
-                      const float* stats, float* work, float* loss, float* dpred, hipStream_t s) {
-  return stats ? launch_mse_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s, stats)
-               : launch_mse_t(pred, tgt, off_dev, B, C, nsplit, rows, work, loss, dpred, s);
-}
-
-// ---------------------------------------------------------------- Lp losses (gnot_lp_loss)
-// The loss family of the original GNOT recipe in the shape of the passes above: per (sample, channel) a term
+// ---------------------------------------------------------------- the losses
+// Per (sample, channel) a term
 //   e[b, c] = ||d||_p / ||t||_p  (kRel: rel2, rel1, relinf)   or   sum |d|^p / N_b  (mse, l1),  max |d|  (linf),
 // d = p' - t with p' the prediction or its de-normalisation, p = kNorm (2, 1, or 0 for the maximum norm), and
 //   loss = (1/B) sum_b sum_c w^_c e[b, c],  w^_c = w_c / sum_c w_c  (1/C without weights).
-// Without weights the instantiations for rel2 and mse are the arithmetic of the rel_l2_* / mse_* kernels above,
-// operation for operation, so loss and gradient have their bits; the plain forms without weights and terms are
-// not instantiated at all (launch_lp runs the kernels above).  The maximum is taken so that a NaN stays one.
+// Three passes: partial norms per (sample, 2048-row split), one workgroup that finishes them in split order, and
+// the elementwise gradient.  The maximum is taken so that a NaN stays one.
 __device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
 
 // block_sum's tree with nan_max in place of the sum
@@ -301,8 +129,7 @@ __global__ void __launch_bounds__(256) lp_partial_kernel(const float* __restrict
 
 // one workgroup: the norms per (b, c) in split order, the term e[b, c] (to terms, if asked for), the loss and
 // the per-(b, c) gradient scale s: d loss / d p' = s d (kNorm 2) or s sign(d) (kNorm 1).  w == nullptr: the
-// mean over (sample, channel) as rel_l2_finish_kernel / mse_finish_kernel take it; else w^_c from w[C], summed
-// in index order.
+// plain mean over (sample, channel), sum e / (B C); else w^_c from w[C], summed in index order.
 template <int kNorm, bool kRel>
 __global__ void __launch_bounds__(256) lp_finish_kernel(const float* __restrict__ partial, const long* __restrict__ off,
                                                         int B, int C, int nsplit, const float* __restrict__ w,
@@ -386,13 +213,12 @@ static hipError_t launch_lp_t(const float* pred, const float* tgt, const long* o
 }
 
 // kind: GNOT_LP_* (gnot_hip.h), checked by the caller, as is dpred == nullptr for the two maximum norms.
-// work: B*nsplit*2C + B*C floats (nsplit = rel_l2_splits); every sample has at least one row.  w, stats, terms,
-// dpred may be null.  rel2 and mse without w and terms: launch_rel_l2 / launch_mse, the same kernels.
+// work: B*nsplit*kW*C + B*C floats, kW = 2 for the relative kinds, else 1 (nsplit = rel_l2_splits).  A sample
+// without rows has zero norms: rel2's term is then sqrt(0 / 0), a NaN (the caller refuses it for every other
+// kind).  w, stats, terms, dpred may be null.
 hipError_t launch_lp(int kind, const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
                      long rows, const float* w, const float* stats, float* work, float* loss, float* terms,
                      float* dpred, hipStream_t s) {
-  if (!w && !terms && kind == 0) return launch_rel_l2(pred, tgt, off_dev, B, C, nsplit, rows, stats, work, loss, dpred, s);
-  if (!w && !terms && kind == 3) return launch_mse(pred, tgt, off_dev, B, C, nsplit, rows, stats, work, loss, dpred, s);
 #define GNOT_LP_CASE(K, NORM, REL)                                                                                   \
   case K:                                                                                                            \
     return stats ? launch_lp_t<NORM, REL>(pred, tgt, off_dev, B, C, nsplit, rows, w, work, loss, terms, dpred, s,    \
@@ -532,6 +358,46 @@ hipError_t launch_grad_norm(const float* grad, long n, const float* hyper, float
 // around them): they are the fusions the first, plain-only form of this kernel was compiled with, in torch's
 // operation order.  A coefficient of 1.0f multiplies exactly, so every variant computes the same exp_avg_sq,
 // denominator and parameter from the same scaled gradient.
+struct AdamwStep {   // what an element's update takes besides its arrays: one set per launch, or per slice
+  float b1, b2, eps, gs, step_size, bc2_sqrt, decay, coef, w;
+};
+
+// the guard of a launch (above; nullptr: none): false when no element may be written
+__device__ __forceinline__ bool adamw_guard_passes(const float* __restrict__ clip, int* __restrict__ guard) {
+#pragma clang fp contract(off)
+  if (!guard) return true;
+  const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (!finite) guard[0] = guard[0] + 1;
+    guard[1] = finite ? 0 : 1;
+  }
+  return finite;
+}
+
+// element i of every update kernel.  fused_scale: the moment's inner term g - exp_avg is fmaf(grad[i], gs, -mi),
+// the scaling not rounded (the plain update without the average alone); else fmaf(gi, coef, -mi).
+template <bool kEma>
+__device__ __forceinline__ void adamw_element(float* __restrict__ param, const float* __restrict__ grad,
+                                              float* __restrict__ m, float* __restrict__ v, float* __restrict__ ema,
+                                              long i, const AdamwStep& k, bool fused_scale) {
+#pragma clang fp contract(off)
+  const float gi = grad[i] * k.gs;
+  const float g = gi * k.coef;
+  float mi = m[i];
+  const float inner = fused_scale ? fmaf(grad[i], k.gs, -mi) : fmaf(gi, k.coef, -mi);
+  mi = fmaf(1.0f - k.b1, inner, mi);                          // exp_avg.lerp_(grad, 1 - beta1)
+  const float vi = fmaf(g, (1.0f - k.b2) * g, v[i] * k.b2);   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
+  const float denom = sqrtf(vi) / k.bc2_sqrt + k.eps;
+  const float p = fmaf(k.decay, param[i], -(k.step_size * (mi / denom)));   // param.addcdiv_(exp_avg, denom, -step_size)
+  param[i] = p;
+  m[i] = mi;
+  v[i] = vi;
+  if (kEma) {
+    const float e = ema[i];
+    ema[i] = fmaf(k.w, p - e, e);
+  }
+}
+
 template <bool kEma>
 __global__ void __launch_bounds__(256) adamw_update_kernel(float* __restrict__ param, const float* __restrict__ grad,
                                                            float* __restrict__ m, float* __restrict__ v,
@@ -539,41 +405,17 @@ __global__ void __launch_bounds__(256) adamw_update_kernel(float* __restrict__ p
                                                            const float* __restrict__ hyper,
                                                            const float* __restrict__ clip, int* __restrict__ guard) {
 #pragma clang fp contract(off)
-  if (guard) {
-    const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      if (!finite) guard[0] = guard[0] + 1;
-      guard[1] = finite ? 0 : 1;
-    }
-    if (!finite) return;
-  }
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
-  const float bc1 = hyper[5], bc2 = hyper[6], gs = hyper[7];
-  const float step_size = lr / bc1;
-  const float bc2_sqrt = sqrtf(bc2);
-  const float decay = fmaf(-lr, wd, 1.0f);               // decoupled weight decay
-  const float coef = clip ? clip[1] : 1.0f;
-  const float w = kEma ? hyper[8] : 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const float gi = grad[i] * gs;
-    const float g = gi * coef;
-    float mi = m[i];
-    // g - exp_avg: the plain update without the average was first compiled with the scaling fused into the
-    // subtraction (grad[i] * grad_scale not rounded), every other variant multiplies the rounded gi by the
-    // coefficient.  The two differ when grad_scale is not a power of two; each entry keeps its own bits.
-    const float inner = (kEma || clip) ? fmaf(gi, coef, -mi) : fmaf(grad[i], gs, -mi);
-    mi = fmaf(1.0f - b1, inner, mi);                        // exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = fmaf(g, (1.0f - b2) * g, v[i] * b2);   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float p = fmaf(decay, param[i], -(step_size * (mi / denom)));   // param.addcdiv_(exp_avg, denom, -step_size)
-    param[i] = p;
-    m[i] = mi;
-    v[i] = vi;
-    if (kEma) {
-      const float e = ema[i];
-      ema[i] = fmaf(w, p - e, e);
-    }
-  }
+  if (!adamw_guard_passes(clip, guard)) return;
+  const float lr = hyper[0], wd = hyper[4], bc1 = hyper[5], bc2 = hyper[6];
+  const AdamwStep k = {hyper[1], hyper[2], hyper[3], hyper[7], lr / bc1, sqrtf(bc2),
+                       fmaf(-lr, wd, 1.0f),                 // decoupled weight decay
+                       clip ? clip[1] : 1.0f, kEma ? hyper[8] : 0.f};
+  // g - exp_avg: the plain update without the average was first compiled with the scaling fused into the
+  // subtraction (grad[i] * grad_scale not rounded), every other variant multiplies the rounded gi by the
+  // coefficient.  The two differ when grad_scale is not a power of two; each entry keeps its own bits.
+  const bool fused_scale = !(kEma || clip);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+    adamw_element<kEma>(param, grad, m, v, ema, i, k, fused_scale);
 }
 
 // ema == nullptr: no average (hyper has 8 floats), else hyper has 9.  n >= 1 when there is a guard (the grid's
@@ -591,7 +433,7 @@ hipError_t launch_adamw_update(float* param, const float* grad, float* m, float*
 }
 
 // ---------------------------------------------------------------- AdamW per slice, with group constants
-// adamw_update_kernel's element expression over a slice table instead of [0, n): workgroup k updates the elements
+// adamw_element over a slice table instead of [0, n): workgroup k updates the elements
 // [begin, begin + len) of row k = {begin, len, group} (len <= kClipSlice) with lr = hyper[0] * ghyper[group][0],
 // the product rounded to fp32 once, and weight_decay = ghyper[group][1]; hyper[4] is not read.  An element outside
 // every row is neither read nor written, in any array.  The moment's inner term is always the rounded-product
@@ -606,43 +448,16 @@ __global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ p
                                                            const long* __restrict__ slices,
                                                            const float* __restrict__ clip, int* __restrict__ guard) {
 #pragma clang fp contract(off)
-  if (guard) {
-    const bool finite = (__float_as_uint(clip[0]) & 0x7f800000u) != 0x7f800000u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      if (!finite) guard[0] = guard[0] + 1;
-      guard[1] = finite ? 0 : 1;
-    }
-    if (!finite) return;
-  }
+  if (!adamw_guard_passes(clip, guard)) return;
   const long* S = slices + (long)blockIdx.x * kSliceCols;
   const long begin = S[0];
   const int len = (int)S[1];
   const float* gh = ghyper + 2 * S[2];
-  const float lr = hyper[0] * gh[0], wd = gh[1];
-  const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3];
-  const float bc1 = hyper[5], bc2 = hyper[6], gs = hyper[7];
-  const float step_size = lr / bc1;
-  const float bc2_sqrt = sqrtf(bc2);
-  const float decay = fmaf(-lr, wd, 1.0f);               // decoupled weight decay
-  const float coef = clip ? clip[1] : 1.0f;
-  const float w = kEma ? hyper[8] : 0.f;
-  for (int j = threadIdx.x; j < len; j += 256) {
-    const long i = begin + j;
-    const float gi = grad[i] * gs;
-    const float g = gi * coef;
-    float mi = m[i];
-    mi = fmaf(1.0f - b1, fmaf(gi, coef, -mi), mi);
-    const float vi = fmaf(g, (1.0f - b2) * g, v[i] * b2);
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float p = fmaf(decay, param[i], -(step_size * (mi / denom)));
-    param[i] = p;
-    m[i] = mi;
-    v[i] = vi;
-    if (kEma) {
-      const float e = ema[i];
-      ema[i] = fmaf(w, p - e, e);
-    }
-  }
+  const float lr = hyper[0] * gh[0], wd = gh[1], bc1 = hyper[5], bc2 = hyper[6];
+  const AdamwStep k = {hyper[1], hyper[2], hyper[3], hyper[7], lr / bc1, sqrtf(bc2),
+                       fmaf(-lr, wd, 1.0f),                 // decoupled weight decay
+                       clip ? clip[1] : 1.0f, kEma ? hyper[8] : 0.f};
+  for (int j = threadIdx.x; j < len; j += 256) adamw_element<kEma>(param, grad, m, v, ema, begin + j, k, false);
 }
 
 // nslices >= 1; the table's rows are validated by the caller.  ema, clip, guard as in launch_adamw_update.

@@ -30,7 +30,10 @@
   checkpoint is written with them folded into its first and last Linears.
 * `LpLoss(kind, component_weights, normalizer)` -- the original GNOT code's named losses (rel2, rel1, relinf, mse,
   l1, linf) with per-component weights through gnot_lp_loss, its `terms()` per (sample, channel),
-  `evaluate_table` (the per-sample error table of a test set) and `fit(log_components=True)`.
+  `evaluate_table` (the per-sample error table of a test set) and `fit(log_components=True)`.  Every loss entry
+  runs the one kernel family of gnot_lp_loss: gnot_rel_l2_loss and gnot_mse_loss (and their _affine forms) are
+  its kinds rel2 and mse without weights and terms, so `LpLoss("rel2")` / `LpLoss("mse")` launch what
+  `RelL2Loss()` / `MSELoss()` launch, with the terms or without.
 * `param_groups` / `FlatAdamW(groups=, layout=)` / `fit(freeze=, no_decay=, lr_scale=)` -- fine-tuning: fnmatch
   patterns over the state_dict names resolve to frozen tensors and AdamW parameter groups, and the norm and the
   update run over a slice table of the trainable tensors (gnot_grad_norm_groups / gnot_grad_clip_groups,

@@ -356,8 +356,12 @@ int gnot_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_
 /* MSELoss (reference loss.py:4-12, the dgl AvgPooling as packed segment means), same arguments as
  * gnot_rel_l2_loss: loss = 1/(B C) sum_b sum_c (1/N_b) sum_n (p-t)^2 to *loss (device) and, if
  * dpred != NULL, d loss / d pred = 2 (p-t) / (B C N_b).  work: device scratch of
- * gnot_mse_work_floats(off_host, B, C) floats.  Every sample needs at least one row (GNOT_E_INVALID,
- * "empty sample": its mean is undefined).  Deterministic (fixed-order reductions). */
+ * gnot_mse_work_floats(off_host, B, C) floats = B*nsplit*C + B*C (nsplit: the 2048-row splits of the longest
+ * sample): the partial sums [B][nsplit][C], then the gradient scale 2 / (B C N_b) per (sample, channel) [B][C].
+ * Size the buffer by the query, never by a formula of your own.  Every sample needs at least one row
+ * (GNOT_E_INVALID, "empty sample": its mean is undefined).  Deterministic (fixed-order reductions).
+ * gnot_rel_l2_loss and gnot_mse_loss are GNOT_LP_REL2 and GNOT_LP_MSE of gnot_lp_loss (below) without
+ * comp_weights and terms: the same kernels. */
 size_t gnot_mse_work_floats(const int64_t* off_host, int B, int C);
 int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host, int B, int C,
                   float* work, float* loss, float* dpred, void* stream);
@@ -559,7 +563,7 @@ int gnot_mse_loss_affine(const float* pred, const float* tgt, const int64_t* off
  * linf are metrics only: a dpred with them is GNOT_E_INVALID, as are an unknown kind and a sample without rows
  * ("empty sample"), all before any launch.  A relative kind with an all-zero target channel gives inf / NaN, like
  * gnot_rel_l2_loss (no epsilon).  Without comp_weights, REL2 and MSE give the bits of gnot_rel_l2_loss(_affine) /
- * gnot_mse_loss(_affine), loss and dpred alike (without terms too, they launch those entries' kernels).  work: device
+ * gnot_mse_loss(_affine), loss and dpred alike (those entries are these two kinds: one set of kernels).  work: device
  * scratch of gnot_lp_loss_work_floats(off_host, B, C) floats.  Three launches at most (partial sums per 2048-row
  * split, one finish workgroup, the elementwise gradient), fixed-order reductions, no atomics, no host
  * synchronisation: deterministic and capturable. */

@@ -5,6 +5,7 @@
     GNOT_LIB=<b.so> python scripts/diag_bitwise_ab.py dump gpurun_out/b.npz
     python scripts/diag_bitwise_ab.py compare gpurun_out/a.npz gpurun_out/b.npz
     GNOT_LIB=<a.so> python scripts/diag_bitwise_ab.py record tests/golden/train_step_bits.npz
+    GNOT_LIB=<a.so> python scripts/diag_bitwise_ab.py record-family tests/golden/train_family_bits.npz
 
 Each case runs one training forward + backward (sum(out * G)) and stores the output and the flat gradient
 arena: d = 256 / E = 8 (configs[2]'s widths) in fp32, bf16 mode and with MoE recompute, d = 128 / E = 4 /
@@ -12,8 +13,11 @@ two input functions (configs[1]'s) in fp32 and bf16 mode, d = 64 (chain.hip; onc
 storing x.grad), and five widths of tests/test_gpu_widths.py (WIDTH_CASES).  Every case also stores the packed
 weight images and biases as they lie in the workspace (layout and content).  Then the training step
 (tests/train_step_util.py step_replay): every AdamW entry, both norm entries and both losses at n = 1, 257, 8195
-and 524291.  `record` writes the inputs and results of the first three sizes as the fixture of
-tests/test_gpu_train_bits.py.
+and 524291, and the loss family and the slice-table update (loss_replay): RelL2Loss, MSELoss and every LpLoss kind,
+raw and with a normalizer, with and without component weights, and gnot_adamw_step_groups behind the slice-table
+norm entries.  `record` writes the inputs and results of the first three sizes, `record-family` those of
+loss_replay, as the two fixtures of tests/test_gpu_train_bits.py; a fixture is recorded from the build BEFORE a
+change, which then has to reproduce it.
 """
 import os
 import sys
@@ -87,6 +91,7 @@ def dump(path):
         print(name, "done", flush=True)
     import train_step_util as U
     res.update({"step." + k: v for k, v in U.step_replay(U.step_inputs(U.NS)).items()})
+    res.update({"family." + k: v for k, v in U.loss_replay(U.loss_inputs()).items()})
     np.savez(path, **res)
 
 
@@ -97,13 +102,23 @@ def record(path):
     np.savez(path, **{"in." + k: v for k, v in inp.items()}, **{"out." + k: v for k, v in out.items()})
 
 
+def record_family(path):
+    import train_step_util as U
+    inp = U.loss_inputs()
+    out = U.loss_replay(inp)
+    np.savez_compressed(path, **{"in." + k: v for k, v in inp.items()}, **{"out." + k: v for k, v in out.items()})
+    size = os.path.getsize(path)
+    assert size <= 1 << 20, f"{path}: {size} bytes, more than a committed file may have"
+    print(f"{path}: {len(inp)} inputs, {len(out)} results, {size} bytes")
+
+
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     bad = 0
     assert sorted(A.files) == sorted(B.files)
     for k in A.files:
         same = A[k].tobytes() == B[k].tobytes()      # bits: a NaN equals itself
-        if not same or not k.startswith("step."):
+        if not same or not k.startswith(("step.", "family.")):
             print(f"{k:24s} {'bitwise equal' if same else 'DIFFERS in %d elements' % (A[k] != B[k]).sum()}")
         bad += not same
     print(f"{len(A.files)} arrays, {bad} differ")
@@ -111,7 +126,7 @@ def compare(a, b):
 
 
 if __name__ == "__main__":
-    if sys.argv[1] in ("dump", "record"):
-        {"dump": dump, "record": record}[sys.argv[1]](sys.argv[2])
+    if sys.argv[1] in ("dump", "record", "record-family"):
+        {"dump": dump, "record": record, "record-family": record_family}[sys.argv[1]](sys.argv[2])
     else:
         compare(sys.argv[2], sys.argv[3])

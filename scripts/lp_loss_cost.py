@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""What the Lp loss family costs beside the RelL2 entry: gnot_rel_l2_loss, gnot_lp_loss(rel2) and
+"""What the entries of the loss family cost: gnot_rel_l2_loss, gnot_mse_loss, gnot_lp_loss(rel2) and
 gnot_lp_loss(rel1, component weights), the last two with and without the per-sample terms, each with the gradient,
 on 262,144 packed rows (4 samples of 65,536) with C = 1 and C = 3 output channels.  --parent-lib names a
-libgnot_hip.so built from the parent commit, whose gnot_rel_l2_loss is then timed in the same process.
+libgnot_hip.so built from the parent commit, whose gnot_rel_l2_loss and gnot_mse_loss, and whose gnot_lp_loss for rel2
+and mse with the terms, are then timed in the same process.
 Every variant is timed in blocks of --calls back-to-back calls between two device events (one call is a few
 microseconds of kernels: a single one would time the events); the blocks of all variants are interleaved, repetition
-after repetition, after a warm-up, and the medians per call are reported.  rel2 without weights and terms launches the
-kernels of gnot_rel_l2_loss, so the two should sit inside the spread of repeated blocks (us_min .. us_max).
+after repetition, after a warm-up, and the medians per call are reported.  gnot_rel_l2_loss / gnot_mse_loss are
+gnot_lp_loss(rel2) / (mse) without weights and terms, so each pair should sit inside the spread of repeated blocks
+(us_min .. us_max), and under the same kind with the terms (the same kernels and one more store).
 
     python scripts/lp_loss_cost.py [--parent-lib PATH] [--reps 30] [--calls 200] [--out FILE]
 """
@@ -29,7 +31,7 @@ ROWS, B = 262144, 4
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parent-lib", default=None, help="a libgnot_hip.so of the parent commit (its gnot_rel_l2_loss)")
+    ap.add_argument("--parent-lib", default=None, help="a libgnot_hip.so of the parent commit, timed beside this tree's")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=200, help="calls per timed block")
@@ -41,6 +43,8 @@ def main():
     if args.parent_lib:
         parent = ctypes.CDLL(args.parent_lib)
         parent.gnot_rel_l2_loss.argtypes = lib.gnot_rel_l2_loss.argtypes
+        parent.gnot_mse_loss.argtypes = lib.gnot_mse_loss.argtypes
+        parent.gnot_lp_loss.argtypes = lib.gnot_lp_loss.argtypes
     s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     P = lambda t: None if t is None else t.data_ptr()
     off = [b * (ROWS // B) for b in range(B + 1)]
@@ -55,12 +59,17 @@ def main():
         work = torch.empty(lib.gnot_lp_loss_work_floats(oh, B, C), device=dev)
         loss, terms, dpred = torch.empty((), device=dev), torch.empty(B, C, device=dev), torch.empty_like(pred)
         head = (P(pred), P(tgt), P(off_dev), oh, B, C)
-        lp = lambda kind, wt, tm: (lambda: lib.gnot_lp_loss(*head, _lib.LP_KINDS[kind], P(wt), None, P(work), P(loss),
-                                                            P(tm), P(dpred), s))
+        lp = lambda kind, wt, tm, of=lib: (lambda: of.gnot_lp_loss(*head, _lib.LP_KINDS[kind], P(wt), None, P(work),
+                                                                   P(loss), P(tm), P(dpred), s))
+        tail = (P(work), P(loss), P(dpred), s)
         runs = {}
         if parent is not None:
-            runs["parent_rel_l2"] = lambda: parent.gnot_rel_l2_loss(*head, P(work), P(loss), P(dpred), s)
-        runs.update({"rel_l2": lambda: lib.gnot_rel_l2_loss(*head, P(work), P(loss), P(dpred), s),
+            runs.update({"parent_rel_l2": lambda: parent.gnot_rel_l2_loss(*head, *tail),
+                         "parent_mse": lambda: parent.gnot_mse_loss(*head, *tail),
+                         "parent_lp_rel2_terms": lp("rel2", None, terms, parent),
+                         "parent_lp_mse_terms": lp("mse", None, terms, parent)})
+        runs.update({"rel_l2": lambda: lib.gnot_rel_l2_loss(*head, *tail),
+                     "mse": lambda: lib.gnot_mse_loss(*head, *tail),
                      "lp_rel2": lp("rel2", None, None), "lp_rel2_terms": lp("rel2", None, terms),
                      "lp_rel1_w": lp("rel1", w, None), "lp_rel1_w_terms": lp("rel1", w, terms)})
         times = {k: [] for k in runs}

@@ -103,7 +103,7 @@ def test_rel2_and_mse_carry_the_bits_of_the_existing_losses(i, kind, cls, with_n
     nz = normalizer(pred.shape[1]) if with_nz else None
     ref_loss, _, ref_g = run(cls(nz), off, pred, tgt, terms=False)
     assert float(ref_g.abs().max()) > 0
-    # without the terms (the existing kernels) and with them (the family's own kernels)
+    # without the terms and with them (one set of kernels; the finish kernel then stores the terms too)
     for terms in (False, True):
         loss, e, g = run(train.LpLoss(kind, normalizer=nz), off, pred, tgt, terms=terms)
         assert torch.equal(bits(loss), bits(ref_loss)), (terms, float(loss), float(ref_loss))

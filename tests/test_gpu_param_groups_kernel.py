@@ -6,13 +6,12 @@ trainable gradient against float64.
 The arena holds tensors of 1, 3, 255, 8191, 8192 and 8193 elements (one element, less than a 16-byte load, less
 than a workgroup's stride, one short of a slice, a slice, a slice and one element); the third and the last are
 frozen; three groups.  Every array's base is 0 to 3 floats behind a 16-byte boundary."""
-import ctypes
-
 import pytest
 import torch
 
 import train_step_util as U
-from gnot_amd import _lib, train
+from gnot_amd import train
+from train_step_util import Table, groups_norm, groups_step
 
 pytestmark = pytest.mark.gpu
 
@@ -27,42 +26,6 @@ for _k, _g in enumerate(GROUP_OF):
     if _g is None:
         FROZEN[BOUNDS[_k]:BOUNDS[_k + 1]] = True
 OFFSETS = [0, 1, 2, 3]
-
-
-class Table:
-    """a slice table on the device and on the host, and the group constants"""
-
-    def __init__(self, rows, ghyper):
-        self.n = len(rows)
-        self.host = (ctypes.c_int64 * (3 * self.n))(*[v for r in rows for v in r])
-        self.dev = torch.tensor(rows, dtype=torch.int64).cuda()
-        self.ghyper = torch.tensor(ghyper, dtype=torch.float32).cuda()
-        self.G = len(ghyper)
-
-
-def groups_norm(g, n, hyper, table, max_norm=None):
-    """clip [2] of gnot_grad_clip_groups (max_norm given) or gnot_grad_norm_groups; work has nslices floats and
-    nothing is written behind them or behind clip"""
-    lib = _lib.load()
-    work = torch.full((table.n + 1,), U.PAD, dtype=torch.float32, device="cuda")
-    clip = torch.full((3,), U.PAD, dtype=torch.float32, device="cuda")
-    if max_norm is None:
-        _lib.check(lib.gnot_grad_norm_groups(g.data_ptr(), n, hyper.data_ptr(), table.dev.data_ptr(), table.host,
-                                             table.n, work.data_ptr(), clip.data_ptr(), U.stream()))
-    else:
-        _lib.check(lib.gnot_grad_clip_groups(g.data_ptr(), n, hyper.data_ptr(), max_norm, table.dev.data_ptr(),
-                                             table.host, table.n, work.data_ptr(), clip.data_ptr(), U.stream()))
-    assert float(work[table.n]) == U.PAD and float(clip[2]) == U.PAD
-    return clip[:2]
-
-
-def groups_step(a, g, hyper, table, clip=None, guard=None, ema=False):
-    """gnot_adamw_step_groups on the U.Arrays a; the PAD elements around every array stay"""
-    _lib.check(_lib.load().gnot_adamw_step_groups(
-        a.p.data_ptr(), g.data_ptr(), a.m.data_ptr(), a.v.data_ptr(), a.e.data_ptr() if ema else None, a.n,
-        hyper.data_ptr(), table.ghyper.data_ptr(), table.G, table.dev.data_ptr(), table.host, table.n,
-        None if clip is None else clip.data_ptr(), None if guard is None else guard.data_ptr(), U.stream()))
-    a._check_pads()
 
 
 # ------------------------------------------------------------------ against torch's parameter groups

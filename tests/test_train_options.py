@@ -59,6 +59,9 @@ def test_grad_clip_refuses_null_pointers():
 def test_work_sizes():
     lib = _lib.load()
     assert lib.gnot_mse_work_floats(_off([0, 37, 38, 5038, 7087]), 4, 3) > 0
+    # the longest sample has 5000 rows, three splits: partial sums [B][nsplit][C] and the gradient scales [B][C]
+    B, nsplit, C = 4, 3, 3
+    assert lib.gnot_mse_work_floats(_off([0, 37, 38, 5038, 7087]), B, C) == B * nsplit * C + B * C
     # one more 2048-row split needs more room
     assert lib.gnot_mse_work_floats(_off([0, 2049]), 1, 1) > lib.gnot_mse_work_floats(_off([0, 2048]), 1, 1)
     sizes = [lib.gnot_grad_clip_work_floats(n) for n in (1, 255, 257, 524291)]

@@ -1,11 +1,13 @@
 """What the GPU tests of the native training step share (test_gpu_train_options.py, test_gpu_train_state.py,
-test_gpu_ema.py, test_gpu_train_bits.py): arrays with sentinels around them, the hyper-parameter vector, the
-norm entries, the four update entries, and a small model with list-of-batches loaders."""
+test_gpu_ema.py, test_gpu_param_groups_kernel.py, test_gpu_train_bits.py): arrays with sentinels around them, the
+hyper-parameter vector, the norm entries, the four update entries and the slice-table ones, a small model with
+list-of-batches loaders, and the inputs and replays of the two files of recorded bits."""
 import ctypes
 
 import numpy as np
 import torch
 
+import lp_util as L
 from gnot_amd import _lib, train
 
 SMALL = (2, 1, 3, 1, 1, 32, 2, 32, 32, 2, 4, 1)      # the model of test_train.py / test_gpu_train_loop.py
@@ -126,6 +128,42 @@ class Arrays:
 
 def guard():
     return torch.zeros(3, dtype=torch.int32, device="cuda")      # {skipped, skipped now} and an element behind
+
+
+class Table:
+    """a slice table on the device and on the host, and the group constants"""
+
+    def __init__(self, rows, ghyper):
+        self.n = len(rows)
+        self.host = (ctypes.c_int64 * (3 * self.n))(*[v for r in rows for v in r])
+        self.dev = torch.tensor(rows, dtype=torch.int64).cuda()
+        self.ghyper = torch.tensor(ghyper, dtype=torch.float32).cuda()
+        self.G = len(ghyper)
+
+
+def groups_norm(g, n, hyper, table, max_norm=None):
+    """clip [2] of gnot_grad_clip_groups (max_norm given) or gnot_grad_norm_groups; work has nslices floats and
+    nothing is written behind them or behind clip"""
+    lib = _lib.load()
+    work = torch.full((table.n + 1,), PAD, dtype=torch.float32, device="cuda")
+    clip = torch.full((3,), PAD, dtype=torch.float32, device="cuda")
+    if max_norm is None:
+        _lib.check(lib.gnot_grad_norm_groups(g.data_ptr(), n, hyper.data_ptr(), table.dev.data_ptr(), table.host,
+                                             table.n, work.data_ptr(), clip.data_ptr(), stream()))
+    else:
+        _lib.check(lib.gnot_grad_clip_groups(g.data_ptr(), n, hyper.data_ptr(), max_norm, table.dev.data_ptr(),
+                                             table.host, table.n, work.data_ptr(), clip.data_ptr(), stream()))
+    assert float(work[table.n]) == PAD and float(clip[2]) == PAD
+    return clip[:2]
+
+
+def groups_step(a, g, hyper, table, clip=None, guard=None, ema=False):
+    """gnot_adamw_step_groups on the Arrays a; the PAD elements around every array stay"""
+    _lib.check(_lib.load().gnot_adamw_step_groups(
+        a.p.data_ptr(), g.data_ptr(), a.m.data_ptr(), a.v.data_ptr(), a.e.data_ptr() if ema else None, a.n,
+        hyper.data_ptr(), table.ghyper.data_ptr(), table.G, table.dev.data_ptr(), table.host, table.n,
+        None if clip is None else clip.data_ptr(), None if guard is None else guard.data_ptr(), stream()))
+    a._check_pads()
 
 
 def bad_index(n, where):
@@ -254,4 +292,135 @@ def step_replay(inp):
         loss.backward()
         out[f"loss.{cls.__name__}.loss"] = as_bits(loss.reshape(1))
         out[f"loss.{cls.__name__}.dpred"] = as_bits(pred.grad)
+    return out
+
+
+# ------------------------------------------------------------------ recorded bits (tests/golden/train_family_bits.npz)
+# The same for the loss family and the slice-table update, written by the build before RelL2Loss / MSELoss moved
+# onto the Lp kernels and the two AdamW kernels onto one element update (scripts/diag_bitwise_ab.py record-family).
+FAMILY_F1E_OFF = [0, 37, 37, 38, 2087]    # LOSS_SIZES' rows with an empty sample: gnot_rel_l2_loss alone takes one
+FAMILY_F2_SIZES = [4096, 4097]            # one channel: the exact multiple of the split, two splits and a row
+FAMILY_WEIGHTS = [1.0, 0.0, 3.0]
+FAMILY_NZ = ([0.3, -1.7, 0.05], [1.9, 0.6, 3.3])      # y mean / std, no powers of two: pred * std + mean rounds
+GROUPS_N, GROUPS_H7 = 257, 0.3
+GROUPS_ROWS = [[0, 100, 0], [130, 127, 1]]            # elements 100 to 129 are frozen
+GROUPS_GHYPER = [[1.0, 0.01], [0.5, 0.0]]
+GROUPS_KINDS = ("plain", "clip_lt1", "guard", "guard_nan")
+GROUPS_NAN_AT = 50                                    # guard_nan: a trainable element of the gradient
+
+
+def _groups_frozen():
+    live = torch.zeros(GROUPS_N, dtype=torch.bool)
+    for begin, length, _ in GROUPS_ROWS:
+        live[begin:begin + length] = True
+    return ~live
+
+
+def loss_inputs():
+    """the inputs of loss_replay, drawn here once and stored with the results"""
+    gen = torch.Generator().manual_seed(12)
+    inp = {}
+    for name, rows, C in (("f1", sum(LOSS_SIZES), LOSS_C), ("f2", sum(FAMILY_F2_SIZES), 1)):
+        inp[name + ".pred"] = torch.randn(rows, C, generator=gen).numpy()
+        inp[name + ".tgt"] = (torch.randn(rows, C, generator=gen) + 0.5).numpy()     # every denominator positive
+    a = Arrays(GROUPS_N)
+    g = torch.randn(GROUPS_N, generator=gen)
+    for k, t in (("p", a.p), ("m", a.m), ("v", a.v), ("e", a.e), ("g", g)):
+        inp["g." + k] = t.cpu().numpy()
+    norm64 = float(g[~_groups_frozen()].double().pow(2).sum().sqrt())
+    inp["g.max_norm"] = np.array([0.5 * GROUPS_H7 * norm64], dtype=np.float32)       # it clips
+    return inp
+
+
+def _loss_pass(fn, off, pred, tgt, grad, terms=False):
+    """(loss [1], terms or None, dpred or None) of one pass of the loss module fn"""
+    p = pred.clone().requires_grad_(grad)
+    loss, e = fn.loss_and_terms(off, p, tgt) if terms else (fn(off, p, tgt), None)
+    if grad:
+        loss.backward()
+    return loss.detach().reshape(1), e, p.grad
+
+
+def loss_replay(inp):
+    """{name: array of bits} of the blocks F1, F1e, F2 (RelL2Loss, MSELoss and LpLoss; raw and with a normalizer,
+    with and without component weights) and G (gnot_adamw_step_groups behind the slice-table norm entries) on the
+    inputs inp.  Asserts on the way that an LpLoss gives the same bits with and without the terms, and that
+    rel2 / mse without weights give those of RelL2Loss / MSELoss."""
+    from gnot_amd import Normalizer
+    as_bits = lambda t: t.detach().cpu().contiguous().view(torch.int32).numpy()
+    same = lambda x, y: (x is None and y is None) or torch.equal(bits(x), bits(y))
+    dev = lambda k: torch.from_numpy(np.asarray(inp[k])).cuda()
+    nzs = lambda C: (("raw", None), ("nz", Normalizer.from_stats(([0.0], [1.0]), ([0.0], [1.0]),
+                                                                 (FAMILY_NZ[0][:C], FAMILY_NZ[1][:C]))))
+    out = {}
+
+    def classes(block, off, pred, tgt):
+        """RelL2Loss and, unless a sample is empty, MSELoss: {(class name, raw / nz): (loss, None, dpred)}"""
+        res = {}
+        for cls in (train.RelL2Loss, train.MSELoss)[:1 if block == "f1e" else 2]:
+            for tag, nz in nzs(pred.shape[1]):
+                res[cls.__name__, tag] = r = _loss_pass(cls(nz), off, pred, tgt, True)
+                out[f"{block}.{cls.__name__}.{tag}.loss"] = as_bits(r[0])
+                out[f"{block}.{cls.__name__}.{tag}.dpred"] = as_bits(r[2])
+        return res
+
+    def family(block, off, pred, tgt, ref, weights, tags, dpred_kinds):
+        for kind in L.KINDS:
+            for wtag, w in weights:
+                for tag, nz in nzs(pred.shape[1]):
+                    if tag not in tags:
+                        continue
+                    grad = kind in L.DIFFERENTIABLE
+                    r = _loss_pass(train.LpLoss(kind, w, nz), off, pred, tgt, grad, terms=True)
+                    bare = _loss_pass(train.LpLoss(kind, w, nz), off, pred, tgt, grad)
+                    name = f"{block}.lp.{kind}.{wtag}.{tag}"
+                    assert same(r[0], bare[0]) and same(r[2], bare[2]), name
+                    if w is None and kind in ("rel2", "mse"):
+                        c = ref["RelL2Loss" if kind == "rel2" else "MSELoss", tag]
+                        assert same(r[0], c[0]) and same(r[2], c[2]), name
+                    out[name + ".loss"], out[name + ".terms"] = as_bits(r[0]), as_bits(r[1])
+                    if kind in dpred_kinds:
+                        out[name + ".dpred"] = as_bits(r[2])
+
+    off1 = np.concatenate([[0], np.cumsum(LOSS_SIZES)]).tolist()
+    pred, tgt = dev("f1.pred"), dev("f1.tgt")
+    family("f1", off1, pred, tgt, classes("f1", off1, pred, tgt), (("u", None), ("w", FAMILY_WEIGHTS)),
+           ("raw", "nz"), L.DIFFERENTIABLE)
+    classes("f1e", FAMILY_F1E_OFF, pred, tgt)
+    off2 = np.concatenate([[0], np.cumsum(FAMILY_F2_SIZES)]).tolist()
+    pred, tgt = dev("f2.pred"), dev("f2.tgt")
+    family("f2", off2, pred, tgt, classes("f2", off2, pred, tgt), (("u", None),), ("raw",), ("rel1", "l1"))
+
+    # G: the slice-table update; the frozen range of the gradient holds NaN, and every array is stored as its
+    # whole allocation, the elements around it and the frozen gap included
+    n, frozen = GROUPS_N, _groups_frozen()
+    p, m, v, e = (torch.from_numpy(np.asarray(inp["g." + k])) for k in "pmve")
+    g = torch.from_numpy(np.asarray(inp["g.g"])).clone()
+    g[frozen] = float("nan")
+    g_nan = g.clone()
+    g_nan[GROUPS_NAN_AT] = float("nan")
+    max_norm = float(inp["g.max_norm"][0])
+    table = Table(GROUPS_ROWS, GROUPS_GHYPER)
+    for offset in (0, 1):
+        for kind in GROUPS_KINDS:
+            for ema in (False, True):
+                name = f"g.o{offset}.{kind}.{'ema' if ema else 'raw'}"
+                hy = hyper(GROUPS_H7, w=9 / 11 if ema else None)
+                start = Arrays(n, offset, (p, m, v, e))
+                gd = _based_on(g_nan if kind == "guard_nan" else g, offset)
+                clip = None if kind == "plain" else groups_norm(gd, n, hy, table,
+                                                                None if kind == "guard_nan" else max_norm)
+                gu = guard() if kind.startswith("guard") else None
+                got = start.copy()
+                groups_step(got, gd, hy, table, clip, gu, ema)
+                if clip is not None:
+                    out[name + ".clip"] = as_bits(clip)
+                if gu is not None:
+                    out[name + ".guard"] = gu.cpu().numpy()
+                if kind == "guard_nan":
+                    out[name + ".untouched"] = np.array([got.differing(start) == []])
+                else:
+                    assert got.differing(start) == ["p", "m", "v"] + ["e"] * ema, name
+                for k in "pmve" if ema else "pmv":
+                    out[f"{name}.{k}b"] = as_bits(getattr(got, k + "b"))
     return out
