@@ -2,7 +2,8 @@
 // exercises every C-ABI entry point that needs no GPU -- plan creation for the supported widths and for the edges
 // of the other constructor arguments (depth, blocks, theta_dim 0, experts, input functions, input / output widths), packed
 // batch geometries (ragged, empty samples, many meshes, padded-equal strides), MoE recompute and
-// precision switches, the pre-norm option, workspace sizing, gradient offsets, the caller-owned gradient arena, the flag
+// precision switches, the pre-norm option, the shapes of an attention call (fused, input-function sources, padded heads,
+// frozen blocks) with their backward plans, workspace sizing, gradient offsets, the caller-owned gradient arena, the flag
 // validation of gnot_backward_ex, the point-shard exchange tables and the error paths -- so heap overflows / use-after-free in engine.cpp's table building show up on the CPU.
 // Run by tests/test_asan.py; exit status 0 = every check passed and ASan reported nothing.
 #include <cstdint>
@@ -27,10 +28,21 @@ static int g_fail = 0;
 // FNV-1a over every workspace size the program sees, in order: two builds of the planning code that print the
 // same digest lay every geometry below out in the same number of bytes
 static uint64_t g_digest = 0xcbf29ce484222325ull;
+static void fold(uint64_t v) {
+  for (int k = 0; k < 8; ++k) g_digest = (g_digest ^ (v >> (8 * k) & 0xff)) * 0x100000001b3ull;
+}
 static size_t ws_bytes(const gnot_plan* p) {
   const size_t v = gnot_plan_workspace_bytes(p);
-  for (int k = 0; k < 8; ++k) g_digest = (g_digest ^ ((uint64_t)v >> (8 * k) & 0xff)) * 0x100000001b3ull;
+  fold(v);
   return v;
+}
+// ... and over the backward plan of every training plan: its weight-gradient job count and lowest stage
+static void fold_backward_plan(const gnot_plan* p) {
+  int jobs = -1, stage = -99;
+  CHECK(gnot_debug_backward_plan(p, &jobs, &stage) == GNOT_OK);
+  CHECK(jobs >= 0);
+  fold((uint64_t)(int64_t)jobs);
+  fold((uint64_t)(int64_t)stage);
 }
 
 static int fake_allreduce(void*, float*, int64_t, void*) { return 0; }
@@ -78,6 +90,7 @@ static void exercise(const gnot_config& cfg, std::mt19937& rng) {
           }
           CHECK(st == GNOT_OK);
           CHECK(ws_bytes(p) > 0);
+          if (tr) fold_backward_plan(p);
           std::vector<int64_t> go(2 * nlin);
           CHECK(gnot_plan_grad_offsets(p, go.data()) == GNOT_OK);
           int64_t expect = 0;
@@ -103,7 +116,10 @@ static void exercise(const gnot_config& cfg, std::mt19937& rng) {
       const auto lo = offsets(loc);
       const int st = gnot_plan_set_batch(p, B, lo.data(), I ? fo.data() : nullptr, 1);
       CHECK(st == GNOT_OK || lo.back() == 0);
-      if (st == GNOT_OK) CHECK(ws_bytes(p) > 0);
+      if (st == GNOT_OK) {
+        CHECK(ws_bytes(p) > 0);
+        fold_backward_plan(p);
+      }
       // a geometry that does not match the declared shard is refused
       if (lo.back() > 0) {
         auto bad = lo;
@@ -353,6 +369,56 @@ static void dropout() {
   CHECK(gnot_dropout_rows(buf, 4, 1, 4, tab, tab, 1, key, 0, 1.f, nullptr) == GNOT_E_INVALID);
 }
 
+// the shapes of an attention call (inside the layout digest): a cross module without input functions (the fused
+// q|k|v form) over two blocks, two input functions, padded heads (d = 100, 4 heads: one weight-gradient job per
+// head), and the encoders and block 0 frozen (the batched input-function side runs a suffix of the blocks) --
+// each with and without pre-norm and gnot_plan_set_input_grads, on a batch with empty samples, a one-point
+// sample and a sample that ends on a 64-point segment edge
+static void attn_calls() {
+  const std::vector<int64_t> n = {65, 0, 1, 0, 128}, m = {17, 5, 1, 0, 64};
+  const auto xo = offsets(n);
+  const int models[][4] = {{32, 4, 0, 0}, {32, 4, 2, 0}, {100, 4, 1, 0}, {32, 4, 2, 1}};   // d, H, I, frozen
+  for (const auto& md : models) {
+    const int I = md[2];
+    gnot_config c{};
+    c.input_dim = 2; c.theta_dim = 1; c.input_func_dim = 3; c.out_dim = 2; c.n_attn_layers = 2;
+    c.n_attn_hidden_dim = c.n_mlp_hidden_dim = c.n_input_hidden_dim = md[0];
+    c.n_mlp_num_layers = 2; c.n_expert = 2; c.n_head = md[1]; c.n_input_functions = I;
+    gnot_plan* p = nullptr;
+    CHECK(gnot_plan_create(&c, &p) == GNOT_OK);
+    if (!p) continue;
+    std::vector<int64_t> fo;
+    for (int i = 0; i < I; ++i) {
+      const auto o = offsets(m);
+      fo.insert(fo.end(), o.begin(), o.end());
+    }
+    const int nlin = gnot_plan_num_linears(p), NL = 3, KI = I > 0 ? I : 1;
+    std::vector<uint8_t> mask(nlin, 1);
+    const int frozen_upto = 2 * NL + I * NL + 6 + 2 * KI + 2 * c.n_expert * NL;   // the encoders and block 0
+    for (int k = 0; k < frozen_upto && md[3]; ++k) mask[k] = 0;
+    CHECK(gnot_plan_set_trainable(p, md[3] ? mask.data() : nullptr) == GNOT_OK);
+    int plain_jobs = -1;
+    for (int pn = 0; pn < 2; ++pn)
+      for (int ig = 0; ig < 2; ++ig) {
+        CHECK(gnot_plan_set_pre_norm(p, pn, 1e-5f) == GNOT_OK);
+        CHECK(gnot_plan_set_input_grads(p, ig) == GNOT_OK);
+        CHECK(gnot_plan_set_batch(p, (int)n.size(), xo.data(), I ? fo.data() : nullptr, 0) == GNOT_OK);
+        CHECK(ws_bytes(p) > 0);
+        CHECK(gnot_plan_set_batch(p, (int)n.size(), xo.data(), I ? fo.data() : nullptr, 1) == GNOT_OK);
+        CHECK(ws_bytes(p) > 0);
+        fold_backward_plan(p);
+        int jobs = 0, stage = 0;
+        CHECK(gnot_debug_backward_plan(p, &jobs, &stage) == GNOT_OK);
+        CHECK(stage == (ig ? -1 : md[3] ? 1 : -1));
+        if (plain_jobs < 0) plain_jobs = jobs;
+        CHECK(jobs == plain_jobs);             // neither option adds or removes a weight-gradient job
+        char forms[512];
+        CHECK(gnot_debug_kernel_forms(p, forms, sizeof forms) == GNOT_OK);
+      }
+    gnot_plan_destroy(p);
+  }
+}
+
 int main() {
   std::mt19937 rng(12345);
   // {width, heads}: 96 / 192 have head widths 12 / 24; 320 runs chainw.hip, 576 (internal width 640) the
@@ -425,6 +491,7 @@ int main() {
     gnot_plan_destroy(p);
   }
   exchange(rng);
+  attn_calls();
   pre_norm();
   dropout();
   std::printf("layout digest: %016llx\n", (unsigned long long)g_digest);

@@ -96,6 +96,40 @@ struct Chain {
   WgradGroup wg;                     // the weight gradients of its Linears
 };
 
+// One set of states an attention call's apply passes read: the query points' own (a fused call) or those of input
+// function `fn` (ckv: its K | V rows, dkv: their gradient, enc: the encoding rows the K / V projections read)
+struct AttnSrc {
+  std::string state, du, dden, dstate;   // S | z per sample; the backward's du, dden rows and its dS | dz
+  int fn = -1;
+  std::string ckv, dkv, enc;
+  WgradGroup st, dst;                // forward states (fused calls; input-function sources: the batched st_fn) and dS | dz
+};
+
+// One LinearAttention call of a block: cross (reading the block's query) or self (reading query1).
+// build_attn_calls states each once; plan_images, the carve, the groups, the batched input-function tables and
+// the forward / backward launches read it from here.  Buffers are names, resolved with P_ at use
+struct AttnCall {
+  int l = 0;
+  bool cross = false;
+  uint32_t site = 0;                 // dropout site: 2 l cross, 2 l + 1 self
+  bool fused = true;                 // one q|k|v projection of the query rows; else q alone and input-function sources
+  int nsrc = 1;                      // state sets the apply passes read (= src.size())
+  int q = 0, o = 0;                  // canonical Linears
+  std::vector<int> k, v;
+  Img proj_img, o_img;               // packed images (proj: q or q|k|v) and bias offsets in pbias (floats)
+  std::vector<Img> kv_img;           // K | V of every input-function source
+  size_t bproj = 0, bo = 0;
+  std::vector<size_t> bkv;
+  std::string in_raw, in, rstd;      // the rows it reads: raw, as projected (pre-norm: normalised, else in_raw), their rstd
+  std::string proj;                  // q or q | k | v rows
+  long pitch = 0;                    // ... of D or 3 D floats
+  std::vector<AttnSrc> src;
+  std::string res, out;              // scramble rows (Dr floats per token) and fc_out's rows
+  std::string dsum, dqkv;            // backward slots: d out, d proj
+  WgradGroup wg;                     // the weight gradients of o, q (and k, v of a fused call)
+  AttnKernel apply_fwd = {}, apply_bwd = {};   // kernel forms (choose_attn_forms)
+};
+
 // b + off, or null while b is unbound: the sizing pass of set_batch builds every job table for its size
 // only and forms no address
 template <typename T>
@@ -132,10 +166,6 @@ struct gnot_plan {
   // ("fnn{i}", shared by every block); the residual stream itself is untouched
   bool pre_norm = false;
   float norm_eps = 1e-5f;
-  std::string norm_buf(int l, bool cross) const { return "b" + std::to_string(l) + (cross ? ".n1" : ".n2"); }
-  std::string norm_rstd(int l, bool cross) const { return "b" + std::to_string(l) + (cross ? ".r1" : ".r2"); }
-  // the rows the key/value projections of input function i read (and their weight gradients)
-  std::string fn_rows(int i) const { return (pre_norm ? "fnn" : "fnenc") + std::to_string(i); }
   // keyed dropout on the attention outputs (gnot_plan_set_dropout, dropout.hip): "b{l}.a" / "b{l}.bb" right
   // after fc_out in the forward, the rows' gradient ("dsum0" / "dsum1") right before fc_out's backward.
   // drop_T = 0: off, no launch and no table
@@ -173,8 +203,6 @@ struct gnot_plan {
   // images
   std::vector<Img> fwd_img, T_img;      // per canonical linear (fwd_img unused for attention q/k/v)
   std::vector<size_t> fwd_bias;         // per canonical linear: offset of padded bias (floats) in pbias
-  struct AttnImgs { Img qkv, q, o; std::vector<Img> kv; size_t bqkv = 0, bq = 0, bo = 0; std::vector<size_t> bkv; };
-  std::vector<AttnImgs> cross_img, self_img;
 
   // grads
   std::vector<long> grad_off;           // 2 per linear
@@ -187,6 +215,10 @@ struct gnot_plan {
   Chain& ch_fn(int i) { return chains[2 + i]; }
   Chain& ch_moe(int l, bool m1) { return chains[2 + I + 2 * l + (m1 ? 0 : 1)]; }
   Chain& ch_out() { return chains.back(); }
+  // the attention calls in build_attn_calls' order: (cross, self) per block
+  std::vector<AttnCall> attn;
+  AttnCall& call(int l, bool cross) { return attn[2 * l + (cross ? 0 : 1)]; }
+  const AttnCall& call(int l, bool cross) const { return attn[2 * l + (cross ? 0 : 1)]; }
   long per_state() const { return (long)H * (dh * dh + dh); }   // floats of one sample's attention state (S, z)
   long Qmax() const { return Q.empty() ? 0 : *std::max_element(Q.begin(), Q.end()); }
 
@@ -195,10 +227,8 @@ struct gnot_plan {
   std::vector<int> qchunk_off;
   std::vector<std::vector<int4>> fchunks;
   std::vector<std::vector<int>> fchunk_off;
-  std::vector<WgradGroup> wg_self, wg_cross;
-  // attention states as point-reduction GEMM jobs (one job per sample)
-  std::vector<std::vector<WgradGroup>> st_c, dst_c;   // [l][source i]
-  // cross attention with input functions: the input-function side of EVERY block is batched
+  // cross attention with input functions: the input-function side of EVERY block is batched (built by walking
+  // the cross calls' sources)
   WgradGroup st_fn;                                    // forward states of all (block, fn, sample)
   WgradGroup wg_fnkv;                                  // weight grads of all key/value projections
   std::vector<LinearArgs> fwd_kv_jobs;                 // key/value projections of all (block, fn)
@@ -207,7 +237,6 @@ struct gnot_plan {
   LinearArgs* d_fwd_kv_jobs = nullptr;
   AttnKVBwdArgs* d_kvbwd_jobs = nullptr;
   std::vector<LinearArgs*> d_dfn_jobs;
-  std::vector<WgradGroup> st_s, dst_s;                 // [l]
   size_t table_bytes = 0;
   size_t slab_wgrad_floats = 0, slab_state_floats = 0;
 
@@ -239,9 +268,7 @@ struct gnot_plan {
   bool moe_direct_out() const { return !tune.moe_stored && D == 256 && npk() == 3; }
   bool moe_direct_dz() const { return moe_direct_out() && serial_wgrad(); }
   // The kernel form of every attention pass, chosen by choose_attn_forms from the batch geometry and `tune`
-  // (attn_kernel, gnot_kernels.h).  [0] self attention (one set of states), [1] cross attention (the states of
-  // the I input functions; without input functions one set, the form of [0])
-  AttnKernel apply_fwd[2] = {}, apply_bwd[2] = {};
+  // (attn_kernel, gnot_kernels.h); the apply passes' forms are the calls' (AttnCall::apply_fwd / apply_bwd)
   AttnKernel kv_bwd = {}, kv_bwd_batch = {};   // the query points' K/V backward; all (block, input function) jobs
   int kv_batch_maxchunks = 0;                   // the largest chunk count among the batched jobs
   std::vector<hipEvent_t> evs;
@@ -347,16 +374,10 @@ struct gnot_plan {
   int lin_fn(int i, int j) const { return 2 * NL + i * NL + j; }
   int blk0() const { return 2 * NL + I * NL; }
   int per_block() const { return 6 + 2 * KI + 2 * E * NL; }
-  int lin_cq(int l) const { return blk0() + l * per_block(); }
-  int lin_co(int l) const { return lin_cq(l) + 1; }
-  int lin_ck(int l, int i) const { return lin_cq(l) + 2 + i; }
-  int lin_cv(int l, int i) const { return lin_cq(l) + 2 + KI + i; }
-  int lin_sq(int l) const { return lin_cq(l) + 2 + 2 * KI; }
-  int lin_so(int l) const { return lin_sq(l) + 1; }
-  int lin_sk(int l) const { return lin_sq(l) + 2; }
-  int lin_sv(int l) const { return lin_sq(l) + 3; }
-  int lin_f1(int l, int e, int j) const { return lin_sq(l) + 4 + e * NL + j; }
-  int lin_f2(int l, int e, int j) const { return lin_sq(l) + 4 + E * NL + e * NL + j; }
+  // block l: cross q, fc_out, KI keys, KI values; self q, fc_out, key, value (build_attn_calls); ffn1, ffn2 experts
+  int blk(int l) const { return blk0() + l * per_block(); }
+  int lin_f1(int l, int e, int j) const { return blk(l) + 6 + 2 * KI + e * NL + j; }
+  int lin_f2(int l, int e, int j) const { return lin_f1(l, E, 0) + e * NL + j; }
   int lin_out(int j) const { return blk0() + L * per_block() + j; }
   int n_lin() const { return lin_out(NL - 1) + 1; }
   // gnot_plan_set_trainable: one byte per canonical Linear; empty: all trainable.  A frozen Linear has no
@@ -388,12 +409,8 @@ struct gnot_plan {
   int k_fn(int i) const { return 1 + 2 * L + i; }
   int k_x() const { return 1 + 2 * L + I; }
   int k_gate() const { return 2 + 2 * L + I; }
-  std::string dsum_buf(bool m1) const { return m1 ? "dsum1" : "dsum0"; }
   // input-function encoder chains run on side2 with their own dZ buffer; the others alternate dz0/dz1
   std::string dz_name(int kcall) const { return (kcall >= k_fn(0) && kcall < k_fn(0) + I) ? "dzf" : dz_buf(kcall); }
-  std::string dqkv_buf(bool cross) const { return cross ? "dqkv1" : "dqkv0"; }
-  std::string dkv_buf(int l, int i) const { return "dkv" + std::to_string(l) + "_" + std::to_string(i); }
-  std::string dstate_fn(int l, int i) const { return "dstate" + std::to_string(l) + "_" + std::to_string(i); }
   // a named buffer's address (+ an element offset); null until the workspace is bound
   float* P_(const std::string& name, long off = 0) const { return at(bufs.at(name).p, off); }
 };
@@ -590,6 +607,46 @@ static void build_chains(gnot_plan* p) {
   add({p->lin_out(0)}, D, p->out, p->k_out(), p->P, p->final_query(), "out_save", CH_STORE);
 }
 
+// the attention calls of the current batch, in the one order gnot_plan::call(l, cross) indexes.  A cross call with
+// input functions projects q alone and reads one source per input function, whose K | V rows, states and
+// backward run batched over all blocks; every other call (self, and a cross module without input functions)
+// is fused: one q|k|v projection of its own rows, one source
+static void build_attn_calls(gnot_plan* p) {
+  p->attn.clear();
+  for (int l = 0; l < p->L; ++l)
+    for (bool cross : {true, false}) {
+      const std::string b = "b" + std::to_string(l) + ".", s = b + (cross ? "c" : "s");
+      AttnCall a;
+      a.l = l; a.cross = cross; a.site = (uint32_t)(2 * l + (cross ? 0 : 1));
+      a.fused = !(cross && p->I > 0);
+      a.nsrc = a.fused ? 1 : p->I;
+      // canonical Linears of block l: cross q, fc_out, KI keys, KI values, then self q, fc_out, key, value
+      const int nkv = cross ? p->KI : 1;
+      a.q = p->blk(l) + (cross ? 0 : 2 + 2 * p->KI);
+      a.o = a.q + 1;
+      for (int i = 0; i < nkv; ++i) { a.k.push_back(a.q + 2 + i); a.v.push_back(a.q + 2 + nkv + i); }
+      a.in_raw = cross ? p->block_query(l) : b + "query1";
+      a.in = p->pre_norm ? b + (cross ? "n1" : "n2") : a.in_raw;
+      a.rstd = b + (cross ? "r1" : "r2");
+      a.proj = s + "q"; a.pitch = (a.fused ? 3 : 1) * (long)p->D;
+      a.res = s + "res"; a.out = b + (cross ? "a" : "bb");
+      a.dsum = cross ? "dsum1" : "dsum0"; a.dqkv = cross ? "dqkv1" : "dqkv0";
+      for (int i = 0; i < a.nsrc; ++i) {
+        const std::string si = std::to_string(i), li = std::to_string(l) + "_" + si;
+        AttnSrc r;
+        r.state = s + "state" + (cross ? si : "");
+        r.du = "du" + si; r.dden = "dden" + si;
+        r.dstate = "dstate0";
+        if (!a.fused) {                      // its dS | dz and dK | dV are kept per (block, source) for the batched side
+          r.fn = i; r.ckv = s + "kv" + si; r.enc = (p->pre_norm ? "fnn" : "fnenc") + si;
+          r.dstate = "dstate" + li; r.dkv = "dkv" + li;
+        }
+        a.src.push_back(std::move(r));
+      }
+      p->attn.push_back(std::move(a));
+    }
+}
+
 // build the packed-weight images and pack jobs (offsets relative to the packed arena)
 static void plan_images(gnot_plan* p) {
   const int DT = p->DT, NL = p->NL;
@@ -678,61 +735,47 @@ static void plan_images(gnot_plan* p) {
   chain_imgs(p->ch_x(), 0);
   chain_imgs(p->ch_gate(), 0);
   for (int i = 0; i < p->I; ++i) chain_imgs(p->ch_fn(i), 0);
-  p->cross_img.assign(p->L, gnot_plan::AttnImgs());
-  p->self_img.assign(p->L, gnot_plan::AttnImgs());
   // attention projections: at d = 256 the q | q|k|v | fc_out images and the backward-data images that
   // linear2.hip uses are output-major bf16x6; the input-function K/V images and their backward-data
   // images stay fp32 for the batched linear.hip kernel
-  auto attn_imgs = [&](gnot_plan::AttnImgs& A, int iq, int io, const std::vector<int>& ik,
-                       const std::vector<int>& iv, bool selftype) {
+  auto attn_imgs = [&](AttnCall& A) {
     const int D = p->D;
     const bool lx6 = p->lin_img() == 3;   // fp32 mode at d <= 192: output-major x6
     const int x6 = c2 ? c2x6 : b1 ? 3 : lx6 ? 2 : 0;
     auto img = [&](int OT, int KT) {
       return c2 ? new_img_x6(OT, KT, c2np) : b1 ? new_img_x6(OT, KT, 1) : lx6 ? new_img_x6(OT, KT, 3) : new_img(OT, KT);
     };
-    if (selftype) {
-      A.qkv = img(3 * DT, DT);
-      A.bqkv = new_bias(3 * D);
-      job(iq, A.qkv, 0, 0, DT, DT, 0, (long)A.bqkv, x6, true);
-      job(ik[0], A.qkv, DT, 0, DT, DT, 0, (long)(A.bqkv + D), x6, true);
-      job(iv[0], A.qkv, 2 * DT, 0, DT, DT, 0, (long)(A.bqkv + 2 * D), x6, true);
-    } else {
-      A.q = img(DT, DT);
-      A.bq = new_bias(D);
-      job(iq, A.q, 0, 0, DT, DT, 0, (long)A.bq, x6, true);
-      for (size_t i = 0; i < ik.size(); ++i) {
-        Img kv = new_img(2 * DT, DT);
-        const size_t bkv = new_bias(2 * D);
-        job(ik[i], kv, 0, 0, DT, DT, 0, (long)bkv, 0, true);
-        job(iv[i], kv, DT, 0, DT, DT, 0, (long)(bkv + D), 0, true);
-        A.kv.push_back(kv);
-        A.bkv.push_back(bkv);
-      }
+    A.proj_img = img((int)(A.pitch / 16), DT);
+    A.bproj = new_bias((int)A.pitch);
+    job(A.q, A.proj_img, 0, 0, DT, DT, 0, (long)A.bproj, x6, true);
+    if (A.fused) {
+      job(A.k[0], A.proj_img, DT, 0, DT, DT, 0, (long)(A.bproj + D), x6, true);
+      job(A.v[0], A.proj_img, 2 * DT, 0, DT, DT, 0, (long)(A.bproj + 2 * D), x6, true);
     }
-    A.o = img(DT, DT);
+    for (int i = 0; i < (A.fused ? 0 : A.nsrc); ++i) {   // K | V of the input-function sources: batched fp32 kernel
+      Img kv = new_img(2 * DT, DT);
+      const size_t bkv = new_bias(2 * D);
+      job(A.k[i], kv, 0, 0, DT, DT, 0, (long)bkv, 0, true);
+      job(A.v[i], kv, DT, 0, DT, DT, 0, (long)(bkv + D), 0, true);
+      A.kv_img.push_back(kv);
+      A.bkv.push_back(bkv);
+    }
+    A.o_img = img(DT, DT);
     A.bo = new_bias(D);
-    job(io, A.o, 0, 0, DT, DT, 0, (long)A.bo, x6);
-    std::vector<int> mine = {iq, io};
-    if (selftype) { mine.push_back(ik[0]); mine.push_back(iv[0]); }
-    for (int li : mine) {
-      Img t = img(DT, DT);
-      job(li, t, 0, 0, DT, DT, 1, -1, x6, li != io);
+    job(A.o, A.o_img, 0, 0, DT, DT, 0, (long)A.bo, x6);
+    // backward-data images: q, fc_out, then the keys / values (input-function ones: the batched fp32 kernel's)
+    auto t_img = [&](int li, bool own, bool heads) {
+      Img t = own ? img(DT, DT) : new_img(DT, DT);
+      job(li, t, 0, 0, DT, DT, 1, -1, own ? x6 : 0, heads);
       p->T_img[li] = t;
-    }
-    if (!selftype)                          // input-function keys/values: batched fp32 kernel
-      for (size_t i = 0; i < ik.size(); ++i)
-        for (int li : {ik[i], iv[i]}) {
-          Img t = new_img(DT, DT);
-          job(li, t, 0, 0, DT, DT, 1, -1, 0, true);
-          p->T_img[li] = t;
-        }
+    };
+    t_img(A.q, true, true);
+    t_img(A.o, true, false);
+    for (size_t i = 0; i < A.k.size(); ++i) { t_img(A.k[i], A.fused, true); t_img(A.v[i], A.fused, true); }
   };
   for (int l = 0; l < p->L; ++l) {
-    std::vector<int> ck, cv;
-    for (int i = 0; i < p->KI; ++i) { ck.push_back(p->lin_ck(l, i)); cv.push_back(p->lin_cv(l, i)); }
-    attn_imgs(p->cross_img[l], p->lin_cq(l), p->lin_co(l), ck, cv, p->I == 0);
-    attn_imgs(p->self_img[l], p->lin_sq(l), p->lin_so(l), {p->lin_sk(l)}, {p->lin_sv(l)}, true);
+    attn_imgs(p->call(l, true));
+    attn_imgs(p->call(l, false));
     for (int e = 0; e < p->E; ++e) {
       chain_imgs(p->ch_moe(l, true), e);
       chain_imgs(p->ch_moe(l, false), e);
@@ -906,18 +949,14 @@ template <typename F>
 static void for_each_group(gnot_plan* p, F&& f) {
   if (p->training) {
     for (Chain& C : p->chains) f(C.wg);
-    for (int l = 0; l < p->L; ++l) { f(p->wg_self[l]); f(p->wg_cross[l]); }
+    for (int l = 0; l < p->L; ++l) { f(p->call(l, false).wg); f(p->call(l, true).wg); }
     f(p->wg_fnkv);
   }
   f(p->st_fn);
-  for (int l = 0; l < p->L; ++l) {
-    for (auto& G : p->st_c[l]) f(G);
-    f(p->st_s[l]);
-    if (p->training) {
-      for (auto& G : p->dst_c[l]) f(G);
-      f(p->dst_s[l]);
-    }
-  }
+  for (int l = 0; l < p->L; ++l)             // per block: the forward states of both calls, then the backward's
+    for (int bwd = 0; bwd <= (p->training ? 1 : 0); ++bwd)
+      for (bool cross : {true, false})
+        for (AttnSrc& r : p->call(l, cross).src) f(bwd ? r.dst : r.st);
 }
 
 // (Re)build every job list from the current buffer pointers.  Before bind every buffer is null and so is every
@@ -926,16 +965,17 @@ static void build_groups(gnot_plan* p) {
   p->slab_wgrad_floats = 0;
   p->slab_state_floats = 0;
   const long P = p->P;
-  const int D = p->D, NL = p->NL, I = p->I, KI = p->KI, dh = p->dh;
+  const int D = p->D, NL = p->NL, dh = p->dh;
   const bool tr = p->training;
   const long per_state = p->per_state();
   float* const grads = p->grads();
   for (Chain& C : p->chains) C.wg = {};
-  p->wg_self.assign(p->L, {}); p->wg_cross.assign(p->L, {});
   p->wg_fnkv = {};
-  p->st_c.assign(p->L, std::vector<WgradGroup>(KI));
-  p->dst_c.assign(p->L, std::vector<WgradGroup>(KI));
-  p->st_s.assign(p->L, {}); p->dst_s.assign(p->L, {});
+  p->st_fn = {};
+  for (AttnCall& a : p->attn) {
+    a.wg = {};
+    for (AttnSrc& r : a.src) r.st = r.dst = {};
+  }
 
   auto lin_job = [&](WgradGroup& G, int li, const float* dz, long lddz, const float* x, long ldx, int gelu,
                      long rows) {
@@ -1025,87 +1065,51 @@ static void build_groups(gnot_plan* p) {
     finish_state_group(p, G);
   };
 
-  for (int l = 0; l < p->L; ++l) {
-    const std::string s = "b" + std::to_string(l) + ".";
-    // forward states (with input functions, all blocks' cross states are one group: st_fn, below)
-    if (I == 0)
-      state_group(p->st_c[l][0], p->P_(s + "cq", D), 3 * D, p->P_(s + "cq", 2 * D), 3 * D, nullptr, 0, p->xoff,
-                  p->P_(s + "cstate0"));
-    state_group(p->st_s[l], p->P_(s + "sq", D), 3 * D, p->P_(s + "sq", 2 * D), 3 * D, nullptr, 0, p->xoff,
-                p->P_(s + "sstate"));
-    if (!tr) continue;
+  for (AttnCall& a : p->attn) {
+    // a fused call's forward states S = k^T v, z = sum k (the input-function sources of all blocks: st_fn, below)
+    if (a.fused)
+      state_group(a.src[0].st, p->P_(a.proj, D), a.pitch, p->P_(a.proj, 2 * D), a.pitch, nullptr, 0, p->xoff,
+                  p->P_(a.src[0].state));
     // backward states dS = sum q^T du, dz = sum dden q
-    for (int i = 0; i < KI; ++i) {
-      const std::string si = std::to_string(i);
-      const long ldq = I > 0 ? D : 3 * D;
-      state_group(p->dst_c[l][i], p->P_(s + "cq"), ldq, p->P_("du" + si), D, p->P_("dden" + si), p->H, p->xoff,
-                  p->P_(I > 0 ? p->dstate_fn(l, i) : std::string("dstate0")));
+    for (AttnSrc& r : a.src)
+      if (tr) state_group(r.dst, p->P_(a.proj), a.pitch, p->P_(r.du), D, p->P_(r.dden), p->H, p->xoff, p->P_(r.dstate));
+  }
+  // the batched input-function side, walking the unfused calls' sources in (block, fn) order
+  for (AttnCall& a : p->attn)
+    for (int i = 0; i < (a.fused ? 0 : a.nsrc); ++i) {
+      const AttnSrc& r = a.src[i];
+      // one state job per sample: S = k^T v, z = sum k over that sample's input-function points
+      float* kv = p->P_(r.ckv);
+      float* st = p->P_(r.state);
+      for (int b = 0; b < p->B; ++b) {
+        WgradJob J{};
+        const long o = p->fnoff[r.fn][b];
+        J.dz = at(kv, o * 2 * D); J.lddz = 2 * D; J.x = at(kv, D + o * 2 * D); J.ldx = 2 * D;
+        J.out = p->hd(); J.in = p->hd(); J.dW = at(st, b * per_state); J.db = J.dW;
+        J.state_dh = dh; J.P = (int)(p->fnoff[r.fn][b + 1] - o);
+        p->st_fn.jobs.push_back(J);
+      }
+      if (!tr) continue;
+      lin_job_heads(p->wg_fnkv, a.k[i], p->P_(r.dkv), 2 * D, p->P_(r.enc), D, p->Q[r.fn]);
+      lin_job_heads(p->wg_fnkv, a.v[i], p->P_(r.dkv, D), 2 * D, p->P_(r.enc), D, p->Q[r.fn]);
     }
-    state_group(p->dst_s[l], p->P_(s + "sq"), 3 * D, p->P_("du0"), D, p->P_("dden0"), p->H, p->xoff,
-                p->P_("dstate0"));
-  }
-  p->st_fn = {};
-  if (I > 0) {
-    // one job per (block, fn, sample): S = k^T v, z = sum k over that sample's input-function points
-    for (int l = 0; l < p->L; ++l)
-      for (int i = 0; i < I; ++i) {
-        const std::string s = "b" + std::to_string(l) + ".", si = std::to_string(i);
-        float* kv = p->P_(s + "ckv" + si);
-        float* st = p->P_(s + "cstate" + si);
-        for (int b = 0; b < p->B; ++b) {
-          WgradJob J{};
-          const long o = p->fnoff[i][b];
-          J.dz = at(kv, o * 2 * D); J.lddz = 2 * D; J.x = at(kv, D + o * 2 * D); J.ldx = 2 * D;
-          J.out = p->hd(); J.in = p->hd(); J.dW = at(st, b * per_state); J.db = J.dW;
-          J.state_dh = dh; J.P = (int)(p->fnoff[i][b + 1] - o);
-          p->st_fn.jobs.push_back(J);
-        }
-      }
-    finish_state_group(p, p->st_fn);
-  }
+  if (p->I > 0) finish_state_group(p, p->st_fn);
   if (!tr) return;
-
-  if (I > 0) {
-    for (int l = 0; l < p->L; ++l)
-      for (int i = 0; i < I; ++i) {
-        const std::string dkv = p->dkv_buf(l, i);
-        const float* enc = p->P_(p->fn_rows(i));
-        lin_job_heads(p->wg_fnkv, p->lin_ck(l, i), p->P_(dkv), 2 * D, enc, D, p->Q[i]);
-        lin_job_heads(p->wg_fnkv, p->lin_cv(l, i), p->P_(dkv, D), 2 * D, enc, D, p->Q[i]);
-      }
-    finish_group(p, p->wg_fnkv);
-  }
+  if (p->I > 0) finish_group(p, p->wg_fnkv);
 
   for (Chain& C : p->chains) {
     if (C.mode == CH_MOE && p->b16s()) moe_group_b16(C);
     else chain_group(C);
   }
-  for (int l = 0; l < p->L; ++l) {
-    const std::string s = "b" + std::to_string(l) + ".";
-    {
-      const std::string dqkv = p->dqkv_buf(false);
-      WgradGroup& G = p->wg_self[l];
-      const float* q1 = p->P_(p->pre_norm ? p->norm_buf(l, false) : s + "query1");
-      lin_job(G, p->lin_so(l), p->P_(p->dsum_buf(false)), D, p->P_(s + "sres"), p->Dr, 0, P);
-      lin_job_heads(G, p->lin_sq(l), p->P_(dqkv), 3 * D, q1, D, P);
-      lin_job_heads(G, p->lin_sk(l), p->P_(dqkv, D), 3 * D, q1, D, P);
-      lin_job_heads(G, p->lin_sv(l), p->P_(dqkv, 2 * D), 3 * D, q1, D, P);
-      finish_group(p, G);
+  for (AttnCall& a : p->attn) {
+    const float* in = p->P_(a.in);
+    lin_job(a.wg, a.o, p->P_(a.dsum), D, p->P_(a.res), p->Dr, 0, P);
+    lin_job_heads(a.wg, a.q, p->P_(a.dqkv), a.pitch, in, D, P);
+    if (a.fused) {                                 // (an unfused call's key / value gradients: wg_fnkv)
+      lin_job_heads(a.wg, a.k[0], p->P_(a.dqkv, D), a.pitch, in, D, P);
+      lin_job_heads(a.wg, a.v[0], p->P_(a.dqkv, 2 * D), a.pitch, in, D, P);
     }
-    {
-      const std::string dqkv = p->dqkv_buf(true);
-      WgradGroup& G = p->wg_cross[l];
-      const float* qin = p->P_(p->pre_norm ? p->norm_buf(l, true) : p->block_query(l));
-      lin_job(G, p->lin_co(l), p->P_(p->dsum_buf(true)), D, p->P_(s + "cres"), p->Dr, 0, P);
-      if (I > 0) {
-        lin_job_heads(G, p->lin_cq(l), p->P_(dqkv), D, qin, D, P);   // key/value grads: wg_fnkv
-      } else {
-        lin_job_heads(G, p->lin_cq(l), p->P_(dqkv), 3 * D, qin, D, P);
-        lin_job_heads(G, p->lin_ck(l, 0), p->P_(dqkv, D), 3 * D, qin, D, P);
-        lin_job_heads(G, p->lin_cv(l, 0), p->P_(dqkv, 2 * D), 3 * D, qin, D, P);
-      }
-      finish_group(p, G);
-    }
+    finish_group(p, a.wg);
   }
 }
 
@@ -1129,21 +1133,21 @@ static void ksplit_job(const gnot_plan* p, LinearArgs& a) {
 // The kernel form of every attention pass of this batch geometry: a function of the shapes and p->tune alone,
 // so set_batch decides once and every launch obeys.  Every pitch the passes use (attn_forward, attn_backward,
 // build_attn_tables) is D, 2 D or 3 D floats, D a multiple of 16
+static AttnKernel attn_form(const gnot_plan* p, AttnPass pass, int nsrc, long nchunks) {
+  return attn_kernel(pass, p->dh, p->dhr, p->H, nsrc, nchunks, true, p->tune.apply_mfma_min_chunks);
+}
+static AttnKernel apply_form(const gnot_plan* p, AttnPass pass, int nsrc) {   // a pass over the query points
+  return attn_form(p, pass, nsrc, (long)p->qchunks.size());
+}
 static void choose_attn_forms(gnot_plan* p) {
-  const int minch = p->tune.apply_mfma_min_chunks;
-  const long nq = (long)p->qchunks.size();
-  auto form = [&](AttnPass pass, int nsrc, long nchunks) {
-    return attn_kernel(pass, p->dh, p->dhr, p->H, nsrc, nchunks, true, minch);
-  };
-  for (int cross = 0; cross < 2; ++cross) {
-    const int nsrc = cross ? p->KI : 1;
-    p->apply_fwd[cross] = form(AttnPass::ApplyFwd, nsrc, nq);
-    p->apply_bwd[cross] = form(AttnPass::ApplyBwd, nsrc, nq);
+  for (AttnCall& a : p->attn) {
+    a.apply_fwd = apply_form(p, AttnPass::ApplyFwd, a.nsrc);
+    a.apply_bwd = apply_form(p, AttnPass::ApplyBwd, a.nsrc);
   }
-  p->kv_bwd = form(AttnPass::KVBwd, 1, nq);
+  p->kv_bwd = apply_form(p, AttnPass::KVBwd, 1);
   p->kv_batch_maxchunks = 0;
   for (int i = 0; i < p->I; ++i) p->kv_batch_maxchunks = std::max(p->kv_batch_maxchunks, (int)p->fchunks[i].size());
-  p->kv_bwd_batch = form(AttnPass::KVBwd, 1, (long)p->kv_batch_maxchunks * p->L * p->I);
+  p->kv_bwd_batch = attn_form(p, AttnPass::KVBwd, 1, (long)p->kv_batch_maxchunks * p->L * p->I);
 }
 
 // Device job tables of the batched input-function side of cross attention (pointers are null
@@ -1156,11 +1160,11 @@ static void build_attn_tables(gnot_plan* p) {
   if (I == 0 || L == 0) return;
   for (int l = 0; l < L; ++l)
     for (int i = 0; i < I; ++i) {
-      const std::string s = "b" + std::to_string(l) + ".", si = std::to_string(i);
-      const gnot_plan::AttnImgs& A = p->cross_img[l];
+      const AttnCall& A = p->call(l, true);
+      const AttnSrc& r = A.src[i];
       LinearArgs a{};
-      a.nseg = 1; a.X[0] = p->P_(p->fn_rows(i)); a.ldx = D; a.Wp[0] = A.kv[i].p; a.nsum = 1; a.K = D;
-      a.bias = p->P_("pbias", A.bkv[i]); a.Y = p->P_(s + "ckv" + si); a.ldy = 2 * D; a.NO = 2 * D; a.P = (int)p->Q[i];
+      a.nseg = 1; a.X[0] = p->P_(r.enc); a.ldx = D; a.Wp[0] = A.kv_img[i].p; a.nsum = 1; a.K = D;
+      a.bias = p->P_("pbias", A.bkv[i]); a.Y = p->P_(r.ckv); a.ldy = 2 * D; a.NO = 2 * D; a.P = (int)p->Q[i];
       a.epi = EPI_STORE; a.nsoft = D; a.dh = p->dh; a.dreal = p->attn_dreal();
       a.dhr = p->head_padded() ? p->dhr : 0;
       ksplit_job(p, a);
@@ -1169,11 +1173,11 @@ static void build_attn_tables(gnot_plan* p) {
   if (!p->training) return;
   for (int l = 0; l < L; ++l)
     for (int i = 0; i < I; ++i) {
-      const std::string s = "b" + std::to_string(l) + ".";
-      const float* kv = p->P_(s + "ckv" + std::to_string(i));
-      float* dkv = p->P_(p->dkv_buf(l, i));
+      const AttnSrc& r = p->call(l, true).src[i];
+      const float* kv = p->P_(r.ckv);
+      float* dkv = p->P_(r.dkv);
       AttnKVBwdArgs kb{};
-      kb.k = kv; kb.v = at(kv, D); kb.ldkv = 2 * D; kb.dstate = p->P_(p->dstate_fn(l, i));
+      kb.k = kv; kb.v = at(kv, D); kb.ldkv = 2 * D; kb.dstate = p->P_(r.dstate);
       kb.chunks = p->d_fchunks[i];               // (walk_tables places the chunk tables before these jobs)
       kb.nchunks = (int)p->fchunks[i].size(); kb.H = p->H; kb.dh = p->dh;
       kb.dk = dkv; kb.dv = at(dkv, D); kb.lddkv = 2 * D;
@@ -1190,8 +1194,9 @@ static void build_attn_tables(gnot_plan* p) {
       a.nseg = std::min(per, nseg - k0);
       for (int sg = 0; sg < a.nseg; ++sg) {
         const int l = (k0 + sg) / 2, kv = (k0 + sg) % 2;
-        a.X[sg] = p->P_(p->dkv_buf(l, i), kv * D);
-        a.Wp[sg] = p->T_img[kv ? p->lin_cv(l, i) : p->lin_ck(l, i)].p;
+        const AttnCall& A = p->call(l, true);
+        a.X[sg] = p->P_(A.src[i].dkv, kv * D);
+        a.Wp[sg] = p->T_img[kv ? A.v[i] : A.k[i]].p;
       }
       a.ldx = 2 * D; a.nsum = 1; a.K = D; a.bias = nullptr; a.Y = p->P_("dfn" + std::to_string(i)); a.ldy = D;
       a.NO = D; a.P = (int)p->Q[i]; a.epi = k0 == 0 ? EPI_STORE : EPI_ACCUM; a.nsoft = 0; a.dh = p->dh;
@@ -1254,11 +1259,10 @@ static void walk_tables(gnot_plan* p, TableWalk& w) {
     auto rimg = [&](Img& im) { im.p = packed + im.off4; };
     for (auto& im : p->fwd_img) rimg(im);
     for (auto& im : p->T_img) rimg(im);
-    for (auto* v : {&p->cross_img, &p->self_img})
-      for (auto& A : *v) {
-        rimg(A.qkv); rimg(A.q); rimg(A.o);
-        for (auto& k : A.kv) rimg(k);
-      }
+    for (AttnCall& A : p->attn) {
+      rimg(A.proj_img); rimg(A.o_img);
+      for (auto& k : A.kv_img) rimg(k);
+    }
     for (Chain& C : p->chains) {
       C.layers.clear();
       for (int f : C.firsts)
@@ -1566,7 +1570,7 @@ extern "C" int gnot_debug_backward_plan(const gnot_plan* p, int* wgrad_jobs, int
   int jobs = 0;
   if (p->training) {
     for (const Chain& C : p->chains) jobs += (int)C.wg.jobs.size();
-    for (int l = 0; l < p->L; ++l) jobs += (int)(p->wg_self[l].jobs.size() + p->wg_cross[l].jobs.size());
+    for (const AttnCall& a : p->attn) jobs += (int)a.wg.jobs.size();
     jobs += (int)p->wg_fnkv.jobs.size();
   }
   *wgrad_jobs = jobs;
@@ -1631,6 +1635,7 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
 
   // ---------------- workspace carve
   build_chains(p);
+  build_attn_calls(p);
   plan_images(p);
   p->bufs.clear();
   p->buf_order.clear();
@@ -1638,6 +1643,15 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
   const long P = p->P, D = p->D, E = p->E, NL = p->NL, H = p->H;
   const long per_state = p->per_state(), Qmax = p->Qmax();
   const int I = p->I, KI = p->KI;
+  // a call's forward buffers, from its description: the names and pitches the launches use are the ones carved
+  auto carve_call = [&](const AttnCall& a) {
+    C.add(a.proj, P * a.pitch, a.pitch);
+    for (const AttnSrc& r : a.src)
+      if (r.fn >= 0) C.add(r.ckv, p->Q[r.fn] * 2 * D, 2 * D);
+    for (const AttnSrc& r : a.src) C.add(r.state, p->B * per_state, per_state);
+    C.add(a.res, P * D, p->Dr);        // scramble rows: Dr floats per token (attn_forward)
+    C.add(a.out, P * D, D);
+  };
   C.add("packed", p->packed4 * 4, 0);
   C.add("pbias", p->pbias, 0);
   // gradient arena
@@ -1671,21 +1685,10 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
   }
   for (int l = 0; l < p->L; ++l) {
     const std::string s = "b" + std::to_string(l) + ".";
-    if (I > 0) {
-      C.add(s + "cq", P * D, D);
-      for (int i = 0; i < I; ++i) C.add(s + "ckv" + std::to_string(i), p->Q[i] * 2 * D, 2 * D);
-    } else {
-      C.add(s + "cq", P * 3 * D, 3 * D);     // q | k | v of the cross module in self mode
-    }
-    for (int i = 0; i < KI; ++i) C.add(s + "cstate" + std::to_string(i), p->B * per_state, per_state);
-    C.add(s + "cres", P * D, p->Dr);   // scramble rows: Dr floats per token (attn_forward)
-    C.add(s + "a", P * D, D);
+    carve_call(p->call(l, true));
     if (tr && !p->moe_recompute) C.add(s + "m1save", E * NL * P * D, D);
     C.add(s + "query1", P * D, D);
-    C.add(s + "sq", P * 3 * D, 3 * D);
-    C.add(s + "sstate", p->B * per_state, per_state);
-    C.add(s + "sres", P * D, p->Dr);
-    C.add(s + "bb", P * D, D);
+    carve_call(p->call(l, false));
     if (tr && !p->moe_recompute) C.add(s + "m2save", E * NL * P * D, D);
     C.add(s + "query2", P * D, D);
   }
@@ -1703,11 +1706,10 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
     // the normalised attention inputs, kept per block (the q / k / v weight gradients read their Linear's
     // input) and once per input function (no parameters: the same rows for every block); training keeps
     // each row's rstd for the backward
-    for (int l = 0; l < p->L; ++l)
-      for (bool cross : {true, false}) {
-        C.add(p->norm_buf(l, cross), P * D, D);
-        if (tr) C.add(p->norm_rstd(l, cross), P, 1);
-      }
+    for (const AttnCall& a : p->attn) {
+      C.add(a.in, P * D, D);
+      if (tr) C.add(a.rstd, P, 1);
+    }
     for (int i = 0; i < I; ++i) {
       C.add("fnn" + std::to_string(i), p->Q[i] * D, D);
       if (tr) C.add("fnr" + std::to_string(i), p->Q[i], 1);
@@ -1733,11 +1735,12 @@ extern "C" int gnot_plan_set_batch(gnot_plan* p, int B, const int64_t* x_off, co
       C.add("dden" + std::to_string(i), P * H, H);
     }
     C.add("dstate0", p->B * per_state, per_state);
-    for (int l = 0; l < p->L; ++l)
-      for (int i = 0; i < I; ++i) {
-        C.add(p->dstate_fn(l, i), p->B * per_state, per_state);
-        C.add(p->dkv_buf(l, i), p->Q[i] * 2 * D, 2 * D);
-      }
+    for (const AttnCall& a : p->attn)                  // kept per (block, source) for the batched K/V backward
+      for (const AttnSrc& r : a.src)
+        if (r.fn >= 0) {
+          C.add(r.dstate, p->B * per_state, per_state);
+          C.add(r.dkv, p->Q[r.fn] * 2 * D, 2 * D);
+        }
     for (int i = 0; i < I; ++i) {
       C.add("dfn" + std::to_string(i), p->Q[i] * D, D);
     }
@@ -2153,118 +2156,103 @@ AttnApplyArgs apply_args(const gnot_plan* p) {
 }
 
 // keyed dropout of one attention call's output rows (forward) or of their gradient (backward), in place on
-// this stream; site 2 l: block l's cross attention, 2 l + 1: its self attention.  Only when the last forward
-// dropped (gnot_plan_set_dropout + gnot_plan_set_dropout_active)
-int drop_rows(Ctx& c, float* rows, int l, bool cross) {
+// this stream, keyed on the call's site.  Only when the last forward dropped (gnot_plan_set_dropout +
+// gnot_plan_set_dropout_active)
+int drop_rows(Ctx& c, float* rows, const AttnCall& a) {
   gnot_plan* p = c.p;
   if (!p->drop_fwd) return GNOT_OK;
-  GNOT_CK(launch_dropout_rows(rows, p->D, p->P, p->Dr, p->d_xoff, p->d_glo, p->B, p->drop_key,
-                              (uint32_t)(2 * l + (cross ? 0 : 1)), p->drop_T, p->drop_scale, c.s));
+  GNOT_CK(launch_dropout_rows(rows, p->D, p->P, p->Dr, p->d_xoff, p->d_glo, p->B, p->drop_key, a.site, p->drop_T,
+                              p->drop_scale, c.s));
   return GNOT_OK;
 }
 
-// one LinearAttention call (model.py:53-107). q_in: the query rows [P, D].
-int attn_forward(Ctx& c, int l, bool cross, const float* q_in, float* res_out, float* out) {
+// the q, S | z (and, in the backward, du, dden) operands of call a's apply passes
+AttnApplyArgs call_apply_args(const gnot_plan* p, const AttnCall& a, bool bwd) {
+  AttnApplyArgs ap = apply_args(p);
+  ap.q = p->P_(a.proj); ap.ldq = a.pitch; ap.nsrc = a.nsrc;
+  for (int i = 0; i < a.nsrc; ++i) {
+    ap.state[i] = p->P_(a.src[i].state);
+    if (bwd) { ap.du[i] = p->P_(a.src[i].du); ap.dden[i] = p->P_(a.src[i].dden); }
+  }
+  return ap;
+}
+
+// one LinearAttention call (model.py:53-107): a.in [P, D] -> a.out, the scramble rows kept in a.res
+int attn_forward(Ctx& c, const AttnCall& a) {
   gnot_plan* p = c.p;
   const long P = p->P;
   const int D = p->D;
-  const std::string s = "b" + std::to_string(l) + ".";
-  const gnot_plan::AttnImgs& A = cross ? p->cross_img[l] : p->self_img[l];
+  const float* q_in = p->P_(a.in);
+  float* res_out = p->P_(a.res);
+  float* out = p->P_(a.out);
   float* pbias = p->P_("pbias");
-  AttnApplyArgs ap = apply_args(p);
+  AttnApplyArgs ap = call_apply_args(p, a, false);
   ap.res = p->sharded ? p->P_("xb") : res_out;
-  if (cross && p->I > 0) {
-    float* q = p->P_(s + "cq");
-    GNOT_RUN(run_linear(c, q_in, D, D, A.q, pbias + A.bq, q, D, D, P, EPI_STORE, D));
-    // keys/values/states of the input functions were computed for every block up front
-    for (int i = 0; i < p->I; ++i) ap.state[i] = p->P_(s + "cstate" + std::to_string(i));
-    ap.q = q; ap.ldq = D; ap.nsrc = p->I;
-  } else {
-    float* qkv = p->P_(cross ? s + "cq" : s + "sq");
-    GNOT_RUN(run_linear(c, q_in, D, D, A.qkv, pbias + A.bqkv, qkv, 3 * D, 3 * D, P, EPI_STORE, 2 * D));
-    float* st = p->P_(cross ? s + "cstate0" : s + "sstate");
-    GNOT_RUN(run_state(c, cross ? p->st_c[l][0] : p->st_s[l]));
-    GNOT_RUN(shard_allreduce(c, st, p->B * p->per_state()));   // S, z over all ranks
-    ap.q = qkv; ap.ldq = 3 * D; ap.nsrc = 1; ap.state[0] = st;
+  // q, or q | k | v (feature softmax over q and k); an unfused call's keys / values / states were computed for
+  // every block up front
+  GNOT_RUN(run_linear(c, q_in, D, D, a.proj_img, pbias + a.bproj, p->P_(a.proj), a.pitch, (int)a.pitch, P, EPI_STORE,
+                      a.fused ? 2 * D : D));
+  if (a.fused) {
+    GNOT_RUN(run_state(c, a.src[0].st));
+    GNOT_RUN(shard_allreduce(c, p->P_(a.src[0].state), p->B * p->per_state()));   // S, z over all ranks
   }
-  GNOT_CK(launch_attn_apply(p->apply_fwd[cross], ap, false, c.s));
+  GNOT_CK(launch_attn_apply(a.apply_fwd, ap, false, c.s));
   if (p->sharded) GNOT_RUN(shard_exchange(c, p->P_("xb"), res_out, false));   // the scramble, across ranks
   // fc_out over the scramble rows: Dr columns per token (the head-major apply output viewed as rows of
   // H * dh = Dr floats, model.py:81-83), read zero-filled to the padded width
-  GNOT_RUN(run_linear(c, res_out, p->Dr, p->Dr, A.o, pbias + A.bo, out, D, D, P, EPI_STORE, 0));
-  GNOT_RUN(drop_rows(c, out, l, cross));     // everything downstream reads the dropped rows
+  GNOT_RUN(run_linear(c, res_out, p->Dr, p->Dr, a.o_img, pbias + a.bo, out, D, D, P, EPI_STORE, 0));
+  GNOT_RUN(drop_rows(c, out, a));            // everything downstream reads the dropped rows
   return GNOT_OK;
 }
 
-// backward of one LinearAttention call; its output gradient is materialised in dsum_buf(cross).
-// Accumulates d(query input) into dquery and forks the weight gradients of its 4+ Linears.
-int attn_backward(Ctx& c, int l, bool cross) {
+// backward of one LinearAttention call; its output gradient is materialised in a.dsum.
+// Accumulates d(query input) into dquery and forks the weight gradients of its Linears.
+int attn_backward(Ctx& c, const AttnCall& a) {
   gnot_plan* p = c.p;
   const long P = p->P;
   const int D = p->D;
-  const std::string s = "b" + std::to_string(l) + ".";
-  const int lo = cross ? p->lin_co(l) : p->lin_so(l);
-  const int lq = cross ? p->lin_cq(l) : p->lin_sq(l);
-  float* dsum = p->P_(p->dsum_buf(cross));
+  float* dsum = p->P_(a.dsum);
   float* dres = p->P_("dres");
   float* dquery = p->P_("dquery");
-  float* dqkv = p->P_(p->dqkv_buf(cross));
+  float* dqkv = p->P_(a.dqkv);
   // pre-norm: the projections' backward-data is the gradient of the NORMALISED rows: stored into "dnorm"
   // (written and read on this stream only; no forked weight gradient reads it), then pulled through the norm
   // and added onto dquery
   float* dq_dst = p->pre_norm ? p->P_("dnorm") : dquery;
   const int dq_epi = p->pre_norm ? EPI_STORE : EPI_ACCUM;
-  auto norm_bwd = [&]() -> int {
-    if (!p->pre_norm) return GNOT_OK;
-    GNOT_CK(launch_layer_norm_bwd(p->P_(p->norm_buf(l, cross)), D, p->P_(p->norm_rstd(l, cross)), dq_dst, D, P, p->Dr,
-                                  dquery, D, 1, c.s));
-    return GNOT_OK;
-  };
   GNOT_RUN(guard_write(c, dqkv));
   // dropout: the forward's mask again, regenerated from the key, before fc_out's backward-data and its weight
   // gradients (a forked group reads the masked rows)
-  GNOT_RUN(drop_rows(c, dsum, l, cross));
+  GNOT_RUN(drop_rows(c, dsum, a));
   // fc_out backward-data: dres = dout W_o (token order); sharded: back to this rank's head-major rows
-  GNOT_RUN(run_linear(c, dsum, D, D, p->T_img[lo], nullptr, dres, p->Dr, D, P, EPI_STORE, 0, p->Dr));
+  GNOT_RUN(run_linear(c, dsum, D, D, p->T_img[a.o], nullptr, dres, p->Dr, D, P, EPI_STORE, 0, p->Dr));
   if (p->sharded) {
     GNOT_RUN(shard_exchange(c, p->P_("xb"), dres, true));
     dres = p->P_("xb");
   }
-  AttnApplyArgs ap = apply_args(p);
-  ap.dres = dres; ap.dq_pre = dqkv; ap.lddu = D;
-  if (cross && p->I > 0) {
-    ap.q = p->P_(s + "cq"); ap.ldq = D; ap.nsrc = p->I; ap.lddq = D;
-    for (int i = 0; i < p->I; ++i) {
-      const std::string si = std::to_string(i);
-      ap.state[i] = p->P_(s + "cstate" + si);
-      ap.du[i] = p->P_("du" + si);
-      ap.dden[i] = p->P_("dden" + si);
-    }
-    GNOT_CK(launch_attn_apply(p->apply_bwd[1], ap, true, c.s));
-    // dS, dz per input function (kept per block: the dK/dV side of every block runs batched later)
-    for (int i = 0; i < p->I; ++i) GNOT_RUN(run_state(c, p->dst_c[l][i]));
-    GNOT_RUN(run_linear(c, dqkv, D, D, p->T_img[lq], nullptr, dq_dst, D, D, P, dq_epi, 0));
-    GNOT_RUN(norm_bwd());
-    GNOT_RUN(run_wgrad_side(c, p->wg_cross[l], {dsum, dqkv}));
-  } else {
-    const float* qkv = p->P_(cross ? s + "cq" : s + "sq");
-    const int lk = cross ? p->lin_ck(l, 0) : p->lin_sk(l);
-    const int lv = cross ? p->lin_cv(l, 0) : p->lin_sv(l);
-    ap.q = qkv; ap.ldq = 3 * D; ap.nsrc = 1; ap.state[0] = p->P_(cross ? s + "cstate0" : s + "sstate");
-    ap.lddq = 3 * D; ap.du[0] = p->P_("du0"); ap.dden[0] = p->P_("dden0");
-    GNOT_CK(launch_attn_apply(p->apply_bwd[cross], ap, true, c.s));
-    float* dst = p->P_("dstate0");
-    GNOT_RUN(run_state(c, cross ? p->dst_c[l][0] : p->dst_s[l]));
+  AttnApplyArgs ap = call_apply_args(p, a, true);
+  ap.dres = dres; ap.dq_pre = dqkv; ap.lddu = D; ap.lddq = a.pitch;
+  GNOT_CK(launch_attn_apply(a.apply_bwd, ap, true, c.s));
+  // dS, dz per source (an input-function source keeps its own per block: the dK/dV side of every block runs
+  // batched later)
+  for (const AttnSrc& r : a.src) GNOT_RUN(run_state(c, r.dst));
+  if (a.fused) {
+    // the call's own K/V backward and the backward-data of q, k and v in one three-segment product
+    const float* qkv = ap.q;
+    float* dst = p->P_(a.src[0].dstate);
     GNOT_RUN(shard_allreduce(c, dst, p->B * p->per_state()));   // dS, dz over all ranks
     AttnKVBwdArgs kb{};
     kb.k = qkv + D; kb.v = qkv + 2 * D; kb.ldkv = 3 * D; kb.dstate = dst; kb.chunks = ap.chunks;
     kb.nchunks = ap.nchunks; kb.H = p->H; kb.dh = p->dh; kb.dk = dqkv + D; kb.dv = dqkv + 2 * D; kb.lddkv = 3 * D;
     GNOT_CK(launch_attn_kv_bwd(p->kv_bwd, &kb, nullptr, 1, kb.nchunks, kb.H, kb.dh, c.s));
-    GNOT_RUN(run_linear_seg(c, {{dqkv, &p->T_img[lq]}, {dqkv + D, &p->T_img[lk]}, {dqkv + 2 * D, &p->T_img[lv]}},
+    GNOT_RUN(run_linear_seg(c, {{dqkv, &p->T_img[a.q]}, {dqkv + D, &p->T_img[a.k[0]]}, {dqkv + 2 * D, &p->T_img[a.v[0]]}},
                             3 * D, dq_dst, D, P, dq_epi));
-    GNOT_RUN(norm_bwd());
-    GNOT_RUN(run_wgrad_side(c, cross ? p->wg_cross[l] : p->wg_self[l], {dsum, dqkv}));
+  } else {
+    GNOT_RUN(run_linear(c, dqkv, D, D, p->T_img[a.q], nullptr, dq_dst, D, D, P, dq_epi, 0));
   }
+  if (p->pre_norm)
+    GNOT_CK(launch_layer_norm_bwd(p->P_(a.in), D, p->P_(a.rstd), dq_dst, D, P, p->Dr, dquery, D, 1, c.s));
+  GNOT_RUN(run_wgrad_side(c, a.wg, {dsum, dqkv}));
   return GNOT_OK;
 }
 
@@ -2427,27 +2415,19 @@ static int forward_impl(gnot_plan* p, const float* x, const float* theta, const 
   }
   // blocks (model.py:126-139)
   for (int l = 0; l < p->L; ++l) {
-    const std::string s = "b" + std::to_string(l) + ".";
-    const float* qin = p->P_(p->block_query(l));
+    const AttnCall &ac = p->call(l, true), &as = p->call(l, false);
+    float* query1 = p->P_(as.in_raw);
     // pre-norm: the attention calls read LN(query) / LN(query1); the residual adds below keep the raw rows
-    const float* q_c = qin;
-    const float* q_s = p->P_(s + "query1");
-    if (p->pre_norm) {
-      GNOT_RUN(norm_fwd(c, qin, P, p->norm_buf(l, true), p->norm_rstd(l, true)));
-      q_c = p->P_(p->norm_buf(l, true));
-    }
-    GNOT_RUN(attn_forward(c, l, true, q_c, p->P_(s + "cres"), p->P_(s + "a")));
+    if (p->pre_norm) GNOT_RUN(norm_fwd(c, p->P_(ac.in_raw), P, ac.in, ac.rstd));
+    GNOT_RUN(attn_forward(c, ac));
     // ffn1 experts: query1 = query + sum_e s_e ffn1_e(a)   (model.py:128-131)
     const bool keep = tr && !p->moe_recompute;   // recompute: the backward re-runs the call into "mrsave"
     const Chain &m1 = p->ch_moe(l, true), &m2 = p->ch_moe(l, false);
-    GNOT_RUN(moe_forward(c, m1, qin, p->P_(s + "query1"), keep ? p->P_(m1.save) : nullptr));
-    if (p->pre_norm) {
-      GNOT_RUN(norm_fwd(c, q_s, P, p->norm_buf(l, false), p->norm_rstd(l, false)));
-      q_s = p->P_(p->norm_buf(l, false));
-    }
-    GNOT_RUN(attn_forward(c, l, false, q_s, p->P_(s + "sres"), p->P_(s + "bb")));
+    GNOT_RUN(moe_forward(c, m1, p->P_(ac.in_raw), query1, keep ? p->P_(m1.save) : nullptr));
+    if (p->pre_norm) GNOT_RUN(norm_fwd(c, query1, P, as.in, as.rstd));
+    GNOT_RUN(attn_forward(c, as));
     // ffn2 experts: query2 = query1 + sum_e s_e ffn2_e(bb)   (model.py:134-137)
-    GNOT_RUN(moe_forward(c, m2, p->P_(s + "query1"), p->P_(s + "query2"), keep ? p->P_(m2.save) : nullptr));
+    GNOT_RUN(moe_forward(c, m2, query1, p->P_(p->block_query(l + 1)), keep ? p->P_(m2.save) : nullptr));
   }
   // decoder (model.py:171)
   GNOT_RUN(chain_fwd(c, p->ch_out(), out, p->out));
@@ -2542,7 +2522,8 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
         GNOT_CK(launch_chain_fwd(cw_scratch(p, f, c.s), c.s));
       }
       ChainArgs a = bwd_args(C, dquery, D);
-      float* dsum = p->P_(p->dsum_buf(m1));
+      const AttnCall& ac = p->call(l, m1);       // the call whose output this MoE read
+      float* dsum = p->P_(ac.dsum);
       // d(MoE input) = sum_e W_e0^T dz_e0: each expert's term into the stage, summed by moe_combine
       GNOT_RUN(guard_write(c, dsum));
       a.dX = stage; a.lddx = D; a.dx_chain_stride = P * D;
@@ -2550,7 +2531,7 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
       GNOT_CK(launch_moe_pass(p, nullptr, stage, dsum, c.s));
       GNOT_RUN(flush_deferred(c));            // the chain's weight gradients: side launch after the pass
       // m2: self attention (model.py:133) ; m1: cross attention (model.py:127)
-      GNOT_RUN(attn_backward(c, l, m1));
+      GNOT_RUN(attn_backward(c, ac));
     }
   }
   // the input-function branch again runs on side2, concurrently with the query encoder and gating.  A backward
@@ -2562,7 +2543,7 @@ static int backward_impl(gnot_plan* p, const float* dout, int flags, void* strea
   Ctx cf{p, br ? p->side2 : c.s};
   // ranks issue their gradient collectives in one host order whatever serial_wgrad() says (it is chosen
   // per rank from the local point count): a forked rank still holds the last attention call's groups
-  // (wg_cross[0]) deferred here, and side2 issues its groups' all-reduces at once -- flush first
+  // (block 0's cross call's) deferred here, and side2 issues its groups' all-reduces at once -- flush first
   if (p->grad_comm_live) GNOT_RUN(flush_deferred(c));
   if (br) {
     hipEvent_t fork = next_event(p);
@@ -2718,13 +2699,18 @@ extern "C" int gnot_debug_kernel_forms(const gnot_plan* p, char* text, size_t ca
   auto state = [](const WgradGroup* G) { return !G || G->jobs.empty() ? "none" : G->state_mfma ? "mfma" : "valu"; };
   std::string t;
   auto put = [&](const char* key, const char* value) { t += (t.empty() ? "" : " ") + std::string(key) + "=" + value; };
-  put("apply_fwd.self", attn(p->apply_fwd[0]));
-  put("apply_fwd.cross", attn(p->apply_fwd[1]));
-  put("apply_bwd.self", attn(p->apply_bwd[0]));
-  put("apply_bwd.cross", attn(p->apply_bwd[1]));
+  // the apply forms of block 0's calls (every block's are the same); without a block, those its calls would take
+  auto apply = [&](bool cross, bool bwd) {
+    if (p->L == 0) return attn(apply_form(p, bwd ? AttnPass::ApplyBwd : AttnPass::ApplyFwd, cross ? p->KI : 1));
+    return attn(bwd ? p->call(0, cross).apply_bwd : p->call(0, cross).apply_fwd);
+  };
+  put("apply_fwd.self", apply(false, false));
+  put("apply_fwd.cross", apply(true, false));
+  put("apply_bwd.self", apply(false, true));
+  put("apply_bwd.cross", apply(true, true));
   put("kv_bwd", attn(p->kv_bwd));
   put("kv_bwd_batch", p->I > 0 && p->L > 0 ? attn(p->kv_bwd_batch) : "none");
-  put("state.query", state(p->L > 0 ? &p->st_s[0] : nullptr));
+  put("state.query", state(p->L > 0 ? &p->call(0, false).src[0].st : nullptr));
   put("state.fn", state(&p->st_fn));
   put("serial_wgrad", p->serial_wgrad() ? "1" : "0");
   put("moe_direct_out", p->moe_direct_out() ? "1" : "0");
