@@ -2765,9 +2765,10 @@ extern "C" size_t gnot_lp_loss_work_floats(const int64_t* off_host, int B, int C
   return gnot_rel_l2_work_floats(off_host, B, C);      // the widest layout of the family: two norms per channel
 }
 
-// Every loss entry: `name` is the caller's in messages; allow_empty: a sample may have no rows.
+// Every loss entry: `name` is the caller's in messages; allow_empty: a sample may have no rows; point_w: the
+// per-row weights of gnot_lp_loss_weighted (nullptr: every other entry, the unweighted kernels).
 static int loss_entry(const char* name, int kind, bool allow_empty, const float* pred, const float* tgt,
-                      const int64_t* off_dev, const int64_t* off_host, int B, int C, const float* comp_weights,
+                      const float* point_w, const int64_t* off_dev, const int64_t* off_host, int B, int C, const float* comp_weights,
                       const float* stats, float* work, float* loss, float* terms, float* dpred, void* stream) {
   static_assert(GNOT_LP_REL2 == 0 && GNOT_LP_REL1 == 1 && GNOT_LP_RELINF == 2 && GNOT_LP_MSE == 3 &&
                 GNOT_LP_L1 == 4 && GNOT_LP_LINF == 5, "launch_lp's kinds");
@@ -2779,44 +2780,58 @@ static int loss_entry(const char* name, int kind, bool allow_empty, const float*
     return fail(GNOT_E_INVALID, "lp_loss: relinf and linf are metrics only: they have no gradient (dpred must be null)");
   std::vector<long> off(off_host, off_host + B + 1);
   if (int rc = check_loss_offsets(off, allow_empty)) return rc;
-  GNOT_CK(launch_lp(kind, pred, tgt, reinterpret_cast<const long*>(off_dev), B, C, rel_l2_splits(off.data(), B), off[B],
-                    comp_weights, stats, work, loss, terms, dpred, static_cast<hipStream_t>(stream)));
+  GNOT_CK(launch_lp(kind, pred, tgt, point_w, reinterpret_cast<const long*>(off_dev), B, C,
+                    rel_l2_splits(off.data(), B), off[B], comp_weights, stats, work, loss, terms, dpred,
+                    static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 
 extern "C" int gnot_rel_l2_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
                                 int B, int C, float* work, float* loss, float* dpred, void* stream) {
-  return loss_entry("rel_l2", GNOT_LP_REL2, true, pred, tgt, off_dev, off_host, B, C, nullptr, nullptr, work, loss,
-                    nullptr, dpred, stream);
+  return loss_entry("rel_l2", GNOT_LP_REL2, true, pred, tgt, nullptr, off_dev, off_host, B, C, nullptr, nullptr, work,
+                    loss, nullptr, dpred, stream);
 }
 
 extern "C" int gnot_rel_l2_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev,
                                        const int64_t* off_host, int B, int C, const float* out_stats, float* work,
                                        float* loss, float* dpred, void* stream) {
   if (!out_stats) return fail(GNOT_E_INVALID, "rel_l2_loss_affine: null out_stats");
-  return loss_entry("rel_l2", GNOT_LP_REL2, true, pred, tgt, off_dev, off_host, B, C, nullptr, out_stats, work, loss,
-                    nullptr, dpred, stream);
+  return loss_entry("rel_l2", GNOT_LP_REL2, true, pred, tgt, nullptr, off_dev, off_host, B, C, nullptr, out_stats, work,
+                    loss, nullptr, dpred, stream);
 }
 
 extern "C" int gnot_mse_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
                              int B, int C, float* work, float* loss, float* dpred, void* stream) {
-  return loss_entry("mse", GNOT_LP_MSE, false, pred, tgt, off_dev, off_host, B, C, nullptr, nullptr, work, loss,
-                    nullptr, dpred, stream);
+  return loss_entry("mse", GNOT_LP_MSE, false, pred, tgt, nullptr, off_dev, off_host, B, C, nullptr, nullptr, work,
+                    loss, nullptr, dpred, stream);
 }
 
 extern "C" int gnot_mse_loss_affine(const float* pred, const float* tgt, const int64_t* off_dev,
                                     const int64_t* off_host, int B, int C, const float* out_stats, float* work,
                                     float* loss, float* dpred, void* stream) {
   if (!out_stats) return fail(GNOT_E_INVALID, "mse_loss_affine: null out_stats");
-  return loss_entry("mse", GNOT_LP_MSE, false, pred, tgt, off_dev, off_host, B, C, nullptr, out_stats, work, loss,
-                    nullptr, dpred, stream);
+  return loss_entry("mse", GNOT_LP_MSE, false, pred, tgt, nullptr, off_dev, off_host, B, C, nullptr, out_stats, work,
+                    loss, nullptr, dpred, stream);
 }
 
 extern "C" int gnot_lp_loss(const float* pred, const float* tgt, const int64_t* off_dev, const int64_t* off_host,
                             int B, int C, int kind, const float* comp_weights, const float* out_stats, float* work,
                             float* loss, float* terms, float* dpred, void* stream) {
-  return loss_entry("lp_loss", kind, false, pred, tgt, off_dev, off_host, B, C, comp_weights, out_stats, work, loss,
-                    terms, dpred, stream);
+  return loss_entry("lp_loss", kind, false, pred, tgt, nullptr, off_dev, off_host, B, C, comp_weights, out_stats, work,
+                    loss, terms, dpred, stream);
+}
+
+extern "C" size_t gnot_lp_loss_weighted_work_floats(const int64_t* off_host, int B, int C) {
+  return gnot_rel_l2_work_floats(off_host, B, C);      // two floats per channel: the norms, or the norm and sum w
+}
+
+extern "C" int gnot_lp_loss_weighted(const float* pred, const float* tgt, const float* point_w, const int64_t* off_dev,
+                                     const int64_t* off_host, int B, int C, int kind, const float* comp_weights,
+                                     const float* out_stats, float* work, float* loss, float* terms, float* dpred,
+                                     void* stream) {
+  if (!point_w) return fail(GNOT_E_INVALID, "lp_loss_weighted: null point_w");
+  return loss_entry("lp_loss_weighted", kind, false, pred, tgt, point_w, off_dev, off_host, B, C, comp_weights,
+                    out_stats, work, loss, terms, dpred, stream);
 }
 
 extern "C" int gnot_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
@@ -2994,6 +3009,23 @@ extern "C" int gnot_channel_stats(const float* src, int64_t rows, int C, float e
   if (!(eps >= 0.f) || !std::isfinite(eps))
     return fail(GNOT_E_INVALID, "channel_stats: eps must be finite and not negative");
   GNOT_CK(launch_channel_stats(src, rows, C, eps, work, stats, static_cast<hipStream_t>(stream)));
+  return GNOT_OK;
+}
+
+extern "C" size_t gnot_channel_stats_weighted_work_floats(int64_t rows, int C) {
+  if (rows < 1 || C < 1) return 0;
+  return (size_t)channel_stats_slices(rows) * (2 + 3 * (size_t)C);
+}
+
+extern "C" int gnot_channel_stats_weighted(const float* src, const float* w, int64_t rows, int C, float eps,
+                                           float* work, float* stats, void* stream) {
+  if (!src || !w || !work || !stats) return fail(GNOT_E_INVALID, "channel_stats_weighted: null argument");
+  if (rows < 1 || rows >= (1L << 31))
+    return fail(GNOT_E_INVALID, "channel_stats_weighted: rows must be in [1, 2^31)");
+  if (C < 1) return fail(GNOT_E_INVALID, "channel_stats_weighted: C must be at least 1");
+  if (!(eps >= 0.f) || !std::isfinite(eps))
+    return fail(GNOT_E_INVALID, "channel_stats_weighted: eps must be finite and not negative");
+  GNOT_CK(launch_channel_stats_weighted(src, w, rows, C, eps, work, stats, static_cast<hipStream_t>(stream)));
   return GNOT_OK;
 }
 

@@ -363,9 +363,12 @@ int rel_l2_splits(const long* off_host, int B);
 // (a stats block {mean[C], std[C], rstd[C]}, stats.hip): the loss of pred * std[c] + mean[c] and its gradient
 // times std[c]; nullptr: the plain loss.  work: B*nsplit*kW*C + B*C floats (nsplit = rel_l2_splits; kW = 2 for
 // the relative kinds 0-2, else 1).  A sample without rows makes sense for rel2 alone (its term is a NaN).
-hipError_t launch_lp(int kind, const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                     long rows, const float* w, const float* stats, float* work, float* loss, float* terms,
-                     float* dpred, hipStream_t s);
+// point_w != nullptr (one weight >= 0 per packed row, device [rows]): the weighted terms of gnot_lp_loss_weighted,
+// rows of weight zero not read; kW is then 2 for every kind but linf (mse / l1 carry sum w).  nullptr: the
+// unweighted kernels, untouched.
+hipError_t launch_lp(int kind, const float* pred, const float* tgt, const float* point_w, const long* off_dev, int B,
+                     int C, int nsplit, long rows, const float* w, const float* stats, float* work, float* loss,
+                     float* terms, float* dpred, hipStream_t s);
 // stage-1 partial sums of sum g^2 over n elements (a function of n alone); 0 for n < 1
 long grad_clip_partials(long n);
 // work: grad_clip_partials(n) floats; clip: 2 floats {norm, coefficient}
@@ -410,5 +413,10 @@ long channel_stats_slices(long rows);
 // std 0, rstd 1).  work: channel_stats_slices(rows) * 3 * C floats; rows >= 1, C >= 1
 hipError_t launch_channel_stats(const float* src, long rows, int C, float eps, float* work, float* stats,
                                 hipStream_t s);
+// the same block with a weight w[r] >= 0 per row (device [rows]): mean = sum w x / sum w, the reliability-weights
+// variance (divisor sum w - sum w^2 / sum w; not positive: a constant channel), rows of weight zero not read.
+// work: channel_stats_slices(rows) * (2 + 3 * C) floats
+hipError_t launch_channel_stats_weighted(const float* src, const float* w, long rows, int C, float eps, float* work,
+                                         float* stats, hipStream_t s);
 
 }  // namespace gnot

@@ -10,6 +10,9 @@
 //             sums reduced in a fixed order, no atomics.
 //   affine    a loss on a normalised prediction: p' = pred * std[c] + mean[c] against the raw target, and the
 //             gradient scaled by std[c], inside the same passes (Stats of the partial and grad kernels).
+//   weighted  a loss with one weight per packed row (gnot_lp_loss_weighted: quadrature weights, masks): sums of
+//             w |d|^p over the rows with w > 0 and sum w for N_b, as one more entry of the same pack
+//             (PointWeights); the unweighted instantiations keep their argument lists and code.
 //   adamw     torch.optim.AdamW's update (main.py:51; decoupled weight decay, bias-corrected moments)
 //             over ONE flat fp32 arena of parameters / gradients / moments, in torch's op order.
 //             Hyper-parameters come from a small device array so a captured hipGraph replays
@@ -23,12 +26,14 @@
 //             (ema_update_kernel); w comes from device memory like the other hyper-parameters.
 // adamw, its clipped and guarded forms and the fused average are one kernel, adamw_update_kernel<kEma>; the
 // slice-table form adamw_groups_kernel<kEma> runs the same guard and the same element update (adamw_element).
+#include <type_traits>
+
 #include "gnot_common.h"
 #include "gnot_kernels.h"
 
 namespace gnot {
 
-constexpr int kLossRows = 2048;   // rows per partial-sum workgroup
+constexpr int kLossRows = 2048;  // rows per partial-sum workgroup
 
 // the sample b of packed row r: off[b] <= r < off[b + 1], for 0 <= r < off[B]
 __device__ __forceinline__ int sample_of_row(const long* __restrict__ off, int B, long r) {
@@ -52,6 +57,28 @@ static unsigned flat_grid(long n) { return (unsigned)std::min<long>((n + 255) / 
 __device__ __forceinline__ float denormalised(float p, const float* __restrict__ stats, int C, int c) {
   return __fadd_rn(mul_rn(p, stats[C + c]), stats[c]);
 }
+
+// A loss with per-point weights (gnot_lp_loss_weighted): one weight w_r >= 0 per packed row, which multiplies
+// the row's |d|^p and |t|^p in the sums and its gradient, and sum w stands where N_b stood.  It is one more entry
+// of the same pack, PointWeights, behind the stats block if there is one: Stats is {}, {const float*},
+// {PointWeights} or {const float*, PointWeights}, and the first two are the kernels above, argument for argument.
+//   * a row with w_r == 0 (anything that is not > 0) is skipped before its pred / tgt are loaded -- a NaN under a
+//     mask never meets a 0 * NaN -- and its gradient elements are stored as zeros;
+//   * w_r == 1 everywhere gives the unweighted kernels' bits: fmaf(w d, d, acc), acc + w |d| and (w d) s multiply
+//     by one exactly, in the unweighted order, and sum w == N_b exactly below 2^24 rows a sample;
+//   * w_r times a power of two over a whole sample scales every sum exactly and cancels in every term and in
+//     w_r * scale: no bit of loss, terms or gradient moves.
+struct PointWeights {
+  const float* w;   // DEVICE [rows]
+};
+template <typename... A>
+inline constexpr bool kHasStats = (std::is_same_v<A, const float*> || ...);
+template <typename... A>
+inline constexpr bool kHasPointW = (std::is_same_v<A, PointWeights> || ...);
+__device__ __forceinline__ const float* stats_of(const float* s) { return s; }
+__device__ __forceinline__ const float* stats_of(const float* s, PointWeights) { return s; }
+__device__ __forceinline__ const float* point_w_of(PointWeights p) { return p.w; }
+__device__ __forceinline__ const float* point_w_of(const float*, PointWeights p) { return p.w; }
 
 // the 2048-row splits of the longest sample: partial sums per (sample, split), at least one split
 int rel_l2_splits(const long* off_host, int B) {
@@ -96,47 +123,79 @@ __device__ __forceinline__ float lp_block(float x, float* red) {
   else return block_sum(x, red);
 }
 
-// partial[b][split][0..kW C), kW = kRel ? 2 : 1: the norm's sum (or maximum) of d [C] and, kRel, of t [C] over
-// the split's rows of sample b (an empty split: zeros)
+// ... and of a row of weight w > 0: sum w v^2, sum w |v|, and the maximum over the weighted rows, which w does
+// not scale.  w == 1 is lp_accumulate, bit for bit.
+template <int kNorm>
+__device__ __forceinline__ float lp_accumulate_w(float w, float v, float acc) {
+  if constexpr (kNorm == 2) return fmaf(mul_rn(w, v), v, acc);
+  else if constexpr (kNorm == 1) return acc + mul_rn(w, fabsf(v));
+  else return nan_max(acc, fabsf(v));
+}
+
+// floats per channel of a partial: the norm of d and, for a relative kind, of t; a weighted mean kind (mse, l1
+// with PointWeights) carries sum w in the second place
+template <int kNorm, bool kRel, bool kPointW>
+constexpr int lp_partial_width() { return (kRel || (kPointW && kNorm != 0)) ? 2 : 1; }
+
+// partial[b][split][0..kW C), kW = lp_partial_width: the norm's sum (or maximum) of d [C] and, kRel, of t [C] over
+// the split's rows of sample b (an empty split: zeros); with PointWeights over its rows of positive weight, and
+// sum w [C] (every channel's the same) in t's place for mse / l1
 template <int kNorm, bool kRel, typename... Stats>
 __global__ void __launch_bounds__(256) lp_partial_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                          const long* __restrict__ off, int C, int nsplit,
                                                          float* __restrict__ partial, Stats... stats_arg) {
   __shared__ float red[256];
-  constexpr int kW = kRel ? 2 : 1;
+  constexpr bool kPointW = kHasPointW<Stats...>;
+  constexpr bool kSumW = kPointW && !kRel && kNorm != 0;
+  constexpr int kW = lp_partial_width<kNorm, kRel, kPointW>();
   const int b = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
   const long r0 = off[b] + (long)split * kLossRows;
   const long r1 = min(off[b + 1], r0 + kLossRows);
   for (int c = 0; c < C; ++c) {
     float num = 0.f, den = 0.f;
     for (long r = r0 + threadIdx.x; r < r1; r += 256) {
-      const float t = tgt[r * C + c];
-      float d;
-      if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[r * C + c], (stats_arg, ...), C, c) - t;
-      else d = pred[r * C + c] - t;
-      num = lp_accumulate<kNorm>(d, num);
-      if constexpr (kRel) den = lp_accumulate<kNorm>(t, den);
+      if constexpr (kPointW) {
+        const float pw = point_w_of(stats_arg...)[r];
+        if (!(pw > 0.f)) continue;      // not read into any sum: its pred and tgt are not even loaded
+        const float t = tgt[r * C + c];
+        float d;
+        if constexpr (kHasStats<Stats...>) d = denormalised(pred[r * C + c], stats_of(stats_arg...), C, c) - t;
+        else d = pred[r * C + c] - t;
+        num = lp_accumulate_w<kNorm>(pw, d, num);
+        if constexpr (kRel) den = lp_accumulate_w<kNorm>(pw, t, den);
+        if constexpr (kSumW) den += pw;
+      } else {
+        const float t = tgt[r * C + c];
+        float d;
+        if constexpr (kHasStats<Stats...>) d = denormalised(pred[r * C + c], stats_of(stats_arg...), C, c) - t;
+        else d = pred[r * C + c] - t;
+        num = lp_accumulate<kNorm>(d, num);
+        if constexpr (kRel) den = lp_accumulate<kNorm>(t, den);
+      }
     }
     num = lp_block<kNorm>(num, red);
     if constexpr (kRel) den = lp_block<kNorm>(den, red);
+    if constexpr (kSumW) den = block_sum(den, red);
     if (threadIdx.x == 0) {
       float* P = partial + ((long)b * nsplit + split) * kW * C;
       P[c] = num;
-      if constexpr (kRel) P[C + c] = den;
+      if constexpr (kW == 2) P[C + c] = den;
     }
   }
 }
 
 // one workgroup: the norms per (b, c) in split order, the term e[b, c] (to terms, if asked for), the loss and
 // the per-(b, c) gradient scale s: d loss / d p' = s d (kNorm 2) or s sign(d) (kNorm 1).  w == nullptr: the
-// plain mean over (sample, channel), sum e / (B C); else w^_c from w[C], summed in index order.
-template <int kNorm, bool kRel>
+// plain mean over (sample, channel), sum e / (B C); else w^_c from w[C], summed in index order.  kPointW (the
+// partials of a weighted pass): the mean kinds divide by the sample's sum w, summed in split order like the
+// norms -- N_b exactly when every weight is 1 -- and every other kind finishes as without weights.
+template <int kNorm, bool kRel, bool kPointW = false>
 __global__ void __launch_bounds__(256) lp_finish_kernel(const float* __restrict__ partial, const long* __restrict__ off,
                                                         int B, int C, int nsplit, const float* __restrict__ w,
                                                         float* __restrict__ scale, float* __restrict__ loss,
                                                         float* __restrict__ terms) {
   __shared__ float red[256];
-  constexpr int kW = kRel ? 2 : 1;
+  constexpr int kW = lp_partial_width<kNorm, kRel, kPointW>();
   float wsum = 0.f;
   if (w) for (int c = 0; c < C; ++c) wsum += w[c];
   float acc = 0.f;
@@ -148,9 +207,11 @@ __global__ void __launch_bounds__(256) lp_finish_kernel(const float* __restrict_
       if constexpr (kNorm == 0) num = nan_max(num, P[c]); else num += P[c];
       if constexpr (kRel) {
         if constexpr (kNorm == 0) den = nan_max(den, P[C + c]); else den += P[C + c];
+      } else if constexpr (kW == 2) {
+        den += P[C + c];
       }
     }
-    const float n = (float)(off[b + 1] - off[b]);
+    const float n = (kW == 2 && !kRel) ? den : (float)(off[b + 1] - off[b]);
     float e;
     if constexpr (kRel) e = kNorm == 2 ? sqrtf(num / den) : num / den;
     else e = kNorm == 0 ? num : num / n;
@@ -179,15 +240,26 @@ __global__ void __launch_bounds__(256) lp_grad_kernel(const float* __restrict__ 
   const long r = i / C;
   const int c = (int)(i % C);
   if (w && w[c] == 0.f) { dpred[i] = 0.f; return; }
+  [[maybe_unused]] float pw = 1.0f;
+  if constexpr (kHasPointW<Stats...>) {      // a row of weight zero: exact zeros, its pred and tgt not loaded
+    pw = point_w_of(stats_arg...)[r];
+    if (!(pw > 0.f)) { dpred[i] = 0.f; return; }
+  }
   const float s = scale[sample_of_row(off, B, r) * C + c];
   float d;
-  if constexpr (sizeof...(Stats) == 1) d = denormalised(pred[i], (stats_arg, ...), C, c) - tgt[i];
+  if constexpr (kHasStats<Stats...>) d = denormalised(pred[i], stats_of(stats_arg...), C, c) - tgt[i];
   else d = pred[i] - tgt[i];
   float g;
-  if constexpr (kNorm == 2) g = d * s;
-  else g = d > 0.f ? s : d < 0.f ? -s : mul_rn(d, 0.f);      // sign(0) = 0; a NaN stays one
-  if constexpr (sizeof...(Stats) == 1) {
-    const float* __restrict__ stats = (stats_arg, ...);
+  if constexpr (kHasPointW<Stats...>) {      // the row's weight times the unweighted expression; w == 1: its bits
+    const float ws = mul_rn(pw, s);
+    if constexpr (kNorm == 2) g = mul_rn(pw, d) * s;
+    else g = d > 0.f ? ws : d < 0.f ? -ws : mul_rn(d, 0.f);
+  } else {
+    if constexpr (kNorm == 2) g = d * s;
+    else g = d > 0.f ? s : d < 0.f ? -s : mul_rn(d, 0.f);      // sign(0) = 0; a NaN stays one
+  }
+  if constexpr (kHasStats<Stats...>) {
+    const float* __restrict__ stats = stats_of(stats_arg...);
     dpred[i] = mul_rn(g, stats[C + c]);
   } else {
     dpred[i] = g;
@@ -198,12 +270,14 @@ template <int kNorm, bool kRel, typename... Stats>
 static hipError_t launch_lp_t(const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
                               long rows, const float* w, float* work, float* loss, float* terms, float* dpred,
                               hipStream_t s, Stats... stats) {
+  constexpr bool kPointW = kHasPointW<Stats...>;
   float* partial = work;                                              // [B][nsplit][kW C]
-  float* scale = work + (size_t)B * nsplit * (kRel ? 2 : 1) * C;      // [B][C]
+  float* scale = work + (size_t)B * nsplit * lp_partial_width<kNorm, kRel, kPointW>() * C;      // [B][C]
   hipLaunchKernelGGL((lp_partial_kernel<kNorm, kRel, Stats...>), dim3(B * nsplit), dim3(256), 0, s, pred, tgt, off_dev,
                      C, nsplit, partial, stats...);
-  hipLaunchKernelGGL((lp_finish_kernel<kNorm, kRel>), dim3(1), dim3(256), 0, s, (const float*)partial, off_dev, B, C,
-                     nsplit, w, scale, loss, terms);
+  // (only the weighted mean kinds finish differently: every other weighted pass shares the unweighted kernel)
+  hipLaunchKernelGGL((lp_finish_kernel<kNorm, kRel, kPointW && !kRel && kNorm != 0>), dim3(1), dim3(256), 0, s,
+                     (const float*)partial, off_dev, B, C, nsplit, w, scale, loss, terms);
   if constexpr (kNorm != 0) {
     if (dpred && rows > 0)
       hipLaunchKernelGGL((lp_grad_kernel<kNorm, Stats...>), dim3((unsigned)((rows * C + 255) / 256)), dim3(256), 0, s,
@@ -215,15 +289,18 @@ static hipError_t launch_lp_t(const float* pred, const float* tgt, const long* o
 // kind: GNOT_LP_* (gnot_hip.h), checked by the caller, as is dpred == nullptr for the two maximum norms.
 // work: B*nsplit*kW*C + B*C floats, kW = 2 for the relative kinds, else 1 (nsplit = rel_l2_splits).  A sample
 // without rows has zero norms: rel2's term is then sqrt(0 / 0), a NaN (the caller refuses it for every other
-// kind).  w, stats, terms, dpred may be null.
-hipError_t launch_lp(int kind, const float* pred, const float* tgt, const long* off_dev, int B, int C, int nsplit,
-                     long rows, const float* w, const float* stats, float* work, float* loss, float* terms,
-                     float* dpred, hipStream_t s) {
+// kind).  w, stats, terms, dpred may be null.  point_w (per-row weights, [rows]; nullptr: none): the weighted
+// kernels, whose partials are two floats wide for every kind but linf.
+hipError_t launch_lp(int kind, const float* pred, const float* tgt, const float* point_w, const long* off_dev, int B,
+                     int C, int nsplit, long rows, const float* w, const float* stats, float* work, float* loss,
+                     float* terms, float* dpred, hipStream_t s) {
+#define GNOT_LP_ARGS pred, tgt, off_dev, B, C, nsplit, rows, w, work, loss, terms, dpred, s
 #define GNOT_LP_CASE(K, NORM, REL)                                                                                   \
   case K:                                                                                                            \
-    return stats ? launch_lp_t<NORM, REL>(pred, tgt, off_dev, B, C, nsplit, rows, w, work, loss, terms, dpred, s,    \
-                                          stats)                                                                     \
-                 : launch_lp_t<NORM, REL>(pred, tgt, off_dev, B, C, nsplit, rows, w, work, loss, terms, dpred, s);
+    if (point_w)                                                                                                     \
+      return stats ? launch_lp_t<NORM, REL>(GNOT_LP_ARGS, stats, PointWeights{point_w})                              \
+                   : launch_lp_t<NORM, REL>(GNOT_LP_ARGS, PointWeights{point_w});                                    \
+    return stats ? launch_lp_t<NORM, REL>(GNOT_LP_ARGS, stats) : launch_lp_t<NORM, REL>(GNOT_LP_ARGS);
   switch (kind) {
     GNOT_LP_CASE(0, 2, true)
     GNOT_LP_CASE(1, 1, true)
@@ -233,6 +310,7 @@ hipError_t launch_lp(int kind, const float* pred, const float* tgt, const long* 
     GNOT_LP_CASE(5, 0, false)
   }
 #undef GNOT_LP_CASE
+#undef GNOT_LP_ARGS
   return hipErrorInvalidValue;
 }
 

@@ -41,6 +41,8 @@ EXPORTS = [
     "gnot_plan_set_dropout", "gnot_plan_set_dropout_active", "gnot_dropout_rows",
     "gnot_adamw_step_groups", "gnot_grad_norm_groups", "gnot_grad_clip_groups",
     "gnot_plan_set_trainable", "gnot_debug_backward_plan",
+    "gnot_lp_loss_weighted_work_floats", "gnot_lp_loss_weighted",
+    "gnot_channel_stats_weighted_work_floats", "gnot_channel_stats_weighted",
 ]
 # (the header's int / void / size_t / const char* functions; gnot_plan_grad_floats returns int64_t and is
 # declared in _declare like the rest)
@@ -168,6 +170,12 @@ def _declare(lib):
     lib.gnot_grad_clip_groups.argtypes = [P, i64, P, ctypes.c_float, P, ctypes.POINTER(i64), i64, P, P, P]
     lib.gnot_plan_set_trainable.argtypes = [P, P]
     lib.gnot_debug_backward_plan.argtypes = [P, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.gnot_lp_loss_weighted_work_floats.argtypes = [ctypes.POINTER(i64), i32, i32]
+    lib.gnot_lp_loss_weighted_work_floats.restype = sz
+    lib.gnot_lp_loss_weighted.argtypes = [P, P, P, P, ctypes.POINTER(i64), i32, i32, i32, P, P, P, P, P, P, P]
+    lib.gnot_channel_stats_weighted_work_floats.argtypes = [i64, i32]
+    lib.gnot_channel_stats_weighted_work_floats.restype = sz
+    lib.gnot_channel_stats_weighted.argtypes = [P, P, i64, i32, ctypes.c_float, P, P, P]
     lib.gnot_last_error.restype = ctypes.c_char_p
     lib.gnot_last_error.argtypes = []
     lib.gnot_version.restype = ctypes.c_char_p

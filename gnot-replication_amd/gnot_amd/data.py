@@ -46,10 +46,12 @@ def safe_load(path):
 
 
 def write_ns2d(path, samples):
-    """Write samples [[X, Y, theta, [f...]], ...] (numpy) in the reference's pickle format."""
+    """Write samples [[X, Y, theta, [f...]], ...] (numpy) in the reference's pickle format.  A sample with a
+    fifth entry W [N] (per-point weights, NS2dData(point_weights=True)) is written with it; one without, as
+    the reference's four entries."""
     with open(path, "wb") as f:
         pickle.dump([[np.asarray(s[0]), np.asarray(s[1]), np.asarray(s[2]), [np.asarray(v) for v in s[3]]]
-                     for s in samples], f, protocol=4)
+                     + ([np.asarray(s[4])] if len(s) > 4 else []) for s in samples], f, protocol=4)
 
 
 def synthetic_sample(rng, n_points, input_dim=2, out_dim=1, theta_dim=1, fn_points=(805,), fn_dim=3):
@@ -62,16 +64,43 @@ def synthetic_sample(rng, n_points, input_dim=2, out_dim=1, theta_dim=1, fn_poin
     return [x.astype(np.float64), y.astype(np.float64), theta, fns]
 
 
-class NS2dData(torch.utils.data.Dataset):
-    """dataset.py:6-44 without dgl: item = (x [N, in], y [N, out], theta, [f_i [M_i, F]])."""
+def _sample_weights(sample, index, n):
+    """the fifth entry of sample `index` as a [n] fp32 tensor, or ValueError (NS2dData(point_weights=True));
+    the checks are on the fp32 values the kernels read"""
+    if len(sample) < 5:
+        raise ValueError(f"NS2dData(point_weights=True): sample {index} has no fifth entry W [N]")
+    w = np.asarray(sample[4])
+    if not (w.ndim == 1 or (w.ndim == 2 and w.shape[1] == 1)) or w.shape[0] != n:
+        raise ValueError(f"NS2dData: the point weights of sample {index} have shape {tuple(w.shape)}, its mesh has "
+                         f"{n} points")
+    w = torch.from_numpy(np.ascontiguousarray(w.reshape(-1))).float()
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError(f"NS2dData: the point weights of sample {index} are not all finite")
+    if bool((w < 0).any()):
+        raise ValueError(f"NS2dData: sample {index} has a negative point weight")
+    if not bool((w > 0).any()):
+        raise ValueError(f"NS2dData: every point weight of sample {index} is zero")
+    return w
 
-    def __init__(self, path_or_samples):
+
+class NS2dData(torch.utils.data.Dataset):
+    """dataset.py:6-44 without dgl: item = (x [N, in], y [N, out], theta, [f_i [M_i, F]]).
+    point_weights: a sample may carry a fifth entry W [N], one weight >= 0 per query point (a quadrature or
+    lumped-mass weight, a 0/1 mask, anything else) for the weighted losses and target statistics.  False
+    (default): a fifth entry is ignored and the items are the 4-tuples above.  True: every sample must have
+    one and the items are 5-tuples (..., w [N] fp32); weights that are not finite, negative, of another length
+    than N, or zero on every row of a sample are a ValueError (checked here, on the host)."""
+
+    def __init__(self, path_or_samples, point_weights=False):
         self.data = safe_load(path_or_samples) if isinstance(path_or_samples, str) else path_or_samples
+        self.point_weights = bool(point_weights)
         self.items = []
-        for s in self.data:
+        for i, s in enumerate(self.data):
             fns = [torch.from_numpy(np.asarray(f)).float() for f in s[3]] if s[3] else []
-            self.items.append((torch.from_numpy(np.asarray(s[0])).float(), torch.from_numpy(np.asarray(s[1])).float(),
-                               s[2], fns))
+            item = (torch.from_numpy(np.asarray(s[0])).float(), torch.from_numpy(np.asarray(s[1])).float(), s[2], fns)
+            if self.point_weights:
+                item += (_sample_weights(s, i, item[0].shape[0]),)
+            self.items.append(item)
 
     def __len__(self):
         return len(self.items)
@@ -83,8 +112,11 @@ class NS2dData(torch.utils.data.Dataset):
 def collate_packed(batch):
     """Packed batch (no padding): x [sum N, in], x_off [B+1], y, theta [B, theta_dim], fns[i] packed with
     fn_offs[i] [B+1].  GNOT.forward_packed(x, x_off, theta, fns, fn_offs) on it equals one unpadded
-    B=1 reference call per sample."""
-    xs, ys, thetas, fnl = zip(*batch)
+    B=1 reference call per sample.  Items with point weights (5-tuples, NS2dData(point_weights=True)) add
+    w [sum N], packed like y; 4-tuples give the batch above and no such key."""
+    if len({len(item) for item in batch}) != 1:
+        raise ValueError("collate_packed: items with and without point weights in one batch")
+    xs, ys, thetas, fnl, *ws = zip(*batch)
     off = [0]
     for x in xs:
         off.append(off[-1] + x.shape[0])
@@ -98,13 +130,19 @@ def collate_packed(batch):
         fns.append(torch.cat(parts))
         fn_offs.append(o)
     theta = torch.tensor(np.stack([np.asarray(t, dtype=np.float64) for t in thetas])).float()
-    return dict(x=torch.cat(xs), x_off=off, y=torch.cat(ys), theta=theta, fns=fns, fn_offs=fn_offs)
+    out = dict(x=torch.cat(xs), x_off=off, y=torch.cat(ys), theta=theta, fns=fns, fn_offs=fn_offs)
+    if ws:
+        out["w"] = torch.cat(ws[0])
+    return out
 
 
 def collate_padded(batch):
     """The reference's batch exactly (main.py:60-82, utils.py:3-4): x zero-padded to the batch max N,
     every input function zero-padded to ONE common max M over all functions and samples, stacked
-    [I, B, M, F]; y is returned packed ([sum N, out], main.py:89/93) with the real counts."""
+    [I, B, M, F]; y is returned packed ([sum N, out], main.py:89/93) with the real counts.  Items with point
+    weights (5-tuples) are refused: padded batches take none."""
+    if any(len(item) != 4 for item in batch):
+        raise ValueError("collate_padded takes no point weights (5-tuple items): use collate_packed")
     xs, ys, thetas, fnl = zip(*batch)
     pad = lambda t, L: torch.nn.functional.pad(t, (0, 0, 0, L - t.shape[0]))
     mmax = max((t.shape[0] for arrays in fnl for t in arrays), default=0)
@@ -175,17 +213,23 @@ class DeviceDataset:
     """An NS2d-format dataset packed in device memory once: x_all [sum N, in], y_all [sum N, out], theta
     [S, theta_dim], fn_all[i] [sum M_i, F] (fp32) and the host offset lists x_off [S+1], fn_offs[i] [S+1].
     samples_or_data: an NS2dData, or what NS2dData takes (a path or a list of samples).  An MI355X holds
-    288 GB; an NS2d training set is a few hundred MB, a few GB at 262k points per mesh."""
+    288 GB; an NS2d training set is a few hundred MB, a few GB at 262k points per mesh.
+    point_weights: True keeps the samples' per-point weights (NS2dData(point_weights=True); an NS2dData passed
+    in must have been built with them) as w_all [sum N], packed like y_all: DeviceLoader then gathers a `w`
+    beside every `y`, and Normalizer.fit weighs the target statistics.  False (default): w_all is None."""
 
-    def __init__(self, samples_or_data, device):
-        ds = samples_or_data if isinstance(samples_or_data, NS2dData) else NS2dData(samples_or_data)
+    def __init__(self, samples_or_data, device, point_weights=False):
+        ds = samples_or_data if isinstance(samples_or_data, NS2dData) else NS2dData(samples_or_data, point_weights)
         if len(ds) == 0:
             raise ValueError("DeviceDataset: no samples")
-        xs, ys, thetas, fnl = zip(*ds.items)
+        if point_weights and not getattr(ds, "point_weights", False):
+            raise ValueError("DeviceDataset(point_weights=True): the NS2dData was built without point weights")
+        xs, ys, thetas, fnl, *ws = zip(*ds.items)
         self.device = torch.device(device)
         put = lambda parts: torch.cat(parts).float().contiguous().to(self.device)
         self.x_off = _offsets(x.shape[0] for x in xs)
         self.x_all, self.y_all = put(xs), put(ys)
+        self.w_all = put(ws[0]) if point_weights else None
         # collate_packed's expression, so a gathered row carries the bits of a collated one
         self.theta = torch.tensor(np.stack([np.atleast_1d(np.asarray(t, dtype=np.float64)) for t in thetas])) \
             .float().contiguous().to(self.device)
@@ -253,24 +297,34 @@ class Normalizer:
     @classmethod
     def fit(cls, dataset, x=True, theta=True, fns=True, y=True, eps=1e-8):
         """Statistics over a DeviceDataset's arrays on its device (two small kernels per array on the current
-        stream, nothing read back)."""
+        stream, nothing read back).  A dataset with point weights (DeviceDataset(point_weights=True)) gets the
+        WEIGHTED statistics of its targets (gnot_channel_stats_weighted: mean = sum w y / sum w, the
+        reliability-weights variance, rows of weight zero not read -- a NaN under a mask is harmless); x, theta
+        and the input functions are model inputs whatever their weight and stay unweighted."""
         if not dataset.x_all.is_cuda:
             raise RuntimeError("gnot_amd.Normalizer.fit computes on a ROCm GPU only (libgnot_hip.so); "
                                "from_stats builds one from host statistics")
         lib = _lib.load()
 
-        def block(src, on):
+        def block(src, on, w=None):
             rows, C = src.shape
             if not on:
                 return cls.identity(C, src.device)
             stats = torch.empty((3, C), dtype=torch.float32, device=src.device)
-            work = torch.empty(lib.gnot_channel_stats_work_floats(rows, C), dtype=torch.float32, device=src.device)
             stream = ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
-            _lib.check(lib.gnot_channel_stats(src.data_ptr(), rows, C, eps, work.data_ptr(), stats.data_ptr(), stream))
+            if w is None:
+                work = torch.empty(lib.gnot_channel_stats_work_floats(rows, C), dtype=torch.float32, device=src.device)
+                _lib.check(lib.gnot_channel_stats(src.data_ptr(), rows, C, eps, work.data_ptr(), stats.data_ptr(),
+                                                  stream))
+            else:
+                work = torch.empty(lib.gnot_channel_stats_weighted_work_floats(rows, C), dtype=torch.float32,
+                                   device=src.device)
+                _lib.check(lib.gnot_channel_stats_weighted(src.data_ptr(), w.data_ptr(), rows, C, eps, work.data_ptr(),
+                                                           stats.data_ptr(), stream))
             return stats
 
-        return cls(block(dataset.x_all, x), block(dataset.theta, theta), block(dataset.y_all, y),
-                   [block(f, fns) for f in dataset.fn_all])
+        return cls(block(dataset.x_all, x), block(dataset.theta, theta),
+                   block(dataset.y_all, y, getattr(dataset, "w_all", None)), [block(f, fns) for f in dataset.fn_all])
 
     @classmethod
     def from_stats(cls, x, theta, y, fns=(), eps=1e-8, device="cpu"):
@@ -394,6 +448,9 @@ class DeviceLoader:
     through gnot_gather_rows_affine -- normalised in the copy, bit for bit Normalizer.encode_batch of the plain
     batch -- and y stays raw (plain gather), for a loss that holds the same normalizer.  None (default): the
     calls above, unchanged.
+    A dataset with point weights (DeviceDataset(point_weights=True)) adds `w` [sum k] to every batch, gathered
+    through x's table like y (one more gnot_gather_rows, one channel), so a points_per_mesh subsample carries
+    the weights of the rows it drew; the tables are the same.  Without weights a batch has no such key.
     Padded batches (collate_padded) and slicing a loader over ranks are out of scope: packed batches, one
     process's whole dataset."""
 
@@ -465,5 +522,7 @@ class DeviceLoader:
                        fns=[self._gather(f, t, dev_table(2 + i), o[-1], st)
                             for i, (f, t, o, st) in enumerate(zip(ds.fn_all, b["fns"], b["fn_offs"], sfn))],
                        fn_offs=b["fn_offs"])
+            if getattr(ds, "w_all", None) is not None:      # the rows y took: x's table, one channel
+                out["w"] = self._gather(ds.w_all.view(-1, 1), b["x"], dev_table(0), b["x_off"][-1]).view(-1)
             r0 += (2 + len(ds.fn_all)) * B
             yield out

@@ -42,6 +42,7 @@
 import contextlib
 import ctypes
 import fnmatch
+import inspect
 import math
 import os
 
@@ -84,7 +85,7 @@ class RelL2Loss(torch.nn.Module):
     (no de-normalised copy of the prediction, the gradient scaled by std_y in the same kernel).  None
     (default): the plain entry.  The point-sharded losses of parallel.py take no normalizer."""
 
-    _entry, _work_floats = "gnot_rel_l2_loss", "gnot_rel_l2_work_floats"
+    _entry, _work_floats, _kind = "gnot_rel_l2_loss", "gnot_rel_l2_work_floats", "rel2"
 
     def __init__(self, normalizer=None):
         super().__init__()
@@ -92,13 +93,15 @@ class RelL2Loss(torch.nn.Module):
         self.normalizer = normalizer
         self._stats = None         # the normalizer's y block on the predictions' device
 
-    def _geometry(self, x_off, predictions):
-        """(device offsets, work buffer, host offsets) of the packed geometry x_off, cached for the last one"""
-        key = (tuple(int(v) for v in x_off), predictions.shape[1], predictions.device)
+    def _geometry(self, x_off, predictions, weighted=False):
+        """(device offsets, work buffer, host offsets) of the packed geometry x_off, cached for the last one;
+        weighted: the work buffer of the weighted entry (gnot_lp_loss_weighted_work_floats)"""
+        key = (tuple(int(v) for v in x_off), predictions.shape[1], predictions.device) + ((True,) if weighted else ())
         if key not in self._cache:
             B = len(key[0]) - 1
             oh = (ctypes.c_int64 * (B + 1))(*key[0])
-            n = getattr(_lib.load(), self._work_floats)(oh, B, key[1])
+            n = getattr(_lib.load(), "gnot_lp_loss_weighted_work_floats" if weighted else self._work_floats)(
+                oh, B, key[1])
             # pinned source + non_blocking: a new geometry must not stall the host on the stream
             # (a pageable copy would); the pinned tensor lives in the cache entry past the copy
             pinned = torch.tensor(key[0], dtype=torch.int64).pin_memory()
@@ -118,9 +121,34 @@ class RelL2Loss(torch.nn.Module):
                              f"channels, the prediction {predictions.shape[1]}")
         return self._stats
 
-    def forward(self, x_off, predictions, targets):
+    def _point_weights(self, point_weights, predictions):
+        """`point_weights` as the contiguous fp32 [rows] tensor the weighted entry reads (a constant: detached), or
+        ValueError -- host checks only, before any GPU work"""
+        who = f"{type(self).__name__}: point_weights"
+        rows = predictions.shape[0]
+        if not torch.is_tensor(point_weights) or not point_weights.is_floating_point():
+            raise ValueError(f"{who} must be a float tensor [rows] or [rows, 1]")
+        if tuple(point_weights.shape) not in ((rows,), (rows, 1)):
+            raise ValueError(f"{who} have shape {tuple(point_weights.shape)}, the prediction has {rows} rows "
+                             f"(expected [{rows}] or [{rows}, 1])")
+        if point_weights.device != predictions.device:
+            raise ValueError(f"{who} are on {point_weights.device}, the prediction on {predictions.device}")
+        return point_weights.detach().reshape(-1).contiguous().float()
+
+    def forward(self, x_off, predictions, targets, point_weights=None):
+        """point_weights: one weight w_n >= 0 per query point, a float tensor [rows] or [rows, 1] on the
+        predictions' device (another shape or device: ValueError before any GPU work) -- a quadrature weight, a
+        mask: sum_n becomes sum_n w_n, a mean over points divides by sum w, and a row of weight zero is not read
+        (gnot_lp_loss_weighted; a NaN target under a mask is harmless).  A constant: no gradient flows to it.
+        None (default): the unweighted call, exactly."""
+        if point_weights is not None:
+            point_weights = self._point_weights(point_weights, predictions)
         if not predictions.is_cuda:
             raise RuntimeError(f"gnot_amd.{type(self).__name__} runs on a ROCm GPU only (libgnot_hip.so)")
+        if point_weights is not None:
+            off_dev, work, off_host = self._geometry(x_off, predictions, weighted=True)
+            return _NativeLpLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, off_host,
+                                       work, self._kind, None, self._y_stats(predictions), None, point_weights)
         off_dev, work, off_host = self._geometry(x_off, predictions)
         stats = self._y_stats(predictions)
         if stats is None:
@@ -136,31 +164,35 @@ class MSELoss(RelL2Loss):
     the loss and d loss/d pred.  Not torch.nn.MSELoss: every sample weighs the same whatever its size.
     A sample without points is refused (its mean is undefined)."""
 
-    _entry, _work_floats = "gnot_mse_loss", "gnot_mse_work_floats"
+    _entry, _work_floats, _kind = "gnot_mse_loss", "gnot_mse_work_floats", "mse"
 
 
 class _NativeLpLoss(torch.autograd.Function):
     """gnot_lp_loss: the loss, d loss / d pred where pred needs it, and the unweighted terms into `terms`
-    ([B, C], or None) in the same pass"""
+    ([B, C], or None) in the same pass.  point_w (fp32 [rows] on pred's device, or None): the same through
+    gnot_lp_loss_weighted, `work` sized for it."""
 
     @staticmethod
-    def forward(ctx, pred, tgt, off_dev, off_host, work, kind, weights, stats, terms):
+    def forward(ctx, pred, tgt, off_dev, off_host, work, kind, weights, stats, terms, point_w=None):
         B = len(off_host) - 1
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
         dpred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
         oh = (ctypes.c_int64 * (B + 1))(*off_host)
         s = ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
         ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(_lib.load().gnot_lp_loss(pred.data_ptr(), tgt.data_ptr(), off_dev.data_ptr(), oh, B, pred.shape[1],
-                                            _lib.LP_KINDS[kind], ptr(weights), ptr(stats), work.data_ptr(),
-                                            loss.data_ptr(), ptr(terms), ptr(dpred), s))
+        tail = (off_dev.data_ptr(), oh, B, pred.shape[1], _lib.LP_KINDS[kind], ptr(weights), ptr(stats),
+                work.data_ptr(), loss.data_ptr(), ptr(terms), ptr(dpred), s)
+        if point_w is None:
+            _lib.check(_lib.load().gnot_lp_loss(pred.data_ptr(), tgt.data_ptr(), *tail))
+        else:
+            _lib.check(_lib.load().gnot_lp_loss_weighted(pred.data_ptr(), tgt.data_ptr(), point_w.data_ptr(), *tail))
         ctx.save_for_backward(dpred) if dpred is not None else None
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
-        return (dpred * g,) + (None,) * 8
+        return (dpred * g,) + (None,) * 9
 
 
 class LpLoss(RelL2Loss):
@@ -203,9 +235,11 @@ class LpLoss(RelL2Loss):
         w = "" if self.component_weights is None else f", w={self.component_weights}"
         return f"LpLoss({self.kind}{w})"
 
-    def _run(self, x_off, predictions, targets, want_terms):
+    def _run(self, x_off, predictions, targets, want_terms, point_weights=None):
         """(loss, terms or None); every refusal the host can make comes before any GPU work"""
         C = predictions.shape[1]
+        if point_weights is not None:
+            point_weights = self._point_weights(point_weights, predictions)
         if self.kind in ("relinf", "linf") and predictions.requires_grad and torch.is_grad_enabled():
             raise ValueError(f"LpLoss({self.kind}) is a metric only: it has no gradient, and this prediction requires "
                              "one (call it under torch.no_grad() or on a detached prediction)")
@@ -213,26 +247,28 @@ class LpLoss(RelL2Loss):
             raise ValueError(f"LpLoss: {len(self.component_weights)} component_weights, the prediction has {C} channels")
         if not predictions.is_cuda:
             raise RuntimeError("gnot_amd.LpLoss runs on a ROCm GPU only (libgnot_hip.so)")
-        off_dev, work, off_host = self._geometry(x_off, predictions)
+        off_dev, work, off_host = self._geometry(x_off, predictions, weighted=point_weights is not None)
         stats = self._y_stats(predictions)
         if self.component_weights is not None and (self._w is None or self._w.device != predictions.device):
             self._w = torch.tensor(self.component_weights, dtype=torch.float32, device=predictions.device)
         terms = torch.empty(len(off_host) - 1, C, dtype=torch.float32, device=predictions.device) if want_terms else None
         loss = _NativeLpLoss.apply(predictions.contiguous().float(), targets.contiguous().float(), off_dev, off_host,
-                                   work, self.kind, self._w, stats, terms)
+                                   work, self.kind, self._w, stats, terms, point_weights)
         return loss, terms
 
-    def forward(self, x_off, predictions, targets):
-        return self._run(x_off, predictions, targets, False)[0]
+    def forward(self, x_off, predictions, targets, point_weights=None):
+        """point_weights: as in RelL2Loss.forward -- the terms above with sum_n w_n in place of sum_n, sum w in
+        place of N_b and the maxima over the rows with w_n > 0 (gnot_lp_loss_weighted)"""
+        return self._run(x_off, predictions, targets, False, point_weights)[0]
 
-    def loss_and_terms(self, x_off, predictions, targets):
+    def loss_and_terms(self, x_off, predictions, targets, point_weights=None):
         """(loss, terms [B, C]) of one pass; the loss is forward()'s, bit for bit, and differentiable like it"""
-        return self._run(x_off, predictions, targets, True)
+        return self._run(x_off, predictions, targets, True, point_weights)
 
-    def terms(self, x_off, predictions, targets):
-        """the unweighted e[b, c] as a [B, C] device tensor (no_grad; they do not depend on the weights)"""
+    def terms(self, x_off, predictions, targets, point_weights=None):
+        """the e[b, c] as a [B, C] device tensor (no_grad; they do not depend on the component weights)"""
         with torch.no_grad():
-            return self._run(x_off, predictions, targets, True)[1]
+            return self._run(x_off, predictions, targets, True, point_weights)[1]
 
 
 # ------------------------------------------------------------------ OneCycleLR (main.py:52)
@@ -836,6 +872,22 @@ def _forward_batch(model, batch, dev, encoder=None):
     return model.forward_packed(x, x_off, theta, fns, fn_offs), x_off, y
 
 
+def _point_weight_args(batch, dev, fn):
+    """{"point_weights": w on the device} for a batch that carries per-point weights (the key `w`: collate_packed
+    on 5-tuple items, a DeviceLoader over a dataset with weights), {} for every other batch -- the keyword of the
+    call `fn` (a loss's forward / loss_and_terms / terms) that follows.  A callable without that keyword is a
+    TypeError that says so: weighted data must not train on an unweighted loss in silence."""
+    if "w" not in batch:
+        return {}
+    target = fn.forward if isinstance(fn, torch.nn.Module) else fn
+    params = inspect.signature(target).parameters
+    if "point_weights" not in params and not any(p.kind is p.VAR_KEYWORD for p in params.values()):
+        name = type(fn).__name__ if isinstance(fn, torch.nn.Module) else getattr(fn, "__qualname__", repr(fn))
+        raise TypeError(f"the batch carries point weights (its key 'w'), but {name} takes no point_weights keyword: "
+                        "use RelL2Loss / MSELoss / LpLoss, give the loss the keyword, or load the data without weights")
+    return {"point_weights": batch["w"].to(dev)}
+
+
 @contextlib.contextmanager
 def _eval_mode(model):
     """the model in eval mode (no attention dropout, as nn.Dropout), its `training` flag restored on exit"""
@@ -906,9 +958,10 @@ def _evaluate(model, loader, loss_fn, encoder, tables=None):
         for batch in loader:
             pred, off, y = _forward_batch(model, batch, dev, encoder)
             if tables is None:
-                vals.append(loss_fn(off, pred, y))
+                vals.append(loss_fn(off, pred, y, **_point_weight_args(batch, dev, loss_fn)))
             else:
-                loss, terms = loss_fn.loss_and_terms(off, pred, y)
+                loss, terms = loss_fn.loss_and_terms(off, pred, y,
+                                                     **_point_weight_args(batch, dev, loss_fn.loss_and_terms))
                 vals.append(loss)
                 tables.append(terms)
     vals = _read_back(vals)
@@ -928,7 +981,7 @@ def evaluate_table(model, loader, kind="rel2", normalizer=None):
     with torch.no_grad(), _eval_mode(model):
         for batch in loader:
             pred, off, y = _forward_batch(model, batch, dev, encoder)
-            tables.append(loss_fn.terms(off, pred, y))
+            tables.append(loss_fn.terms(off, pred, y, **_point_weight_args(batch, dev, loss_fn.terms)))
     return torch.cat(tables).cpu() if tables else torch.empty(0, 0)
 
 
@@ -970,7 +1023,7 @@ def _accum_step(model, eng, opt, loss_fn, group, dev, encoder=None):
     vals = []
     for i, (batch, w) in enumerate(zip(group, weights)):
         pred, off, y = _forward_batch(model, batch, dev, encoder)
-        loss = loss_fn(off, pred, y)
+        loss = loss_fn(off, pred, y, **_point_weight_args(batch, dev, loss_fn))
         # the first micro-batch overwrites the arena (no clear), the others add; only the last one reduces
         with model.backward_options(accumulate=i > 0, reduce=i == len(group) - 1):
             (loss * w).backward()
@@ -1157,7 +1210,7 @@ def fit(model, train_loader, test_loader=None, epochs=100, lr=1e-3, per_epoch_sc
             if accum_steps == 1:
                 for batch in train_loader:
                     pred, off, y = _forward_batch(model, batch, dev, enc_train)
-                    loss = loss_fn(off, pred, y)
+                    loss = loss_fn(off, pred, y, **_point_weight_args(batch, dev, loss_fn))
                     loss.backward()
                     opt.step(eng.grad_flat)
                     if not per_epoch_schedule:

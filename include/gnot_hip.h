@@ -573,6 +573,43 @@ int gnot_lp_loss(const float* pred, const float* tgt, const int64_t* off_dev, co
                  int kind, const float* comp_weights, const float* out_stats, float* work, float* loss, float* terms,
                  float* dpred, void* stream);
 
+/* gnot_lp_loss with one weight per query point: point_w is a DEVICE array [rows] (rows = off[B]) of weights
+ * w_n >= 0 -- FEM lumped-mass or quadrature weights, a 0/1 mask, anything else -- and the term of (sample b,
+ * channel c) becomes, with d as in gnot_lp_loss (out_stats included),
+ *   GNOT_LP_REL2    sqrt(sum w d^2 / sum w t^2)          GNOT_LP_MSE   sum w d^2 / sum w
+ *   GNOT_LP_REL1    sum w |d| / sum w |t|                GNOT_LP_L1    sum w |d| / sum w
+ *   GNOT_LP_RELINF  max_{w>0} |d| / max_{w>0} |t|        GNOT_LP_LINF  max_{w>0} |d|
+ * loss, comp_weights, terms, the refusals and the launch structure are gnot_lp_loss's (three launches at most,
+ * fixed-order reductions, no atomics, no host synchronisation, capturable); dpred is the exact derivative: w_n
+ * multiplies the element's gradient and the mean kinds divide by sum w where N_b stood.
+ *   - A row with w_n == 0 contributes nothing and is not read into any sum: a NaN or Inf in pred or tgt there
+ *     (a masked target) changes no bit of loss, terms or any other row's gradient, and its own dpred elements are
+ *     exact zeros.
+ *   - Every w_n == 1.0f gives the bits of gnot_lp_loss -- loss, terms and dpred, every kind, with and without
+ *     comp_weights / out_stats -- while a sample has fewer than 2^24 rows (sum w is then N_b exactly in fp32).
+ *   - Multiplying every weight of a sample by one power of two (no overflow, no denormals) changes no bit.
+ * point_w is not validated (that would take a host synchronisation): a negative or NaN weight counts as zero,
+ * and a sample whose weights are all zero gives 0 / 0, like an all-zero target channel of a relative kind.  A
+ * null point_w is GNOT_E_INVALID; every host check of gnot_lp_loss applies unchanged.  work: device scratch of
+ * gnot_lp_loss_weighted_work_floats(off_host, B, C) floats (the per-split partials of mse / l1 carry sum w). */
+size_t gnot_lp_loss_weighted_work_floats(const int64_t* off_host, int B, int C);
+int gnot_lp_loss_weighted(const float* pred, const float* tgt, const float* point_w, const int64_t* off_dev,
+                          const int64_t* off_host, int B, int C, int kind, const float* comp_weights,
+                          const float* out_stats, float* work, float* loss, float* terms, float* dpred, void* stream);
+
+/* gnot_channel_stats with one weight per row, w: DEVICE [rows], w >= 0.  With V1 = sum w and V2 = sum w^2,
+ * mean[c] = sum w v / V1 and std[c]^2 = sum w (v - mean)^2 / (V1 - V2 / V1), the reliability-weights estimator
+ * (rows - 1 at w == 1); rstd, eps and the constant-channel rule are gnot_channel_stats's, and a channel with
+ * V1 - V2 / V1 <= 0 (one weighted row) is constant.  Rows with w == 0 are not read (a NaN there is harmless); the
+ * weights are not validated, and no weighted row at all gives mean = 0 / 0.  The same scheme: slices of 4096
+ * rows reduced about a pivoted mean (the pivot is the slice's first row with w > 0; a slice without one is
+ * skipped) and merged about the global mean, never E[x^2] - E[x]^2; two launches, fixed order, no atomics,
+ * capturable.  work: gnot_channel_stats_weighted_work_floats(rows, C) floats.  The refusals of
+ * gnot_channel_stats, and a null w. */
+size_t gnot_channel_stats_weighted_work_floats(int64_t rows, int C);
+int gnot_channel_stats_weighted(const float* src, const float* w, int64_t rows, int C, float eps, float* work,
+                                float* stats, void* stream);
+
 /* Live kernel timing for the bench's roofline:while enabled, every launch of kernel class `kind`
  * ("moe_fwd" fused expert chains forward, "moe_bwd" their backward, "wgrad" weight-gradient GEMMs;
  * "" disables) is bracketed by hipEvents on its stream.  gnot_profile_read synchronizes on those

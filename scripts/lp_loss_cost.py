@@ -36,6 +36,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=200, help="calls per timed block")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--weighted", action="store_true",
+                    help="also time gnot_lp_loss_weighted (rel2, mse; weights of ones and with a quarter zeros)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     lib = _lib.load()
@@ -72,6 +74,17 @@ def main():
                      "mse": lambda: lib.gnot_mse_loss(*head, *tail),
                      "lp_rel2": lp("rel2", None, None), "lp_rel2_terms": lp("rel2", None, terms),
                      "lp_rel1_w": lp("rel1", w, None), "lp_rel1_w_terms": lp("rel1", w, terms)})
+        if args.weighted:      # gnot_lp_loss_weighted beside the unweighted entry of the same kind: one more float a row
+            pw = torch.rand(ROWS, device=dev, generator=gen) * 2.9 + 0.1
+            pw[torch.rand(ROWS, device=dev, generator=gen) < 0.25] = 0.0
+            ones = torch.ones(ROWS, device=dev)
+            work_w = torch.empty(lib.gnot_lp_loss_weighted_work_floats(oh, B, C), device=dev)
+            lpw = lambda kind, pts: (lambda: lib.gnot_lp_loss_weighted(
+                P(pred), P(tgt), P(pts), P(off_dev), oh, B, C, _lib.LP_KINDS[kind], None, None, P(work_w), P(loss), None,
+                P(dpred), s))
+            runs.update({"lp_mse": lp("mse", None, None), "weighted_rel2_ones": lpw("rel2", ones),
+                         "weighted_rel2_quarter_zeros": lpw("rel2", pw), "weighted_mse_ones": lpw("mse", ones),
+                         "weighted_mse_quarter_zeros": lpw("mse", pw)})
         times = {k: [] for k in runs}
         for rep in range(args.warmup + args.reps):
             for k, fn in runs.items():               # interleaved: every repetition times a block of each

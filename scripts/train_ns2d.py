@@ -93,6 +93,11 @@ def parse_args(argv=None):
                     help="normalise per channel to zero mean and unit variance with the training set's statistics: "
                          "all four arrays, or a comma-separated subset of x,theta,fns,y.  Loss and metric stay in "
                          "physical units and the checkpoint has the statistics folded in (implies --device-data)")
+    ap.add_argument("--point-weights", action="store_true",
+                    help="read a fifth entry W [N] of every sample, one weight >= 0 per query point (quadrature "
+                         "weights, a 0/1 mask): the loss, the test metric and, with --normalize, the target statistics "
+                         "weigh the points with it, and rows of weight zero are never read (their targets may be "
+                         "NaN).  For --device-data and the host loaders alike (implies --packed; default: off)")
     ap.add_argument("--x-fourier", type=int, default=0, metavar="N",
                     help="embed every coordinate v as [v, cos(2^k v), sin(2^k v)], k = -N .. N, inside the model "
                          "(4 N + 3 columns per channel, N up to 8; default 0: raw coordinates)")
@@ -157,6 +162,10 @@ def parse_args(argv=None):
                      "from --normalize")
     args.device_data = args.device_data or args.points_per_mesh is not None or norm is not None
     args.normalize = norm
+    if args.point_weights:
+        if args.synthetic:
+            ap.error("--point-weights reads the samples' fifth entry; --synthetic meshes have none")
+        args.packed = True       # padded batches take no weights
     return args
 
 
@@ -176,8 +185,8 @@ def main():
         tr = data.NS2dData([data.synthetic_sample(rng, int(rng.integers(1000, 4000))) for _ in range(args.synthetic)])
         te = data.NS2dData([data.synthetic_sample(rng, int(rng.integers(1000, 4000))) for _ in range(max(4, args.synthetic // 8))])
     else:
-        tr, te = data.NS2dData(args.train), data.NS2dData(args.test)
-    x0, y0, th0, f0 = tr[0]
+        tr, te = data.NS2dData(args.train, args.point_weights), data.NS2dData(args.test, args.point_weights)
+    x0, y0, th0, f0 = tr[0][:4]
     dev = torch.device("cuda", args.gpu_id)
     model = GNOT(x0.shape[1], len(np.atleast_1d(th0)), f0[0].shape[1], y0.shape[1], args.n_attn_layers,
                  args.n_attn_hidden_dim, args.n_mlp_num_layers, args.n_mlp_hidden_dim, args.n_input_hidden_dim,
@@ -190,12 +199,12 @@ def main():
                                                     else data.collate_padded)
     nz = None
     if args.device_data:       # the test set stays at full resolution
-        dtr = data.DeviceDataset(tr, dev)
+        dtr = data.DeviceDataset(tr, dev, args.point_weights)
         if norm is not None:   # the training set's statistics serve both loaders
             nz = data.Normalizer.fit(dtr, **{k: k in norm for k in ("x", "theta", "fns", "y")})
         loaders = (data.DeviceLoader(dtr, args.batch, shuffle=True, points_per_mesh=args.points_per_mesh,
                                      normalizer=nz),
-                   data.DeviceLoader(data.DeviceDataset(te, dev), args.batch, normalizer=nz))
+                   data.DeviceLoader(data.DeviceDataset(te, dev, args.point_weights), args.batch, normalizer=nz))
     else:
         loaders = dl(tr, True), dl(te, False)
     _, test = train.fit(model, *loaders, epochs=args.epochs,
